@@ -20,6 +20,10 @@ Workloads (BASELINE.json configs):
   --input index         the batch carries index lists and the features are gathered from a device-resident table INSIDE the
                         timed step (segmm_gather_l1: gather + pad + mask + L1 normalisation); reports the gather's GB/s.
 
+Timed region: after the warm-up, EXACTLY --steps steps (--windows N cuts them into N windows; `value` = the median window rate).
+--dump-outputs DIR then writes what the last timed step computed (outputs and updated parameters, float32 .npy, <= 64 MB; inputs
+and initial parameters are seeded, so two builds run with the same arguments can be compared array for array).
+
 Prints ONE JSON line (rank 0) with the driver contract fields plus
   roofline     -- the dominant kernel: algorithmic FLOPs (or bytes) per launch / HIP-event duration on the launch's own stream,
                   measured live in a timed replay of the recorded step (`measured_in`; eager step modes: the same steps enqueued
@@ -45,12 +49,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# HIP multiplexes streams onto GPU_MAX_HW_QUEUES (default 4) in-order hardware queues.  A data-parallel rank has the main
-# stream, the engine's side stream, RCCL's stream and RCCL's internal ones: with 4 queues the RCCL stream shares a queue with
-# the main stream, and an all-reduce waiting for the side stream's weight gradients stalls the main stream behind it
-# (head-of-line blocking: 7.5 % of the step on one GPU, measured with a forced one-rank process group; 2.4 % with 8 queues).
-# Must be set before the HIP runtime initialises, i.e. before torch is imported; inherited by the ranks bench.py launches.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 PEAK_F32_MFMA_TFLOPS = 157.3          # v_mfma_f32_32x32x2_f32, MI355X_MICROARCH.md
 PEAK_BF16_MFMA_TFLOPS = 2500.0        # dense bf16 / fp16 MFMA, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0                 # HBM3E spec, MI355X_MICROARCH.md
@@ -67,11 +65,15 @@ def f_train_flops(D_in, d, S, Lt, N, id_mode=False):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps: the timed region of `value` runs exactly this many steps")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5,
-                    help="timed windows of --steps steps each, run back to back after the warm-up; `value` is the MEDIAN window, "
-                         "value_min / value_max the slowest / fastest (box noise and clock transients stay visible)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="cut the --steps timed steps into this many windows of (near) equal length, run back to back after the warm-up; "
+                         "`value` is the MEDIAN window rate, value_min / value_max the slowest / fastest (box noise and clock transients stay "
+                         "visible); at most --steps windows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its output tensors and the updated parameters) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all; see dump_outputs()")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
     ap.add_argument("--batch", type=int, default=None, help="rows per GPU (default: 512; config 3: 1024)")
     ap.add_argument("--global-batch", type=int, default=None, help="total rows over all GPUs (config 4: 2048)")
@@ -102,14 +104,20 @@ def parse_args():
                     help="gloo: CPU-staged collectives, lets several ranks share one GPU (CI rehearsal of the N > 1 path)")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the sustained leg (value_sustained: >= 2000 steps / >= 8 s in one window)")
+    ap.add_argument("--sustained", action="store_true",
+                    help="add the sustained leg (value_sustained: one window of >= 2000 steps / >= 8 s after the timed region; its step count "
+                         "is set by the clock, not by --steps, so it is off by default)")
+    ap.add_argument("--no-sustained", action="store_true", help="(the default) no sustained leg")
     ap.add_argument("--no-index-leg", action="store_true", help="skip the index-input leg (value_index_input: the product's input path)")
     ap.add_argument("--no-f32-engine", action="store_true")
     ap.add_argument("--cpu-rows", type=int, default=128)
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.windows < 1:
+        ap.error("--steps and --windows must be >= 1")
+    return args
 
 
 def relaunch(args):
@@ -242,6 +250,34 @@ def cpu_baseline(args, w, h):
             "sample": "median of %d timed steps (%d warm-up) of B=%d rows, same S/D/Lt/N, dropout 0.1, dead layers executed like the "
                       "reference, torch-CPU %d threads of %d host threads%s"
                       % (args.cpu_steps, args.cpu_warmup, Bc, cores, host, sweep or " (more threads ran slower on this box)")}
+
+
+DUMP_BYTES = 60 << 20          # array data of --dump-outputs; with the .npy headers the directory stays under 64 MB
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step -- the floating-point tensors of the step's
+    output dict (`loss`, its terms, `logits`) and every parameter as the step's AdamW left it (`param.<name>`) -- as path/<name>.npy
+    in float32 (float64 tensors stay float64).  Smallest first, every array gets an equal share of what is left of DUMP_BYTES: a
+    longer one is replaced by a fixed sample of its flattened elements (indices from numpy's default_rng seeded with the array's
+    name and size, sorted), the same sample in every run, so two builds can be compared array for array."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = [(k, v) for k, v in out.items() if torch.is_tensor(v) and v.is_floating_point()]
+    arrays += [("param." + k, p) for k, p in model.named_parameters()]
+    arrays.sort(key=lambda a: (a[1].numel(), a[0]))
+    left = DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for i, (name, t) in enumerate(arrays):
+        t = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        cap = left // (len(arrays) - i) // t.element_size()
+        if t.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, t.numel())).encode()))
+            idx = np.sort(rng.choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        left -= t.numel() * t.element_size()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def csrc_sha16():
@@ -467,35 +503,41 @@ def main():
             args.recorded = False
             record_note = "eager, device-side step state (record() refused: %s)" % str(e)[:120]
     run(trainer, args.warmup)
-    # ---- the timed region: `windows` windows of EXACTLY `steps` steps, each bracketed by barrier + synchronize on both sides,
-    # MAX over ranks per window; `value` is the median window (value_min / value_max beside it)
+    # ---- the timed region: EXACTLY `steps` steps, cut into `windows` windows of (near) equal length, each bracketed by barrier +
+    # synchronize on both sides, MAX over ranks per window; `value` is the median window rate (value_min / value_max beside it)
+    n_win = min(args.windows, args.steps)
+    counts = [args.steps // n_win + (1 if i < args.steps % n_win else 0) for i in range(n_win)]
     win = []
     del host_s[:]
-    for wi in range(max(args.windows, 1)):
+    done = 0
+    for n in counts:
         barrier()
         t0 = time.perf_counter()
-        out = run(trainer, args.steps, args.warmup + wi * args.steps)
+        out = run(trainer, n, args.warmup + done)
         barrier()
         win.append(time.perf_counter() - t0)
+        done += n
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
     host_ms = 1e3 * sorted(host_s)[len(host_s) // 2] if host_s else 0.0
     loss = float(out["loss"].detach())
     t = torch.tensor(win, dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    win = sorted(float(x) for x in t.tolist())
-    elapsed = win[len(win) // 2]
-    rows_per_s = world * B * args.steps / elapsed
+    per_step = sorted(float(x) / n for x, n in zip(t.tolist(), counts))          # seconds per step of every window
+    step_s = per_step[len(per_step) // 2]
+    rows_per_s = world * B / step_s
 
-    # ---- sustained leg: the SAME step in ONE window of >= 2000 steps and >= 8 s (at most ~15 s), bracketed like the windows above,
-    # with the GPU's clock and power sampled from sysfs while it runs: what the part holds once it is warm and power-managed
+    # ---- sustained leg (--sustained): the SAME step in ONE window of >= 2000 steps and >= 8 s (at most ~15 s), bracketed like the
+    # windows above, with the GPU's clock and power sampled from sysfs while it runs: what the part holds once it is warm and
+    # power-managed
     sustained = None
-    if not args.no_sustained:
-        step_s = elapsed / args.steps
+    if args.sustained:
         n_sus = int(min(max(2000, math.ceil(8.0 / step_s)), max(math.ceil(15.0 / step_s), 200)))
         with SmiSampler(dev) as smi:
             barrier()
             ts0 = time.perf_counter()
-            run(trainer, n_sus, args.warmup + len(win) * args.steps)
+            run(trainer, n_sus, args.warmup + args.steps)
             barrier()
             ts = time.perf_counter() - ts0
         tt = torch.tensor([ts], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -507,7 +549,7 @@ def main():
                                                    "power1 of this GPU every 0.25 s during the window (null: sysfs not readable here)"}
 
     if inst is None:
-        inst = instrumented(args.warmup + len(win) * args.steps)
+        inst = instrumented(args.warmup + args.steps)
     psteps, prof, aprof, kprof, prof_elapsed = inst
     # ---- recorded step mode: the GEMM / attention launches are timed in a TIMED REPLAY of the recorded step itself -- the same C
     # launch sequences as the timed windows, cut at every GEMM / attention command with a HIP-event pair around it on the command's
@@ -549,10 +591,10 @@ def main():
                  "f16x3p": "f32 (products via scaled fp16x2 split, 22-bit operands, fp32 accumulate; operands pre-split by their producers)"}[engine]
         rec = {
             "metric": "train interactions/sec (segment-Transformer, B=512·S=40·D=768)",
-            "value": round(rows_per_s, 2), "value_min": round(world * B * args.steps / win[-1], 2), "value_max": round(world * B * args.steps / win[0], 2),
+            "value": round(rows_per_s, 2), "value_min": round(world * B / per_step[-1], 2), "value_max": round(world * B / per_step[0], 2),
             "value_sustained": sustained["value"] if sustained else None, "sustained": sustained,
-            "windows": len(win), "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "host_enqueue_ms_per_step": round(host_ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "windows": n_win, "unit": "interactions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * step_s, 4), "host_enqueue_ms_per_step": round(host_ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": dtype, "data": "synthetic",
             "config": {"workload": "%s: synthetic SegMM B=%d/GPU x S=%d x D_in=%d -> d=%d, h=%d, %d-layer segment encoder, %s/%s inputs, Lt=%d user "
                                    "tokens, interestBPR, dropout 0.1, AdamW; %d distinct batches rotated; input=%s"

@@ -17,6 +17,37 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    _rank_checks(rank, world, q)
+
+
+def _threaded_world(world, q):
+    """Every rank of a gloo world as a thread of THIS process: each thread gets a c10d world of its own (torch's ThreadLocalWorld
+    and thread isolation mode: default group, new_group and group names per thread) and a real gloo process group over one
+    in-process store.  A GPU box admits only a few processes with the GPU open, and every torch process that runs a backward
+    opens it (the autograd engine counts the devices), so eight rank processes cannot run there; eight threads in one can."""
+    import threading
+    from torch.testing._internal.distributed.multi_threaded_pg import ThreadLocalWorld
+    dist.distributed_c10d._world = ThreadLocalWorld()
+    torch._C._distributed_c10d._set_thread_isolation_mode(True)          # process-group name registry per thread, too
+    store = dist.HashStore()
+    errors = []
+
+    def rank_main(rank):
+        try:
+            dist.init_process_group("gloo", rank=rank, world_size=world, store=store)
+            _rank_checks(rank, world, q)
+        except BaseException as e:          # (reported by the process's exit code)
+            errors.append("rank %d: %r" % (rank, e))
+
+    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+
+
+def _rank_checks(rank, world, q):
     try:
         sys.path.insert(0, ROOT)
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -101,16 +132,14 @@ def test_dp_world2_gloo_matches_single_process():
 def test_dp_world8_gloo_matches_single_process():
     """The same check at the world size of BASELINE configs 4 / 5 (two rows per rank): eight gloo ranks on CPU -- label
     statistics gathered in rank order, two asynchronous gradient buckets, the row exchange of the id tables and the gathered
-    leave ranks -- against a single process on the whole batch (the only N = 8 run this repo can make)."""
+    leave ranks -- against a single process on the whole batch (the only N = 8 run this repo can make).  The
+    eight ranks are threads of one process (_threaded_world), so the test also runs on a GPU box."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 30500 + os.getpid() % 1000
-    procs = [ctx.Process(target=_worker, args=(r, 8, port, q)) for r in range(8)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(240)
-        assert p.exitcode == 0
+    p = ctx.Process(target=_threaded_world, args=(8, q))
+    p.start()
+    p.join(240)
+    assert p.exitcode == 0
     loss, ref_loss, gerr, gmax = q.get(timeout=5)
     assert abs(loss - ref_loss) < 1e-4 * max(1.0, abs(ref_loss))
     assert gerr < 1e-4 * gmax

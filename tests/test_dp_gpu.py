@@ -244,7 +244,7 @@ def test_bench_launcher_four_ranks_on_one_gpu():
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--config", "4", "--global-batch", "64",
-           "--dim", "64", "--heads", "4", "--lt", "12", "--steps", "3", "--warmup", "1", "--batches", "2",
+           "--dim", "64", "--heads", "4", "--lt", "12", "--steps", "3", "--warmup", "1", "--windows", "3", "--batches", "2",
            "--no-cpu-baseline", "--no-f32-engine", "--no-host-fed", "--no-probe"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
@@ -254,7 +254,7 @@ def test_bench_launcher_four_ranks_on_one_gpu():
     assert p.stdout.count("\n") == 1 and p.stdout.startswith('{"metric"'), p.stdout
     rec = json.loads(p.stdout)
     assert rec["n_gpus"] == 4 and rec["scaling"] == "weak" and rec["value"] > 0
-    assert rec["windows"] == 5 and rec["value_min"] <= rec["value"] <= rec["value_max"]
+    assert rec["windows"] == 3 and rec["steps"] == 3 and rec["value_min"] <= rec["value"] <= rec["value_max"]
     assert rec["config"]["global_batch"] == 64 and rec["config"]["rows_per_gpu"] == 16
     assert rec["config"]["replicas_identical"] is True
     assert rec["config"]["parallelism"].startswith("dp4")

@@ -2,7 +2,6 @@
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from segmminterest_amd import hipabi as H
 from segmminterest_amd.synth import make_batch
