@@ -307,6 +307,15 @@ __device__ __forceinline__ float wave_scan_incl(float v, int lane) {
     }
     return v;
 }
+// inclusive suffix sum over the wave: lane k gets v_k + v_(k+1) + ... + v_63
+__device__ __forceinline__ float wave_suffix_incl(float v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_down(v, o, 64);
+        if (lane + o < 64) v += t;
+    }
+    return v;
+}
 
 // ---- raw buffer addressing: one resource descriptor (4 SGPRs) per tensor, a 32-bit per-lane byte offset and a
 // scalar byte offset per access -- no 64-bit per-lane address arithmetic, and reads beyond [p, p + bytes) return 0

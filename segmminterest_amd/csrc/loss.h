@@ -59,7 +59,12 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
     const int v = (int)wave_sum((in && gt == 1) ? 1.f : 0.f);       // view length = index of the leave segment
     const int dur = (int)wave_sum(mf);
     const float p = sigmoidf_(z);
-    const float logp = in ? logf(p) : 0.f;
+    // survival h_t = sum_(k <= t) log p_k, surv = exp(h), hazard = 1 - surv (:511).  Evaluated in forms that keep their relative
+    // accuracy where the literal ones cancel: log p = min(z, 0) - log1p(exp(-|z|)) (logf(p) of a p rounded to 1 keeps only
+    // ulp(1) of a log p ~ -exp(-z)), hazard = -expm1(h), and 1 - p = sigmoid(-z) in the gradient chain below -- a leave right
+    // after segments with p ~ 1 has hazard ~ exp(-z), and d hazard / d logit carries 1 / hazard (tests/test_loss_gpu.py)
+    const float q = sigmoidf_(-z);                       // 1 - p
+    const float logp = in ? fminf(z, 0.f) - log1pf(expf(-fabsf(z))) : 0.f;
     const float h = wave_scan_incl(logp, lane);
     const float surv = in ? expf(h) : 0.f;
     float dz = 0.f;          // d total / d z (this lane's position)
@@ -74,7 +79,8 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
         const bool neg = in && lane != v;
         const float mx = wave_max(neg ? z : -INFINITY);
         const float e = neg ? expf(z - mx) : 0.f;
-        const float w = e / wave_sum(e);
+        const float se = wave_sum(e);
+        const float w = se > 0.f ? e / se : 0.f;         // S = 1: no negative lane -> w = 0, A clamps to 1e-8, zero gradient
         const float sg = neg ? sigmoidf_(z - pos) : 0.f;
         const float A = wave_sum(sg * w);
         const float Ac = fminf(fmaxf(A, 1e-8f), 1.0f - 1e-8f);
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
         }
     }
     // ---- huber (huber_loss :61-66 on [B] vs [B,1] => [B,B] broadcast, :540) and mse / mse2 (:552-558)
-    const float hz = m ? 1.f - surv : 0.f;
+    const float hz = m ? -expm1f(h) : 0.f;
     const float ssum_h = wave_sum(hz);                   // sum of masked hazard
     const float ssum = wave_sum(m ? surv : 0.f);         // sum of masked survival
     {
@@ -179,12 +185,16 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
             qs += a.coef[L_HAZARD] * (dh / Bg) * (-1.f);  // hz = 1 - surv
         }
     }
-    // ---- survival chain: d surv_j / d z_k = surv_j (1 - p_k) for k <= j  => suffix sum over j >= k
+    // ---- survival chain: d surv_j / d z_k = surv_j (1 - p_k) for k <= j  => suffix sum over j >= k.  Summed as a suffix scan: the
+    // row total minus a prefix scan cancels wherever the survival has dropped to ~0 (saturated logits), leaving an error of
+    // ulp(total) on gradients many orders of magnitude smaller (tests/test_loss_gpu.py).  The terms are carried times 2^64: a
+    // survival below fp32's normal range (h < -87) would otherwise enter as a subnormal of a few bits and be multiplied up by
+    // qs (a power-of-two scaling: exact wherever nothing underflows or overflows; |qs| <= 1e6 / batch keeps qs 2^64 finite).
     {
-        const float u = in ? qs * surv : 0.f;
-        const float c = wave_scan_incl(u, lane);
-        const float tot = __shfl(c, 63, 64);
-        if (in) dz += (1.f - p) * (tot - c + u);
+        const float sv = h < -80.f ? expf(h + 44.3614196f) : surv * 18446744073709551616.f;     // surv * 2^64 (64 ln 2 = 44.36)
+        const float u = in ? qs * sv : 0.f;
+        const float suf = wave_suffix_incl(u, lane);
+        if (in) dz += (q * suf) * 5.42101086242752217e-20f;                                      // * 2^-64
     }
     if (in) {
         a.logits_out[(size_t)row * S + lane] = z;

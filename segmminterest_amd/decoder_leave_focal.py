@@ -48,7 +48,9 @@ class LossSpec:
 
     One difference in error behaviour: a batch in which EVERY row is fully watched has no BPR negative -- the reference raises there
     (``neg_pred.max()`` of an empty tensor, decoder_leave_focal.py:213); the device-side loss returns ``interestBPR`` = 0 with zero
-    gradients (it has no host synchronisation to raise from)."""
+    gradients (it has no host synchronisation to raise from).  Likewise at S = 1 a row that leaves at segment 0 has no negative
+    lane at all (the reference raises on the empty ``neg_pred.max()``): the kernel takes the softmax weights as 0, so A = 0 clamps
+    to 1e-8, the row adds -log(1e-8) / (valid rows) to ``interestBPR`` and nothing to the gradient."""
 
     def __init__(self, model_cfg, S_hint=40):
         lst = list(model_cfg.loss_type_list)

@@ -1,0 +1,428 @@
+"""K8, the leave/skip losses (csrc/loss.h: label_stats -> loss_fwd_bwd -> loss_finish), through the C ABI against the float64
+oracle (oracle/segmm_oracle.compute_loss with autograd) under the rule of helpers.loss_check: every loss slot, the total and
+d total / d logits, at every in-domain label row, at sizes where the kernels' loops take more than one trip, and at logit
+magnitudes a trained model reaches.  Label statistics, the unpack of the data-parallel record and loss_finish's gmax / delayed
+scales are compared exactly.  Run with ``pytest -m gpu``.
+
+SEGMM_LOSS_RATIO_LOG=<file>: the worst |k - t| / allowance per quantity family of the run is written there (JSON)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import (LOGIT_REGIMES, LOSS_SLOTS, LOSS_WEIGHTS, ROOT, WORST_RATIO, all_label_rows, loss_cfg, loss_check,
+                     loss_compare, make_logits, oracle_loss)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+from segmminterest_amd.synth import make_labels  # noqa: E402
+
+ALL7 = ["interestBPR", "surviveCE", "interestCE", "interestKL", "huber", "hazard"]
+ORDERS = {"focal_first": ["focal"] + ALL7, "focal_last": ALL7 + ["focal"], "no_focal": ALL7}
+# the loss lists of the reference configurations the golden fixtures were captured with (oracle/gen_golden.py)
+REAL_LISTS = (["interestBPR"], ["interestBPR", "surviveCE", "interestCE", "interestKL", "huber", "hazard"],
+              ["focal", "interestCE", "interestKL", "interestBPR"], ["interestCE", "interestKL", "surviveCE"],
+              ["interestBPR", "surviveCE"], ["focal", "interestBPR"])
+
+
+@pytest.fixture(scope="module", autouse=True)
+def ratio_log():
+    yield
+    path = os.environ.get("SEGMM_LOSS_RATIO_LOG")
+    if path:
+        with open(path, "w") as f:
+            json.dump(dict(sorted(WORST_RATIO.items())), f, indent=1)
+
+
+def _abi():
+    from segmminterest_amd import hipabi
+    hipabi.lib()
+    return hipabi
+
+
+def _spec(cfg):
+    """LossSpec of ``cfg``, checked against coef / enabled / rewrite flags derived here from the loss list by compute_loss's rules:
+    a loss is on iff listed (mse / mse2 always: logged); its weight is loss_weight[name], huber's is loss_weight['mse']; interestCE
+    / interestKL see focal's in-place label rewrite iff focal comes earlier in the list."""
+    from segmminterest_amd.decoder_leave_focal import LossSpec
+    lst = cfg["loss_type_list"]
+    w = cfg["loss_weight"]
+    enabled = [int(n in lst) for n in LOSS_SLOTS[:7]] + [1, 1]
+    coef = [float(w["mse" if n == "huber" else n]) if n in lst else 0.0 for n in LOSS_SLOTS[:7]] + [0.0, 0.0]
+
+    def after_focal(n):
+        return int("focal" in lst and n in lst and lst.index("focal") < lst.index(n))
+
+    sp = LossSpec(argparse.Namespace(loss_type_list=list(lst), loss_weight=dict(w), mask_loss=cfg["mask_loss"],
+                                     exposure_prob=list(cfg["exposure_prob"])))
+    assert sp.coef == coef and sp.enabled == enabled
+    assert (sp.rew_ce, sp.rew_kl, sp.has_focal, sp.use_mask) == (after_focal("interestCE"), after_focal("interestKL"),
+                                                                 "focal" in lst, cfg["mask_loss"])
+    assert sp.exposure == [float(x) for x in cfg["exposure_prob"]]
+    return sp
+
+
+def k8(z, gt, cfg, sd=None, stats=None):
+    """label_stats -> loss_fwd_bwd -> loss_finish on fp32 logits / int64 labels.  ``stats``: (v_all, v2_all, norms) of the global
+    batch on the device (data-parallel shard); otherwise label_stats of these rows."""
+    H = _abi()
+    sp = _spec(cfg)
+    B, S = gt.shape
+    gtd = gt.to(DEV).contiguous()
+    zd = z.float().to(DEV).contiguous()
+    out = {}
+    if stats is None:
+        v, v2, norms = (torch.full((n,), float("nan"), device=DEV) for n in (B, B, 3))
+        H.label_stats(gtd, B, S, int(sp.has_focal), v, v2, norms)
+        v_all, v2_all = v, v2
+        out.update(v=v.cpu(), v2=v2.cpu())
+    else:
+        v_all, v2_all, norms = stats
+    expo = torch.tensor(sp.exposure[:S], dtype=torch.float32, device=DEV)
+    bw = sd["bias_weight"].float().reshape(-1)[:S].contiguous().to(DEV) if sd is not None else None
+    bb = sd["bias_bias"].float().reshape(-1)[:S].contiguous().to(DEV) if sd is not None else None
+    lo, dl = torch.full((B, S), float("nan"), device=DEV), torch.full((B, S), float("nan"), device=DEV)
+    parts = torch.full((B, 12), float("nan"), device=DEV)
+    H.loss_fwd_bwd(B, S, zd, gtd, bw, bb, expo, sp.coef, sp.enabled, sp.rew_ce, sp.rew_kl, sp.use_mask, norms, v_all, v2_all,
+                   v_all.numel(), lo, dl, parts)
+    coef12 = torch.tensor(sp.coef + [0.0] * 3, dtype=torch.float32, device=DEV)
+    losses, total = torch.full((12,), float("nan"), device=DEV), torch.full((), float("nan"), device=DEV)
+    H.loss_finish(parts, B, coef12, losses, total)
+    torch.cuda.synchronize()
+    out.update(logits_out=lo.cpu(), dlogits=dl.cpu().double().numpy(), losses=losses.cpu(), parts=parts.cpu(),
+               slots=losses.cpu().double().numpy()[:9], total=float(total), norms=norms.cpu())
+    return out
+
+
+def _bias(S, seed):
+    """learnable_bias parameters on a 2^-10 grid: (s + 1) w + b is exact in fp32 however it is rounded or fused."""
+    g = torch.Generator().manual_seed(seed)
+    w = torch.round(torch.randn(1, S, generator=g) * 0.05 * 1024) / 1024
+    b = torch.round(torch.randn(1, S, generator=g) * 0.5 * 1024) / 1024
+    return {"bias_weight": w, "bias_bias": b}
+
+
+def _stats_host(gt, rewritten):
+    S = gt.shape[1]
+    v = (gt == 1).sum(1).float()
+    v2 = ((gt != -2) if rewritten else (gt >= 0)).sum(1).float()
+    return v, v2, torch.tensor([float((v < S).sum()), float(gt.shape[0]), float((gt != -2).sum())])
+
+
+def run_case(z, gt, cfg, sd=None, what="", max_edge_frac=0.02):
+    got = k8(z, gt, cfg, sd)
+    B, S = gt.shape
+    # logits incl. the position bias: exact (the bias is exact, z + bias one fp32 rounding either way)
+    ref_lo = z.float() if sd is None else z.float() + ((torch.arange(S, dtype=torch.float32) + 1) * sd["bias_weight"][0, :S]
+                                                      + sd["bias_bias"][0, :S])
+    assert torch.equal(got["logits_out"], ref_lo), what
+    v, v2, norms = _stats_host(gt, "focal" in cfg["loss_type_list"])
+    assert torch.equal(got["v"], v) and torch.equal(got["v2"], v2) and torch.equal(got["norms"], norms), what
+    # slots of losses that are not selected, and the 3 padding slots, are exactly 0
+    lst = cfg["loss_type_list"]
+    off = [i for i, n in enumerate(LOSS_SLOTS[:7]) if n not in lst] + [9, 10, 11]
+    assert float(got["losses"][off].abs().max()) == 0.0, what
+    t, r = oracle_loss(z, gt, cfg, sd), oracle_loss(z, gt, cfg, sd, dtype=torch.float32)
+    n_edge = loss_compare(got, t, r, cfg, what)
+    assert n_edge <= max(1, int(max_edge_frac * B)), (what, n_edge)
+    return got
+
+
+# ------------------------------------------------------------------ every in-domain label row, every logit regime
+_CASES = []
+for _S in (2, 7, 20, 33, 40, 63, 64):
+    for _reg in LOGIT_REGIMES:
+        for _order in (ORDERS if _S in (7, 40, 64) else ["focal_first"]):
+            _CASES.append((_S, _reg, _order))
+
+
+@pytest.mark.parametrize("S,regime,order", _CASES)
+def test_all_label_rows(S, regime, order):
+    """All (dur, v) rows of S in one batch (860 rows at S = 40, 2 144 at S = 64), all 7 losses; mask_loss, learnable_bias and
+    the exposure profile cycle over the cases so that every combination appears."""
+    i = _CASES.index((S, regime, order))
+    mask_loss, bias, expo = i % 2, (i // 2) % 2 and regime != "ties", ("ones", "stat")[(i // 4) % 2]
+    gt = all_label_rows(S)
+    z = make_logits(regime, gt.shape[0], S, seed=100 + i)
+    cfg = loss_cfg(ORDERS[order], S, mask_loss=mask_loss, learnable_bias=int(bias), exposure=expo)
+    run_case(z, gt, cfg, _bias(S, i) if bias else None, what="S=%d %s %s" % (S, regime, order))
+
+
+@pytest.mark.parametrize("mask_loss", [0, 1])
+@pytest.mark.parametrize("regime", LOGIT_REGIMES)
+@pytest.mark.parametrize("loss", ["interestBPR", "focal", "surviveCE", "interestCE", "interestKL", "huber", "hazard"])
+def test_each_loss_alone(loss, regime, mask_loss):
+    """One loss alone: its gradient sets every row's scale (with all losses together, other terms dominate it).  Under "ties"
+    interestBPR sees uniform softmax weights and sg = 0.5 on every negative."""
+    S = 33
+    gt = all_label_rows(S)
+    z = make_logits(regime, gt.shape[0], S, seed=7 + LOSS_SLOTS.index(loss))
+    run_case(z, gt, loss_cfg([loss], S, mask_loss=mask_loss, exposure="stat"), what="%s %s" % (loss, regime))
+
+
+@pytest.mark.parametrize("B", [1, 3, 64, 65, 257, 2048])
+@pytest.mark.parametrize("li", range(len(REAL_LISTS)))
+def test_reference_lists_make_labels(li, B):
+    """make_labels batches (a third fully watched) with the reference configurations' loss lists; huber / mse loop over Bg."""
+    S = 40
+    gt, _, _ = make_labels(B, S, torch.Generator().manual_seed(B + 17 * li), allow_full_len=False)
+    z = make_logits("trained", B, S, seed=B + li)
+    lst = REAL_LISTS[li]
+    cfg = loss_cfg(lst, S, mask_loss=int("interestCE" in lst and li % 2), learnable_bias=li % 2, exposure="stat" if li % 3 else "ones")
+    run_case(z, gt, cfg, _bias(S, li) if li % 2 else None, what="list %d B=%d" % (li, B))
+
+
+# ------------------------------------------------------------------ outside the reference's domain: the kernel's finite behaviour
+def test_s1_bpr_row_without_negative():
+    """S = 1: a row leaving at segment 0 has no negative lane (the reference raises on the empty neg.max()).  The kernel takes
+    the softmax weights as 0: A = 0 clamps to 1e-8, the row adds -log(1e-8) / (valid rows) and no gradient.  Every other loss of
+    the batch follows the oracle."""
+    S = 1
+    gt = all_label_rows(S).repeat(3, 1)                           # [0], [1] (fully watched: no BPR row)
+    z = make_logits("trained", gt.shape[0], S, seed=1)
+    others = ["focal", "surviveCE", "interestCE", "interestKL", "huber", "hazard"]
+    got_bpr = k8(z, gt, loss_cfg(["interestBPR"], S))
+    n_valid = int((gt == 0).sum())
+    assert np.isfinite(got_bpr["dlogits"]).all() and (got_bpr["dlogits"] == 0).all()
+    want = float(-np.log(np.float32(1e-8)))
+    assert abs(got_bpr["slots"][0] - want) <= 1e-6 * want, (got_bpr["slots"][0], want, n_valid)
+    assert float(got_bpr["parts"][:, 0].sum()) == pytest.approx(want, rel=1e-6)
+    cfg = loss_cfg(["interestBPR"] + others, S)
+    got = k8(z, gt, cfg)
+    rest = loss_cfg(others, S)
+    t, r = oracle_loss(z, gt, rest), oracle_loss(z, gt, rest, dtype=torch.float32)
+    got_rest = dict(got, slots=np.where(np.arange(9) == 0, np.nan, got["slots"]),
+                    total=got["total"] - LOSS_WEIGHTS["interestBPR"] * float(got["losses"][0]))
+    loss_compare(got_rest, t, r, rest, "S=1")
+    assert abs(float(got["losses"][0]) - want) <= 1e-6 * want
+
+
+def _ce_kl_without_rows(drop):
+    """compute_loss with interestCE / interestKL taken over the rows not in ``drop`` (normalised by the whole batch), every other
+    loss over all rows: the kernel's treatment of rows that have no unmasked segment."""
+    import segmm_oracle
+    keep = torch.from_numpy(~np.asarray(drop, dtype=bool))
+
+    def fn(z, gt, cfg, sd, gs):
+        lst = cfg["loss_type_list"]
+        ce_kl = [n for n in lst if n in ("interestCE", "interestKL")]
+        out = segmm_oracle.compute_loss(z, gt.clone(), dict(cfg, loss_type_list=[n for n in lst if n not in ce_kl]), sd, gs)
+        sub = segmm_oracle.compute_loss(z[keep], gt[keep].clone(), cfg, sd, gs)
+        for n in ce_kl:
+            out[n] = sub[n]
+            out["loss"] = out["loss"] + sub[n] * cfg["loss_weight"][n]
+        return out
+    return fn
+
+
+def test_all_padding_row_with_mask_loss():
+    """A row of padding only (dur = 0) under mask_loss: the reference divides 0 / 0 in interestCE / interestKL (NaN); the kernel
+    leaves the row out of those two losses (contribution 0) and follows the oracle everywhere else."""
+    S = 20
+    gt = torch.cat([all_label_rows(S)[:60], torch.full((2, S), -2, dtype=torch.int64)])
+    B = gt.shape[0]
+    pad = (gt == -2).all(1).numpy()
+    z = make_logits("trained", B, S, seed=2)
+    cfg = loss_cfg(["focal", "interestBPR", "surviveCE", "interestCE", "interestKL", "huber", "hazard"], S, mask_loss=1)
+    got = k8(z, gt, cfg)
+    assert np.isfinite(got["dlogits"]).all() and np.isfinite(got["slots"]).all()
+    assert float(got["parts"][torch.from_numpy(pad)][:, 3:5].abs().max()) == 0.0
+    v, v2, norms = _stats_host(gt, True)
+    gs = dict(v_all=v, v2_all=v2, norms=norms)          # the whole batch's: the same normalisers as without it
+    fn = _ce_kl_without_rows(pad)
+    t, r = oracle_loss(z, gt, cfg, gs=gs, fn=fn), oracle_loss(z, gt, cfg, gs=gs, dtype=torch.float32, fn=fn)
+    loss_compare(got, t, r, cfg, "pad row")
+
+
+@pytest.mark.parametrize("lst", [["interestBPR", "hazard", "surviveCE"], ["focal", "interestBPR", "huber"]])
+def test_every_row_fully_watched(lst):
+    """No row has a leave (v = S everywhere): the reference raises on the empty neg.max() of interestBPR.  The kernel gives
+    interestBPR = 0 and hazard = 0 with no gradient from them, and the other losses follow the oracle."""
+    S = 40
+    gt = torch.ones(37, S, dtype=torch.int64)
+    z = make_logits("trained", 37, S, seed=4)
+    cfg = loss_cfg(lst, S)
+    got = k8(z, gt, cfg)
+    assert got["slots"][0] == 0.0 and got["slots"][6] == 0.0
+    rest = loss_cfg([n for n in lst if n not in ("interestBPR", "hazard")], S)
+    t, r = oracle_loss(z, gt, rest), oracle_loss(z, gt, rest, dtype=torch.float32)
+    loss_compare(dict(got, slots=np.where(np.isin(np.arange(9), [0, 6]), np.nan, got["slots"])), t, r, rest, "fully watched")
+
+
+# ------------------------------------------------------------------ data-parallel identity at the op level
+def test_data_parallel_shards_add_up():
+    """2 048 rows in G = 8 shards (config 4): per shard label_stats, the [v | v2 | norms] record, label_stats_unpack of all
+    records, loss_fwd_bwd with the global v_all / v2_all / norms, loss_finish.  The shard losses add up to the full batch's
+    float64 loss and the shard dlogits are its gradient rows."""
+    H = _abi()
+    S, G, Bfull = 40, 8, 2048
+    B = Bfull // G
+    gt, _, _ = make_labels(Bfull, S, torch.Generator().manual_seed(5))
+    z = make_logits("trained", Bfull, S, seed=5)
+    cfg = loss_cfg(["focal", "interestBPR", "surviveCE", "interestCE", "interestKL", "huber", "hazard"], S, mask_loss=1,
+                   exposure="stat")
+    sp = _spec(cfg)
+    n = 2 * B + 3
+    gathered = torch.full((G, n), float("nan"), device=DEV)
+    for g in range(G):
+        gtd = gt[g * B:(g + 1) * B].to(DEV).contiguous()
+        rec = gathered[g]
+        H.label_stats(gtd, B, S, int(sp.has_focal), rec[:B], rec[B:2 * B], rec[2 * B:])
+    v_all, v2_all, norms = torch.empty(G * B, device=DEV), torch.empty(G * B, device=DEV), torch.empty(3, device=DEV)
+    H.label_stats_unpack(gathered, G, B, v_all, v2_all, norms)
+    v, v2, nh = _stats_host(gt, True)
+    assert torch.equal(v_all.cpu(), v) and torch.equal(v2_all.cpu(), v2) and torch.equal(norms.cpu(), nh)
+    slots, total, dls = np.zeros(9), 0.0, []
+    for g in range(G):
+        sh = slice(g * B, (g + 1) * B)
+        o = k8(z[sh], gt[sh], cfg, stats=(v_all, v2_all, norms))
+        slots += o["slots"]
+        total += o["total"]
+        dls.append(o["dlogits"])
+    t, r = oracle_loss(z, gt, cfg), oracle_loss(z, gt, cfg, dtype=torch.float32)
+    loss_compare(dict(slots=slots, total=total, dlogits=np.concatenate(dls)), t, r, cfg, "G=8 shards")
+
+
+@pytest.mark.parametrize("G,B", [(1, 300), (2, 300), (8, 256), (8, 20000)])
+def test_label_stats_unpack_exact(G, B):
+    """(8, 20000): 160 000 rows, more than one trip of the 512 x 256 grid-stride loop."""
+    H = _abi()
+    g = torch.Generator().manual_seed(G * B)
+    n = 2 * B + 3
+    rec = torch.randint(0, 65, (G, n), generator=g).float()
+    gathered = rec.to(DEV)
+    v_all, v2_all, norms = (torch.full((m,), float("nan"), device=DEV) for m in (G * B, G * B, 3))
+    H.label_stats_unpack(gathered, G, B, v_all, v2_all, norms)
+    assert torch.equal(v_all.cpu(), torch.cat([rec[k, :B] for k in range(G)]))
+    assert torch.equal(v2_all.cpu(), torch.cat([rec[k, B:2 * B] for k in range(G)]))
+    want = torch.zeros(3)
+    for k in range(G):          # summed in rank order
+        want = want + rec[k, 2 * B:]
+    assert torch.equal(norms.cpu(), want)
+
+
+@pytest.mark.parametrize("rewritten", [0, 1])
+@pytest.mark.parametrize("B", [1, 1023, 1024, 1025, 5000])
+def test_label_stats_exact(B, rewritten):
+    H = _abi()
+    S = 40
+    gt, _, _ = make_labels(B, S, torch.Generator().manual_seed(B))
+    v, v2, norms = (torch.full((m,), float("nan"), device=DEV) for m in (B, B, 3))
+    H.label_stats(gt.to(DEV), B, S, rewritten, v, v2, norms)
+    hv, hv2, hn = _stats_host(gt, rewritten)
+    assert torch.equal(v.cpu(), hv) and torch.equal(v2.cpu(), hv2) and torch.equal(norms.cpu(), hn)
+
+
+# ------------------------------------------------------------------ loss_finish on its own
+@pytest.mark.parametrize("B", [1, 15, 16, 17, 63, 64, 65, 2048])
+def test_loss_finish_column_sums(B):
+    H = _abi()
+    g = torch.Generator().manual_seed(B)
+    parts = torch.randn(B, 12, generator=g) * torch.logspace(-3, 3, 12)
+    coef = torch.tensor([1.0, 0.7, 1.1, 0.8, 1.2, 0.7, 0.9, 0.0, 0.0, 0.0, 0.0, 0.0])
+    losses, total = torch.full((12,), float("nan"), device=DEV), torch.full((), float("nan"), device=DEV)
+    H.loss_finish(parts.to(DEV), B, coef.to(DEV), losses, total)
+    t = parts.double().sum(0)
+    scale = parts.double().abs().sum(0)
+    loss_check(losses.cpu().double().numpy(), t.numpy(), parts.sum(0).double().numpy(), scale.numpy(), "loss_finish:losses")
+    loss_check(float(total), float((coef.double() * t).sum()), float((coef * parts.sum(0)).sum()),
+               float((coef.double() * scale).sum()), "loss_finish:total")
+
+
+def _scales_py(old, gain, g, target):
+    """The delayed-scale rule of loss_finish_kernel restated: for g = max |dlogits| > 0 and finite, every site with gain > 0 whose
+    fp32 product pred = gain * g is positive, finite and normal gets 2^clamp((target - 1) - exponent(pred), -60, 60)."""
+    out = old.clone()
+    g32 = np.float32(g)
+    if not (g32 > 0 and np.isfinite(g32)):
+        return out
+    for i, gi in enumerate(gain.numpy().astype(np.float32)):
+        with np.errstate(over="ignore", under="ignore"):
+            pred = np.float32(gi * g32)
+        e = int(np.array(pred, dtype=np.float32).view(np.uint32)) >> 23
+        if gi > 0 and pred > 0 and e != 0xFF and e != 0:
+            se = max(-60, min(60, (target - 1) - (e - 127)))
+            out[i] = 2.0 ** se
+    return out
+
+
+def _finish_with_scales(dl_view, gain, old, target):
+    H = _abi()
+    parts = torch.ones(3, 12, device=DEV)
+    coef = torch.ones(12, device=DEV)
+    losses, total = torch.empty(12, device=DEV), torch.empty((), device=DEV)
+    sc, gmax = old.clone().to(DEV), torch.full((1,), float("nan"), device=DEV)
+    H.loss_finish(parts, 3, coef, losses, total, dlogits=dl_view, site_scale=sc, gain=gain.to(DEV), n_sites=gain.numel(),
+                  gmax=gmax, target=target)
+    torch.cuda.synchronize()
+    assert torch.equal(losses.cpu(), torch.full((12,), 3.0)) and float(total) == 36.0
+    return float(gmax), sc.cpu()
+
+
+def _gains(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    gain = torch.exp(torch.randn(n, generator=g) * 8)
+    gain[0] = 0.0                    # no recorded gain: untouched
+    gain[1] = -1.0
+    gain[2] = 3e38                   # gain * g overflows (g >= 4): untouched
+    gain[3] = 1.4e-45                # gain * g subnormal (g < 8e6): untouched
+    gain[4] = 1e-30                  # exponent below the clamp: 2^60
+    gain[5] = 1e30                   # 2^-60
+    return gain
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("n_dl", [1, 4 * 256 * 4 + 7, 2048 * 40 + 3])
+def test_loss_finish_gmax_and_scales(n_dl, offset):
+    """gmax is max |dlogits| bitwise, on a 16-byte aligned view (float4 path) and one float further (scalar path); n_dl % 4 != 0
+    puts elements in the tail loop.  The site scales follow _scales_py bitwise."""
+    g = torch.Generator().manual_seed(n_dl + offset)
+    buf = (torch.randn(n_dl + 8, generator=g) * torch.exp(torch.randn(n_dl + 8, generator=g) * 3)).to(DEV)
+    dl = buf[offset:offset + n_dl]
+    dl[n_dl // 2] = 4.0 * float(torch.sign(dl[n_dl // 2]) or 1.0) if float(dl.abs().max()) < 4 else float(dl[n_dl // 2])
+    assert (dl.data_ptr() % 16 == 0) == (offset == 0)
+    gain = _gains(300, n_dl)
+    old = torch.full((300,), 0.25)
+    for target in (7, 12):
+        gm, sc = _finish_with_scales(dl, gain, old, target)
+        want = float(dl.abs().max())
+        assert gm == want
+        assert torch.equal(sc, _scales_py(old, gain, want, target))
+        assert sc[0] == 0.25 and sc[1] == 0.25 and sc[2] == 0.25 and sc[3] == 0.25 and sc[4] == 2.0 ** 60 and sc[5] == 2.0 ** -60
+    # the largest element last, in the scalar tail
+    dl[-1] = 2 * float(dl.abs().max())
+    gm, _ = _finish_with_scales(dl, gain, old, 7)
+    assert gm == float(dl[-1])
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_loss_finish_zero_gradient_leaves_scales(offset):
+    """g = 0: nothing to scale by, every site keeps its scale."""
+    buf = torch.zeros(1000 + 8, device=DEV)
+    gain = _gains(40, 3)
+    old = torch.linspace(0.5, 4.0, 40)
+    gm, sc = _finish_with_scales(buf[offset:offset + 1001 - 4], gain, old, 7)
+    assert gm == 0.0 and torch.equal(sc, old)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_loss_finish_nan_in_dlogits(offset):
+    """What a NaN in dlogits does today: fmaxf drops it, so gmax is the largest |finite value| and the scales follow that value --
+    the delayed-scale logic does not flag the NaN (the backward's own non-finite checks have to)."""
+    g = torch.Generator().manual_seed(9)
+    buf = torch.randn(4099 + 8, generator=g).to(DEV)
+    dl = buf[offset:offset + 4099]
+    dl[17] = float("nan")
+    dl[-2] = float("nan")
+    gain = _gains(64, 9)
+    old = torch.full((64,), 0.5)
+    gm, sc = _finish_with_scales(dl, gain, old, 7)
+    want = float(dl[~torch.isnan(dl)].abs().max())
+    assert gm == want
+    assert torch.equal(sc, _scales_py(old, gain, want, 7))
