@@ -339,6 +339,21 @@ int segmm_adamw(float* p, const float* g, float* m, float* v, int64_t n, float l
 int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                       uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
                       segmm_stream_t stream);
+/* Global-norm gradient clipping without a host sync: torch.nn.utils.clip_grad_norm_(params, max_norm) followed by AdamW
+ * (main_for_seq_leave_earlystop_SegMM.py:298), everything on the device.
+ * segmm_grad_norm: total_norm = the 2-norm of g[0, n) (any float offset, any n >= 0), summed in fp64 per workgroup into `scratch`
+ *   (1024 doubles, caller-owned) and then in a fixed order: the same gradient gives the same bits every run.  Writes
+ *   out2[0] = total_norm and out2[1] = coef = min(1, max_norm / (total_norm + 1e-6)), both fp32, coef evaluated as torch does
+ *   (reciprocal, then product; a NaN norm gives a NaN coef).  max_norm > 0; max_norm = inf reports the norm and gives coef = 1.
+ * segmm_adamw_scaled / segmm_adamw_table_scaled: segmm_adamw / phase 1 of segmm_adamw_table with the gradient multiplied by *coef
+ *   (device memory, e.g. out2 + 1) and rounded to fp32 first -- bit for bit segmm_adamw on fp32(g * coef).  The table's phase 0
+ *   (g = 0) takes no scale. */
+int segmm_grad_norm(const float* g, int64_t n, float max_norm, double* scratch, float* out2, segmm_stream_t stream);
+int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream);
+int segmm_adamw_table_scaled(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                             uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* coef,
+                             segmm_stream_t stream);
 /* Device-side step state, so that a whole training step (main_for_seq_leave_earlystop_SegMM.py:265-300) can be replayed from its
  * recorded launch sequences with unchanged kernel arguments: two dropout seed words and the optimizer's step count with its bias
  * corrections live in device memory -- a struct of segmm_step_state_bytes() bytes in CALLER-OWNED, 16-byte aligned device memory

@@ -509,7 +509,7 @@ __global__ void step_advance_kernel(StepState* st, float b1, float b2) {
 extern "C" {
 
 const char* segmm_last_error(void) { return g_segmm_err; }
-int segmm_abi_version(void) { return 29; }
+int segmm_abi_version(void) { return 30; }
 int segmm_attn_mode(int mode) { const int prev = attn_f16(); if (mode >= 0 && mode <= 2) g_knobs[K_ATTN].value = mode; return prev; }
 
 static PlaneOut plane_out(uint16_t* planes, int ld2, float* hdr, const float* scale_in) {
@@ -1411,19 +1411,38 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
     return 0;
 }
 
+static int adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      int step, const float* coef, hipStream_t stream) {
+    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    long long blocks = ((n >> 2) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    if (coef)
+        hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
+                           beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
+    else
+        hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
+                           beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int segmm_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                 float eps, float weight_decay, int step, segmm_stream_t stream) {
     SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw: pointer/alignment");
     SEGMM_REQUIRE(step >= 1 || step == -1, "adamw: step=%d (>= 1, or -1: the device-side step state)", step);
     if (n <= 0) return 0;
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
-    long long blocks = ((n >> 2) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr, beta1,
-                       beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr);
-    LAUNCH_CHECK();
-    return 0;
+    return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, (hipStream_t)stream);
+}
+
+int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_scaled: pointer/alignment");
+    SEGMM_REQUIRE(coef, "adamw_scaled: null coef (use segmm_adamw for an unscaled step)");
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_scaled: step=%d (>= 1, or -1: the device-side step state)", step);
+    if (n <= 0) return 0;
+    return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream);
 }
 
 int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
@@ -1450,8 +1469,50 @@ int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_ro
         return 0;
     }
     if (n_ids == 0) return 0;
-    hipLaunchKernelGGL(adamw_table_rows_kernel, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids, n_ids,
-                       flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr);
+    hipLaunchKernelGGL(adamw_table_rows_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids, n_ids,
+                       flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr,
+                       (const float*)nullptr);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_adamw_table_scaled(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                             uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* coef,
+                             segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && g && m && v && flags && (ids || n_ids == 0) && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v),
+                  "adamw_table_scaled: pointer/alignment");
+    SEGMM_REQUIRE(coef, "adamw_table_scaled: null coef (use segmm_adamw_table for an unscaled step)");
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "adamw_table_scaled: width %% 4, sizes");
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_scaled: step=%d (>= 1, or -1: the device-side step state)", step);
+    if (n_rows == 0 || n_ids == 0) return 0;
+    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    hipLaunchKernelGGL(adamw_table_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, width / 4,
+                       (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
+                       step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr, coef);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_grad_norm(const float* g, int64_t n, float max_norm, double* scratch, float* out2, segmm_stream_t stream) {
+    SEGMM_REQUIRE(g && scratch && out2, "grad_norm: null pointer");
+    SEGMM_REQUIRE((((uintptr_t)g) & 3u) == 0 && (((uintptr_t)scratch) & 7u) == 0 && (((uintptr_t)out2) & 3u) == 0, "grad_norm: alignment");
+    SEGMM_REQUIRE(n >= 0, "grad_norm: n=%lld", (long long)n);
+    SEGMM_REQUIRE(max_norm > 0.f, "grad_norm: max_norm=%f (> 0, or inf: report the norm, never clip)", (double)max_norm);
+    hipStream_t s = (hipStream_t)stream;
+    int nparts = 0;
+    if (n > 0) {
+        const int to16 = (int)((4u - ((((uintptr_t)g) >> 2) & 3u)) & 3u);          // floats before the first 16-byte boundary
+        const int lead = n < to16 ? (int)n : to16;
+        const long long n4 = (n - lead) >> 2;
+        const int tail = (int)((n - lead) & 3);
+        long long blocks = (n4 + 255) / 256;
+        if (blocks > GRAD_NORM_PARTS) blocks = GRAD_NORM_PARTS;
+        if (blocks < 1) blocks = 1;
+        nparts = (int)blocks;
+        hipLaunchKernelGGL(sumsq_parts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, lead, n4, tail, scratch);
+        LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)scratch, nparts, max_norm, out2);
     LAUNCH_CHECK();
     return 0;
 }

@@ -611,17 +611,26 @@ __device__ __forceinline__ void adamw_elem4(f32x4& pp, const f32x4 gg, f32x4& mm
     pp.x -= step * (mm.x / den.x); pp.y -= step * (mm.y / den.y);
     pp.z -= step * (mm.z / den.z); pp.w -= step * (mm.w / den.w);
 }
+// the gradient seen by a clipped step: g * coef rounded to fp32, as torch's g.mul_(clip_coef) leaves it (SCALED = false: g as is)
+template <bool SCALED>
+__device__ __forceinline__ f32x4 adamw_grad4(f32x4 gg, const float* coef) {
+#pragma clang fp contract(off)
+    if constexpr (SCALED) { const float c = *coef; gg *= c; }
+    return gg;
+}
 // ---------------------------------------------------------------- fused AdamW over a flat range (a13 / K9)
 // torch.optim.AdamW single-tensor update order (decoupled decay first), bias corrections passed in.
+// SCALED: the gradient is multiplied by *coef first (segmm_adamw_scaled: the clip coefficient segmm_grad_norm wrote)
+template <bool SCALED>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
-                             float bc1, float bc2_sqrt, const StepState* live) {
+                             float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; }          // bias corrections of the device-side step count
     const long long n4 = n >> 2;
     const float step = lr / bc1;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         f32x4 pp = ((f32x4*)p)[i];
-        const f32x4 gg = ((const f32x4*)g)[i];
+        const f32x4 gg = adamw_grad4<SCALED>(((const f32x4*)g)[i], coef);
         f32x4 mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
         adamw_elem4(pp, gg, mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
@@ -630,7 +639,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long long i = (n4 << 2) + threadIdx.x;
         f32x4 pp = {p[i], 0.f, 0.f, 0.f}, mm = {m[i], 0.f, 0.f, 0.f}, vv = {v[i], 0.f, 0.f, 0.f};
-        adamw_elem4(pp, f32x4{g[i], 0.f, 0.f, 0.f}, mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, adamw_grad4<SCALED>(f32x4{g[i], 0.f, 0.f, 0.f}, coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
         p[i] = pp.x; m[i] = mm.x; v[i] = vv.x;
     }
 }
@@ -659,10 +668,12 @@ __global__ __launch_bounds__(256) void adamw_table_rest_kernel(float* __restrict
     }
 }
 // the marked rows, each once: one wave per list entry; lane 0 claims (and clears) the row's mark
+template <bool SCALED>
 __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                                float* __restrict__ v, long long n_rows, int w4, const long long* __restrict__ ids,
                                                                int n_ids, unsigned int* __restrict__ flags, float lr, float b1, float b2, float eps,
-                                                               float wd, float bc1, float bc2_sqrt, const StepState* live) {
+                                                               float wd, float bc1, float bc2_sqrt, const StepState* live,
+                                                               const float* __restrict__ coef) {
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; }
     const float step = lr / bc1;
     const int lane = threadIdx.x & 63;
@@ -677,8 +688,67 @@ __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict
     for (int c = lane; c < w4; c += 64) {
         const long long i = id * w4 + c;
         f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        adamw_elem4(pp, ((const f32x4*)g)[i], mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, adamw_grad4<SCALED>(((const f32x4*)g)[i], coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+    }
+}
+
+// ---------------------------------------------------------------- global 2-norm of a flat gradient range (segmm_grad_norm)
+// torch.nn.utils.clip_grad_norm_(params, max_norm) without a host sync: sum of squares in fp64 (the square of an fp32 value is
+// exact in fp64, so fp32 gradients near 1e-20 or 1e19 neither underflow nor overflow), one partial per workgroup into caller-owned
+// scratch, then a fixed-order sum in a second one-workgroup launch.  No atomics: the same gradient gives the same bits every run.
+constexpr int GRAD_NORM_PARTS = 1024;          // workgroups (and fp64 partials) at most
+__device__ __forceinline__ double sq4(f32x4 x) {
+    return ((double)x.x * x.x + (double)x.y * x.y) + ((double)x.z * x.z + (double)x.w * x.w);
+}
+// fixed-order sum of one value per thread of a 256-thread workgroup; the result is valid in thread 0
+__device__ __forceinline__ double block_sum256(double acc, double* red) {
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// g: the range from its first 16-byte boundary (`lead` < 4 floats before it are read by workgroup 0), n4 whole vectors, then `tail`
+__global__ __launch_bounds__(256) void sumsq_parts_kernel(const float* __restrict__ g, int lead, long long n4, int tail,
+                                                          double* __restrict__ parts) {
+    __shared__ double red[4];
+    const f32x4* g4 = (const f32x4*)(g + lead);
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    double acc = 0.0;
+    for (; i + 3 * stride < n4; i += 4 * stride) {          // four independent 16-B loads in flight per lane
+        const f32x4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
+        acc += (sq4(a) + sq4(b)) + (sq4(c) + sq4(d));
+    }
+    for (; i < n4; i += stride) acc += sq4(g4[i]);
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < lead) acc += (double)g[threadIdx.x] * g[threadIdx.x];
+        if (threadIdx.x < tail) {
+            const float x = g[lead + (n4 << 2) + threadIdx.x];
+            acc += (double)x * x;
+        }
+    }
+    acc = block_sum256(acc, red);
+    if (threadIdx.x == 0) parts[blockIdx.x] = acc;
+}
+// out2 = {total_norm, coef}: coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 the way torch evaluates it
+// (clip_grad_norm_: max_norm / t is t.reciprocal() * max_norm; torch.clamp keeps a NaN); max_norm = inf: coef = 1, never a clip
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ parts, int nparts, float max_norm,
+                                                               float* __restrict__ out2) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < nparts; k += 256) acc += parts[k];
+    acc = block_sum256(acc, red);
+    if (threadIdx.x == 0) {
+        const float t = (float)sqrt(acc);
+        float c = 1.0f;
+        if (!__builtin_isinf(max_norm)) {
+            c = (1.0f / (t + 1e-6f)) * max_norm;
+            if (c > 1.0f) c = 1.0f;
+        }
+        out2[0] = t;
+        out2[1] = c;
     }
 }
 

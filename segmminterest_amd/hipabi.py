@@ -15,7 +15,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGMM_LIB") or os.path.join(_HERE, "libsegmm_hip.so")      # SEGMM_LIB: A/B builds of the kernels
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _lib = None
 
@@ -81,6 +81,9 @@ SIGNATURES = {
     "segmm_loss_fwd_bwd": [_i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p],
     "segmm_adamw": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _p],
     "segmm_adamw_table": [_p, _p, _p, _p, _i64, _i, _p, _i, _p, _f, _f, _f, _f, _f, _i, _i, _p],
+    "segmm_adamw_scaled": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _p, _p],
+    "segmm_adamw_table_scaled": [_p, _p, _p, _p, _i64, _i, _p, _i, _p, _f, _f, _f, _f, _f, _i, _p, _p],
+    "segmm_grad_norm": [_p, _i64, _f, _p, _p, _p],
     "segmm_dropout_mult": [_p, _i64, _f, _u64, _u32, _p],
     "segmm_rank_leave": [_p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "segmm_auc_counts": [_p, _p, _p, _i, _p, _p],
@@ -1005,25 +1008,50 @@ def loss_fwd_bwd(B, S, logits, gt, bias_w, bias_b, exposure, coef, enabled, rew_
                                     _ptr(dlogits), _ptr(parts), _stream()), "segmm_loss_fwd_bwd")
 
 
-def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0):
+def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0, coef=None):
+    """segmm_adamw over [p_off, p_off + n) of the flat buffers; ``coef``: a device float the gradient is multiplied by first
+    (segmm_adamw_scaled, the clip coefficient of :func:`grad_norm`)."""
     with _kprof("adamw", 28 * int(n)):
-        _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off)
+        _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off, coef)
 
 
-def adamw_table(p, g, m, v, off, n_rows, width, ids, flags, lr, beta1, beta2, eps, weight_decay, step, phase):
+def adamw_table(p, g, m, v, off, n_rows, width, ids, flags, lr, beta1, beta2, eps, weight_decay, step, phase, coef=None):
     """segmm_adamw_table on the table that starts ``off`` floats into the flat buffers (phase 0: rows without a gradient, g = 0;
-    phase 1: the rows listed in ``ids``)."""
+    phase 1: the rows listed in ``ids``, their gradient multiplied by the device float ``coef`` first when one is given)."""
     with _kprof("adamw", (24 if phase == 0 else 28) * int(n_rows if phase == 0 else ids.numel()) * int(width)):
-        _check(lib().segmm_adamw_table(p.data_ptr() + 4 * off, None if g is None else g.data_ptr() + 4 * off, m.data_ptr() + 4 * off,
-                                       v.data_ptr() + 4 * off, int(n_rows), int(width), ids.data_ptr(), ids.numel(), flags.data_ptr(),
-                                       float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), int(phase),
-                                       _stream()), "segmm_adamw_table")
+        args = (p.data_ptr() + 4 * off, None if g is None else g.data_ptr() + 4 * off, m.data_ptr() + 4 * off, v.data_ptr() + 4 * off,
+                int(n_rows), int(width), ids.data_ptr(), ids.numel(), flags.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
+                float(weight_decay), int(step))
+        if coef is None:
+            _check(lib().segmm_adamw_table(*args, int(phase), _stream()), "segmm_adamw_table")
+        else:
+            if phase != 1:
+                raise RuntimeError("adamw_table: a scaled update is phase 1 only (phase 0 has g = 0)")
+            _check(lib().segmm_adamw_table_scaled(*args, coef.data_ptr(), _stream()), "segmm_adamw_table_scaled")
 
 
-def _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0):
-    _check(lib().segmm_adamw(p.data_ptr() + 4 * p_off, g.data_ptr() + 4 * p_off, m.data_ptr() + 4 * p_off,
-                             v.data_ptr() + 4 * p_off, n, lr, beta1, beta2, eps, weight_decay, step, _stream()),
-           "segmm_adamw")
+def _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0, coef=None):
+    args = (p.data_ptr() + 4 * p_off, g.data_ptr() + 4 * p_off, m.data_ptr() + 4 * p_off, v.data_ptr() + 4 * p_off, n, lr, beta1, beta2,
+            eps, weight_decay, step)
+    if coef is None:
+        _check(lib().segmm_adamw(*args, _stream()), "segmm_adamw")
+    else:
+        _check(lib().segmm_adamw_scaled(*args, coef.data_ptr(), _stream()), "segmm_adamw_scaled")
+
+
+GRAD_NORM_SCRATCH = 1024          # fp64 partials segmm_grad_norm may write
+
+
+def grad_norm(g, n, max_norm, scratch, out2, off=0):
+    """segmm_grad_norm over g[off, off + n): out2 (two device floats) = {2-norm, clip coefficient for ``max_norm``};
+    ``scratch``: GRAD_NORM_SCRATCH float64 on the device."""
+    if scratch.dtype != torch.float64 or scratch.numel() < GRAD_NORM_SCRATCH or out2.dtype != torch.float32 or out2.numel() < 2:
+        raise RuntimeError("grad_norm: scratch must be %d float64, out2 two float32" % GRAD_NORM_SCRATCH)
+    if off < 0 or n < 0 or off + n > g.numel():
+        raise RuntimeError("grad_norm: range [%d, %d) outside a tensor of %d elements" % (off, off + n, g.numel()))
+    with _kprof("grad_norm", 4 * int(n)):
+        _check(lib().segmm_grad_norm(g.data_ptr() + 4 * off, int(n), float(max_norm), scratch.data_ptr(), out2.data_ptr(), _stream()),
+               "segmm_grad_norm")
 
 
 def bias_grad(dl, B, S, gbw, gbb):

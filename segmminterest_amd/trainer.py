@@ -74,16 +74,38 @@ def default_args(**over):
 
 
 # ------------------------------------------------------------------------------------------------ optimizer
+def _check_max_grad_norm(max_grad_norm):
+    if max_grad_norm is None:
+        return None
+    try:
+        m = float(max_grad_norm)
+    except (TypeError, ValueError):
+        raise ValueError("max_grad_norm must be a positive float, inf or None, not %r" % (max_grad_norm,))
+    if not m > 0.0:          # (also NaN)
+        raise ValueError("max_grad_norm must be a positive float, inf or None, not %r" % (max_grad_norm,))
+    return m
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics (lr 1e-3, wd 1e-4, betas (.9,.999), eps 1e-8 at
     main_for_seq_leave_earlystop_SegMM.py:226) as ONE kernel over the contiguous live range of the
-    flat parameter buffer.  Dead parameters (no gradient in the reference either) are never touched."""
+    flat parameter buffer.  Dead parameters (no gradient in the reference either) are never touched.
 
-    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    ``max_grad_norm``: None (default) = no clipping, what the reference actually runs (its clip_grad_norm_ call at :298 gets an
+    exhausted generator).  A positive float m (inf allowed) = ``torch.nn.utils.clip_grad_norm_(params, m)`` before every step:
+    the 2-norm of every live gradient (segmm_grad_norm, fp64 sums, bitwise reproducible) and the coefficient
+    min(1, m / (norm + 1e-6)) stay on the device, and AdamW multiplies the gradient by it as it reads it -- no host sync.
+    ``grad_norm`` is the last step's norm as a 0-dim device tensor (valid until the next step; ``.item()`` syncs); m = inf
+    reports the norm and never clips.  Unlike torch, ``.grad`` keeps the UNCLIPPED gradient after the step.  A non-finite norm
+    propagates as in torch, except to the id-table rows without a gradient of a two-pass table update (stepped with g = 0)."""
+
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
         self.step_count = 0
         self.m = self.v = None
         self._flat_id = None
+        self._clip_out = self._clip_scratch = None          # {norm, coef} of the last step; the norm's fp64 partials
 
     def _state(self):
         st = self.model._store
@@ -101,8 +123,16 @@ class FusedAdamW:
         for p in plist:
             p.grad = None
 
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """The 2-norm of the last step's gradients (before clipping) as a 0-dim device tensor, None without ``max_grad_norm``."""
+        return None if self.max_grad_norm is None or self._clip_out is None else self._clip_out[0]
+
+    def _coef(self):
+        return None if self.max_grad_norm is None else self._clip_out[1:2]
+
     def step(self, gbuf=None):
-        self.begin_step()
+        self.begin_step(gbuf)
         st = self._state()
         pos = 0
         # id tables whose rows without a gradient were already stepped at the head of the step (table_early): the listed rows
@@ -110,7 +140,8 @@ class FusedAdamW:
         for o, n, rows, width, ids, flags in sorted(self.__dict__.pop("_early", []), key=lambda e: e[0]):
             self.step_range(pos, o, gbuf)
             H.adamw_table(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self.lr, self.betas[0],
-                          self.betas[1], self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, 1)
+                          self.betas[1], self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, 1,
+                          coef=self._coef())
             pos = o + n
         self.step_range(pos, st.n_live, gbuf)
         self.end_step()
@@ -134,11 +165,18 @@ class FusedAdamW:
 
     # one optimizer step as several launches over disjoint ranges that together cover the live range: the data-parallel
     # trainer steps each gradient bucket as soon as ITS all-reduce has completed (begin_step, step_range ..., end_step)
-    def begin_step(self):
+    def begin_step(self, gbuf=None):
         st = self._state()
         self.step_count += 1
         if not st.__dict__.get("direct_grads", False):
             self._sync_grads(st)
+        if self.max_grad_norm is not None:
+            # the global norm reads every live gradient: the caller enqueues this once all of them are complete (train_step: the
+            # tail stream, after the side / auxiliary streams have joined and, under data parallelism, every bucket is reduced)
+            if self._clip_out is None or self._clip_out.device != st.flat.device:
+                self._clip_out = torch.zeros(2, dtype=torch.float32, device=st.flat.device)
+                self._clip_scratch = torch.zeros(H.GRAD_NORM_SCRATCH, dtype=torch.float64, device=st.flat.device)
+            H.grad_norm(st.gflat if gbuf is None else gbuf, st.n_live, self.max_grad_norm, self._clip_scratch, self._clip_out)
 
     def _sync_grads(self, st):
         """The kernel reads the FLAT gradient buffer.  After Trainer.train_step the parameters' ``.grad`` ARE views of it
@@ -162,7 +200,7 @@ class FusedAdamW:
         if end > start:
             # device_state: the bias corrections come from the device-side step count (segmm_step_advance), step = -1
             H.adamw(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, end - start, self.lr, self.betas[0], self.betas[1],
-                    self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, p_off=start)
+                    self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, p_off=start, coef=self._coef())
 
     def end_step(self):
         self.model._store.fused_version += 1          # the pre-split weight planes of the GEMM engines are now stale
@@ -402,11 +440,13 @@ def shard_rows(n_rows: int, world: int, rank: int):
 class Trainer:
     """zero_grad -> L1-normalise -> forward -> backward (-> bucketed all-reduce) -> AdamW, i.e. the body of
     the reference's hot loop (main_for_seq_leave_earlystop_SegMM.py:269-300) minus its host syncs.
-    Gradient clipping is a no-op in the reference (exhausted generator at :298) and is therefore absent."""
+    Gradient clipping is a no-op in the reference (exhausted generator at :298), so the default ``max_grad_norm=None`` does not
+    clip; ``max_grad_norm=m`` clips to global norm m on the device before AdamW (see FusedAdamW; ``trainer.opt.grad_norm`` is the
+    norm the reference logs), in the eager, recorded and data-parallel steps."""
 
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
-                 feature_table=None, sparse_tables=True, device_state=False):
+                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None):
         self.model = model
         # device_state: what changes from step to step (dropout seed words, AdamW's step count and bias corrections, the
         # site-header rows of a step) lives on the device / is laid out per step, so the kernel arguments of a step never
@@ -418,7 +458,7 @@ class Trainer:
         # HBM-bound kernel (segmm_gather_l1) and the 573 KB/row host->device copy disappears
         self.feature_table = feature_table
         self.dropout = dropout      # False: run the step in eval mode (deterministic; used by the DP equivalence tests)
-        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay)
+        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         self.comm = comm if comm is not None else DPComm()
         self.overlap = overlap
         st = model._store
@@ -808,8 +848,16 @@ class Trainer:
             # ... in TWO launches: every cross-stream wait costs ~15 us of queue time on the GPU, so the buckets that
             # completed early (a contiguous prefix of the flat buffer: head | layers ...) are stepped together, then the last one
             H.mark(H.PHASE_STEP_TAIL)
-            self.opt.begin_step()
             works = self._bucket_works
+            if self.opt.max_grad_norm is not None:
+                # a global norm needs every bucket reduced: no per-bucket overlap, one norm over the reduced live range (each rank
+                # computes it from its own, identical copy of the all-reduced gradient), then one AdamW launch
+                H.host_action(functools.partial(self._wait_buckets, range(len(works))))
+                self.opt.begin_step()
+                self.opt.step_range(0, st.n_live)
+                self.opt.end_step()
+                return out
+            self.opt.begin_step()
             order = sorted(range(len(works)), key=lambda i: works[i][0])
             last = len(works) - 1
             early = [i for i in order if i != last]
@@ -938,8 +986,11 @@ class Trainer:
         self._recorded = dict(phases=phases, keep=rec.keep, pool=pool, prev_batch=batch, tab_keys=tab_keys, out=out, relocs=relocs, spans={k: (sh, dt) for k, _, _, sh, dt in spans},
                               main=main, events=evs, table=H.stream_table(streams, [e.cuda_event for e in evs[:2 * (len(streams) - 1)]]),
                               n_cmds=sum(ph.n_cmds for ph, a in phases if a is not None),
-                              hyper=(self.opt.lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps))
+                              hyper=self._hyper())
         return out
+
+    def _hyper(self):
+        return (self.opt.lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm)
 
     def _timed_plan(self, r):
         """The recorded phases cut at every GEMM / attention command (bench.py's timed replay): [("host", fn) | ("run", Phase) |
@@ -996,10 +1047,11 @@ class Trainer:
         if r is None:
             raise RuntimeError("run_recorded() before record()")
         H.step_bind(self._step_state)
-        if (self.opt.lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps) != r["hyper"]:
-            # the recorded segmm_adamw / segmm_adamw_table commands carry lr, weight decay, betas and eps BY VALUE
+        if self._hyper() != r["hyper"]:
+            # the recorded segmm_adamw / segmm_adamw_table / segmm_grad_norm commands carry lr, weight decay, betas, eps and the
+            # clipping norm BY VALUE
             raise RuntimeError("run_recorded(): the optimizer's hyperparameters changed since record() (%r -> %r): record() again"
-                               % (r["hyper"], (self.opt.lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps)))
+                               % (r["hyper"], self._hyper()))
         for k, (sh, dt) in r["spans"].items():
             v = batch[k]
             if tuple(v.shape) != sh or v.dtype != dt or not v.is_contiguous():
