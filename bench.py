@@ -24,7 +24,9 @@ Timed region: after the warm-up, EXACTLY --steps steps (--windows N cuts them in
 --dump-outputs DIR then writes what the last timed step computed (outputs and updated parameters, float32 .npy, <= 64 MB; inputs
 and initial parameters are seeded, so two builds run with the same arguments can be compared array for array).
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus
+Prints ONE JSON line (rank 0) with the driver contract fields.  A plain run does only what they need: it sets up, warms up, times
+the steps, dumps (--dump-outputs) and prints.  --full adds the fields below; what it runs for them is HIP events on steps that
+run anyway, and legs after the timed region and the dump, so the timed steps and the dump are the same with or without it:
   roofline     -- the dominant kernel: algorithmic FLOPs (or bytes) per launch / HIP-event duration on the launch's own stream,
                   measured live in a timed replay of the recorded step (`measured_in`; eager step modes: the same steps enqueued
                   launch by launch), vs the peak of the instruction used (MI355X_MICROARCH.md)
@@ -36,6 +38,9 @@ Prints ONE JSON line (rank 0) with the driver contract fields plus
   value_f32_engine / ms_per_step_f32_engine (N = 1) -- the same step on the exact-fp32 MFMA engine, same run.
   host_fed (N = 1) -- the same step with the feature tensors copied from pinned host memory every step (what the reference's
                   loop does); PCIe-inclusive, reported beside `value`, never as `value`.
+  value_index_input (N = 1) -- the same step fed by index batches from a device-resident feature table.
+  config.replicas_identical (N > 1) -- fp64 checksums of every rank's parameters agree.
+The --no-* options drop single legs of a --full run.
 """
 import argparse
 import math
@@ -74,6 +79,9 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (its output tensors and the updated parameters) "
                          "as DIR/<name>.npy, float32, at most 64 MB in all; see dump_outputs()")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline passes, the host-fed, index-input, exact-fp32 "
+                         "and CPU legs, the replicas' checksums (see the module docstring)")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
     ap.add_argument("--batch", type=int, default=None, help="rows per GPU (default: 512; config 3: 1024)")
     ap.add_argument("--global-batch", type=int, default=None, help="total rows over all GPUs (config 4: 2048)")
@@ -87,7 +95,7 @@ def parse_args():
     ap.add_argument("--n-users", type=int, default=1903)
     ap.add_argument("--batches", type=int, default=8, help="distinct synthetic batches rotated through the steps")
     ap.add_argument("--input", choices=("features", "index"), default="features")
-    ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed (PCIe-inclusive) leg")
+    ap.add_argument("--no-host-fed", action="store_true", help="--full: skip the host-fed (PCIe-inclusive) leg")
     ap.add_argument("--prefetch", action="store_true",
                     help="Trainer.train_step(batch, next_batch=...): the input stage (L1 normalisation / table gather) of the next batch runs on "
                          "its own stream under the current step.  Off by default: measured +0.2 %% (the GPU is saturated, the overlap buys nothing)")
@@ -98,18 +106,18 @@ def parse_args():
                          "segmm_step_tail), data-parallel collectives as host actions in between: the eager two-stream schedule without the "
                          "per-launch host work.  Bit-identical to the per-launch step (tests/test_eval_gpu.py, tests/test_dp_gpu.py)")
     ap.add_argument("--eager", action="store_true", help="enqueue every launch of every step from Python (the round-1..3 step mode; A/B partner of the default)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the sustained-MFMA probe (roofline.sustained_probe)")
-    ap.add_argument("--eager-roofline", action="store_true", help="recorded step mode: take roofline / roofline_attention from the launch-by-launch eager pass instead of the timed replay of the recorded step")
+    ap.add_argument("--no-probe", action="store_true", help="--full: skip the sustained-MFMA probe (roofline.sustained_probe)")
+    ap.add_argument("--eager-roofline", action="store_true", help="--full, recorded step mode: take roofline / roofline_attention from the launch-by-launch eager pass instead of the timed replay of the recorded step")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="gloo: CPU-staged collectives, lets several ranks share one GPU (CI rehearsal of the N > 1 path)")
     ap.add_argument("--no-overlap", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU leg")
     ap.add_argument("--sustained", action="store_true",
                     help="add the sustained leg (value_sustained: one window of >= 2000 steps / >= 8 s after the timed region; its step count "
                          "is set by the clock, not by --steps, so it is off by default)")
     ap.add_argument("--no-sustained", action="store_true", help="(the default) no sustained leg")
-    ap.add_argument("--no-index-leg", action="store_true", help="skip the index-input leg (value_index_input: the product's input path)")
-    ap.add_argument("--no-f32-engine", action="store_true")
+    ap.add_argument("--no-index-leg", action="store_true", help="--full: skip the index-input leg (value_index_input: the product's input path)")
+    ap.add_argument("--no-f32-engine", action="store_true", help="--full: skip the exact-fp32 engine leg")
     ap.add_argument("--cpu-rows", type=int, default=128)
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=3)
@@ -493,7 +501,10 @@ def main():
         if args.prefetch:
             raise SystemExit("--recorded: no prefetch")
         run(trainer, max(args.warmup, 3))
-        inst = instrumented(args.warmup)
+        if args.full:
+            inst = instrumented(args.warmup)
+        else:          # the same steps without the event pairs: the timed steps start from the same state either way
+            run(trainer, min(args.steps, 10), args.warmup)
         try:
             trainer.record(batches[0], warmup=2)
         except RuntimeError as e:          # a configuration record() refuses (it says why): the per-launch step, and the line says so
@@ -548,39 +559,42 @@ def main():
                      "smi": smi.summary(), "note": "one window of `steps` steps after the timed windows, same step mode; smi = hwmon freq1_input / "
                                                    "power1 of this GPU every 0.25 s during the window (null: sysfs not readable here)"}
 
-    if inst is None:
-        inst = instrumented(args.warmup + args.steps)
-    psteps, prof, aprof, kprof, prof_elapsed = inst
-    # ---- recorded step mode: the GEMM / attention launches are timed in a TIMED REPLAY of the recorded step itself -- the same C
-    # launch sequences as the timed windows, cut at every GEMM / attention command with a HIP-event pair around it on the command's
-    # own stream (Trainer.run_recorded(timed=...)): the two streams overlap as they do in the timed region, which the launch-by-launch
-    # eager pass above (kept for the HBM-bound kernels' table and as the fallback) only approximates.  Outside the timed region.
-    roofline_pass = "eager steps enqueued launch by launch"
-    if args.recorded and trainer.__dict__.get("_recorded") is not None and not args.eager_roofline:
-        try:
-            tg, ta = [], []
-            tsteps = min(args.steps, 10)
-            barrier()
-            for i in range(2):          # (builds the plan, warms the cut sequence)
-                trainer.run_recorded(batches[i % len(batches)], timed=([], []))
-            barrier()
-            tp0_ = time.perf_counter()
-            for i in range(tsteps):
-                trainer.run_recorded(batches[i % len(batches)], timed=(tg, ta))
-            barrier()
-            psteps, prof, aprof, prof_elapsed = tsteps, tg, ta, time.perf_counter() - tp0_
-            roofline_pass = "timed replay of the recorded step (C launch sequences cut at every GEMM / attention command)"
-        except Exception as e:          # never lose the line over the evidence pass
-            sys.stderr.write("bench.py: timed replay failed (%s); roofline from the eager instrumented pass\n" % e)
-
-    # data parallel: the replicas must still hold the SAME parameters (fp64 checksums of the flat parameter buffer of every rank)
+    # ---- --full only, from here on: the roofline passes and the replicas' checksums; after the line is built, the host-fed,
+    # index-input, exact-fp32 and CPU legs
     replicas_identical = None
-    if world > 1:
-        flat = model._store.flat.detach().double()
-        cs = [float(flat.sum().item()), float((flat * flat).sum().item())]
-        allcs = [None] * world
-        dist.all_gather_object(allcs, cs)
-        replicas_identical = all(c == allcs[0] for c in allcs)
+    if args.full:
+        if inst is None:
+            inst = instrumented(args.warmup + args.steps)
+        psteps, prof, aprof, kprof, prof_elapsed = inst
+        # ---- recorded step mode: the GEMM / attention launches are timed in a TIMED REPLAY of the recorded step itself -- the same C
+        # launch sequences as the timed windows, cut at every GEMM / attention command with a HIP-event pair around it on the command's
+        # own stream (Trainer.run_recorded(timed=...)): the two streams overlap as they do in the timed region, which the launch-by-launch
+        # eager pass above (kept for the HBM-bound kernels' table and as the fallback) only approximates.  Outside the timed region.
+        roofline_pass = "eager steps enqueued launch by launch"
+        if args.recorded and trainer.__dict__.get("_recorded") is not None and not args.eager_roofline:
+            try:
+                tg, ta = [], []
+                tsteps = min(args.steps, 10)
+                barrier()
+                for i in range(2):          # (builds the plan, warms the cut sequence)
+                    trainer.run_recorded(batches[i % len(batches)], timed=([], []))
+                barrier()
+                tp0_ = time.perf_counter()
+                for i in range(tsteps):
+                    trainer.run_recorded(batches[i % len(batches)], timed=(tg, ta))
+                barrier()
+                psteps, prof, aprof, prof_elapsed = tsteps, tg, ta, time.perf_counter() - tp0_
+                roofline_pass = "timed replay of the recorded step (C launch sequences cut at every GEMM / attention command)"
+            except Exception as e:          # never lose the line over the evidence pass
+                sys.stderr.write("bench.py: timed replay failed (%s); roofline from the eager instrumented pass\n" % e)
+
+        # data parallel: the replicas must still hold the SAME parameters (fp64 checksums of the flat parameter buffer of every rank)
+        if world > 1:
+            flat = model._store.flat.detach().double()
+            cs = [float(flat.sum().item()), float((flat * flat).sum().item())]
+            allcs = [None] * world
+            dist.all_gather_object(allcs, cs)
+            replicas_identical = all(c == allcs[0] for c in allcs)
 
     engine = {hipabi.ENGINE_F32: "f32", hipabi.ENGINE_BF16X6: "bf16x6", hipabi.ENGINE_F16X3: "f16x3", hipabi.ENGINE_F16X3P: "f16x3p"}[hipabi.GEMM_ENGINE]
     ftrain = f_train_flops(Din, D, S, Lt, N, w["id_mode"])
@@ -610,6 +624,7 @@ def main():
                        "live_train_flops_per_interaction": ftrain, "gemm_engine": engine,
                        "step_frac_of_f32_mfma_peak": round(rows_per_s / world * ftrain / (PEAK_F32_MFMA_TFLOPS * 1e12), 4)},
         }
+    if rank == 0 and args.full:
         # ---------------- roofline of the dominant kernel: the GEMMs in every configuration (config 3 too: with the fused AdamW the
         # dense optimizer over the item table is 8 % of the step, the d = 512 GEMMs ~60 %); config 3 keeps the optimizer and the
         # table-gradient kernels as a sub-object priced against HBM
@@ -829,7 +844,7 @@ def main():
     # ---- the same steps fed from HOST memory (N = 1, feature input): what the reference's loop does every step
     # (main...SegMM.py:271: batch[k].to(device)).  Pinned host batches, a copy stream one batch ahead, two device buffers.
     # PCIe-inclusive, so it is reported beside `value`, never as `value`.
-    if world == 1 and not args.no_host_fed and not w["id_mode"] and args.input == "features":
+    if args.full and world == 1 and not args.no_host_fed and not w["id_mode"] and args.input == "features":
         fkeys = ("user", "photo")
         host = [{k: batches[i][k].cpu().pin_memory() for k in fkeys} for i in range(min(len(batches), 4))]
         dbuf = [{k: torch.empty_like(batches[0][k]) for k in fkeys} for _ in range(2)]
@@ -878,7 +893,7 @@ def main():
 
     # ---- the same step fed by INDEX batches from a device-resident feature table (N = 1): the product's input path (SURVEY §8 f-1:
     # gather + pad + mask + L1 normalisation in one kernel, feature_store.py) -- nothing crosses PCIe per step but the indices
-    if world == 1 and not args.no_index_leg and not w["id_mode"] and args.input == "features":
+    if args.full and world == 1 and not args.no_index_leg and not w["id_mode"] and args.input == "features":
         from segmminterest_amd.feature_store import ResidentFeatureTable
         gi = torch.Generator(device="cpu").manual_seed(99)
         table = ResidentFeatureTable(torch.rand((200000, Din), generator=gi).to(dev))
@@ -930,7 +945,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- the same step on the exact-fp32 MFMA engine, same run (N = 1): the strict-fp32 number next to the headline
-    if world == 1 and not args.no_f32_engine and not w["id_mode"] and engine != "f32":
+    if args.full and world == 1 and not args.no_f32_engine and not w["id_mode"] and engine != "f32":
         del trainer, model
         torch.cuda.empty_cache()
         saved = hipabi.GEMM_ENGINE
@@ -950,7 +965,7 @@ def main():
         finally:
             hipabi.GEMM_ENGINE = saved
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args, w, h)
         real_stdout.write(json.dumps(rec) + "\n")
         real_stdout.flush()

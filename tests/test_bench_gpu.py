@@ -1,4 +1,5 @@
-"""bench.py on the GPU: --steps sets the number of timed steps, and --dump-outputs writes what the last of them computed."""
+"""bench.py on the GPU: --steps sets the number of timed steps, --dump-outputs writes what the last of them computed, and --full
+adds its legs without changing either."""
 import json
 import os
 import subprocess
@@ -9,12 +10,13 @@ import pytest
 
 from helpers import ROOT
 
-TOY = ["--dim", "64", "--heads", "4", "--lt", "12", "--batch", "32", "--batches", "2", "--warmup", "1",
-       "--no-cpu-baseline", "--no-f32-engine", "--no-host-fed", "--no-probe", "--no-index-leg"]
+TOY_SHAPE = ["--dim", "64", "--heads", "4", "--lt", "12", "--batch", "32", "--batches", "2", "--warmup", "1"]
+TOY = TOY_SHAPE + ["--no-cpu-baseline", "--no-f32-engine", "--no-host-fed", "--no-probe", "--no-index-leg"]
+FULL_ONLY = {"roofline", "roofline_attention", "value_index_input", "index_input", "cpu_baseline", "value_f32_engine", "host_fed"}
 
 
-def _bench(out_dir, *extra):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + TOY + list(extra) + ["--dump-outputs", str(out_dir)],
+def _bench(out_dir, *extra, base=TOY):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + list(extra) + ["--dump-outputs", str(out_dir)],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     assert p.stdout.count("\n") == 1, p.stdout
@@ -37,3 +39,18 @@ def test_bench_steps_are_the_timed_steps_and_the_dump_is_the_last_one(tmp_path):
     for k in a:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
     assert any(not np.array_equal(a[k], c[k]) for k in a if k.startswith("param."))
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_its_legs_and_leaves_the_timed_steps_alone(tmp_path):
+    """A plain run prints none of the --full fields; --full (every leg on) prints them, and its last timed step computed bitwise
+    what the plain run's did: the event pairs ride on steps a plain run takes too, and the legs run after the dump."""
+    plain, a = _bench(tmp_path / "plain", "--steps", "3", base=TOY_SHAPE)
+    full, b = _bench(tmp_path / "full", "--steps", "3", "--full", base=TOY_SHAPE)
+    assert not FULL_ONLY & set(plain) and plain["config"]["replicas_identical"] is None
+    assert FULL_ONLY <= set(full), sorted(FULL_ONLY - set(full))
+    assert full["roofline"]["launches"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert plain["config"]["final_loss"] == full["config"]["final_loss"]
+    assert a.keys() == b.keys()
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)

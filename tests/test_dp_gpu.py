@@ -240,12 +240,12 @@ def test_bench_launcher_four_ranks_on_one_gpu():
     """bench.py --gpus N end to end, the way the driver starts it for N > 1 (a child torch.distributed.run, one rank per
     process, rows sharded, global loss normalisers, bucketed all-reduce, per-bucket AdamW): config 4 at a toy width, FOUR
     gloo ranks sharing this GPU (the GPU boxes admit at most 6 processes on the card, so 8 ranks cannot be rehearsed here).
-    One JSON line, n_gpus = 4, every rank ends with bit-identical parameters."""
+    One JSON line, n_gpus = 4, every rank ends with bit-identical parameters (--full compares their checksums)."""
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--config", "4", "--global-batch", "64",
            "--dim", "64", "--heads", "4", "--lt", "12", "--steps", "3", "--warmup", "1", "--windows", "3", "--batches", "2",
-           "--no-cpu-baseline", "--no-f32-engine", "--no-host-fed", "--no-probe"]
+           "--full", "--no-cpu-baseline", "--no-f32-engine", "--no-host-fed", "--no-probe"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)

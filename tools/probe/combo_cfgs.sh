@@ -1,4 +1,4 @@
-X="--no-cpu-baseline --no-sustained --no-index-leg --no-host-fed --no-f32-engine --no-probe"
+X="--full --no-cpu-baseline --no-sustained --no-index-leg --no-host-fed --no-f32-engine --no-probe"
 for CFG in "4 --global-batch 256" "3"; do
  for i in 1 2; do
   for C in "8 8" "4 8" "4 4" "8 4"; do

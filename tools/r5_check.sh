@@ -1,6 +1,6 @@
 # round-5 checkpoint on the GPU box: bash tools/r5_check.sh <tag> [tests|notests]
 TAG=${1:-x}; O=gpurun_out/r5; mkdir -p $O
-X="--no-cpu-baseline --no-f32-engine --no-host-fed"
+X="--full --no-cpu-baseline --no-f32-engine --no-host-fed"
 if [ "${2:-tests}" = "tests" ]; then
   python -m pytest tests -x -q -m gpu > $O/gpu_tests_$TAG.log 2>&1; tail -12 $O/gpu_tests_$TAG.log
 fi

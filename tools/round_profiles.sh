@@ -4,16 +4,16 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-X="--no-cpu-baseline --no-f32-engine --no-host-fed --no-probe --no-sustained --no-index-leg"
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
+X="--full --no-cpu-baseline --no-f32-engine --no-host-fed --no-probe --no-sustained --no-index-leg"
+python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
 python bench.py --eager --steps 20 --warmup 5 $X > $O/bench_n1_eager.json 2>/dev/null
 SEGMM_SCALING=exact python bench.py --steps 20 --warmup 5 $X > $O/bench_n1_exact_scaling.json 2>/dev/null
-python bench.py --config 3 --steps 20 --warmup 5 > $O/bench_cfg3.json 2>/dev/null
+python bench.py --full --config 3 --steps 20 --warmup 5 > $O/bench_cfg3.json 2>/dev/null
 python bench.py --config 5 --steps 20 --warmup 5 $X > $O/bench_cfg5.json 2>/dev/null
 python bench.py --config 4 --gpus 1 --global-batch 256 --steps 20 --warmup 5 $X > $O/bench_cfg4_256rows.json 2>/dev/null
 for M in "--eager" "--device-state" ""; do python bench.py --config 4 --gpus 1 --global-batch 256 --steps 20 --warmup 5 $M $X 2>/dev/null | tail -1; done > $O/bench_cfg4_256rows_step_modes.jsonl
 python bench.py --input index --steps 20 --warmup 5 $X > $O/bench_index_input.json 2>/dev/null
-python bench.py --gpus 2 --backend gloo --steps 6 --warmup 2 --windows 2 --no-cpu-baseline --no-probe > $O/bench_gloo2_one_gpu.json 2>/dev/null
+python bench.py --full --gpus 2 --backend gloo --steps 6 --warmup 2 --windows 2 --no-cpu-baseline --no-probe > $O/bench_gloo2_one_gpu.json 2>/dev/null
 SEGMM_DP_FORCE=1 python bench.py --steps 20 --warmup 5 $X > $O/bench_dp_forced_one_rank.json 2>/dev/null
 bash tools/bench_matrix.sh ${TAG}_matrix > $O/step_mode_matrix.txt 2>&1
 bash tools/prof_stats.sh ${TAG}_cfg2 > $O/prof_cfg2_summary.txt 2>&1
