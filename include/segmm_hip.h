@@ -389,6 +389,24 @@ int segmm_auc_counts(const float* score, const int8_t* label, const int64_t* seg
                      segmm_stream_t stream);
 int segmm_survival(const float* interest, int ld, const int64_t* gt, float* surv, int8_t* label, int B, int S,
                    segmm_stream_t stream);
+/* Per-row metrics of the test phase (main_eval_batch, my_evaluation.py:249-266; TOP_K_leave(test=1); --eval_cold,
+ * --count_view_completion).  Floating-point results, unlike the three above; one thread per row with segmm_survival's
+ * sequential fp32 recurrence, so surv is bit-identical to it.
+ * segmm_row_metrics: interest [B, ld] (ld >= S), gt [B, S] in {1,0,-1,-2}; photo_id [B] and seen [n_seen] bytes or both
+ *   null.  One record per row, stored field-major:
+ *     irec [4, B] int32: view_length = #(gt == 1) | duration = #(gt != -2) | top1 = argmin interest, lowest index on ties |
+ *                        group = 1 (cold: photo_id outside [0, n_seen) or seen[photo_id] == 0), else 0 (hot; no table: 0)
+ *     frec [4, B] float: jaccard = (sum_{t < view_length} (1 - |gt[t] - surv[t]|) + duration - view_length) / duration
+ *                        (NaN for duration == 0) | pred_view_length = sum_{gt[t] != -2} surv[t] |
+ *                        leave_ctr = 1 - interest[k] | leave_ctr_view = 1 - surv[k], k = view_length - 1, S - 1 for view_length 0
+ *   Any S >= 1; B == 0 launches nothing.
+ * segmm_row_metrics_accumulate: acc [3, 10] double (caller-owned and -zeroed; groups: all, cold, hot rows) += over the B
+ *   records of {1, jaccard, pred, (pred - vl)^2, |pred - vl|, leave_ctr, leave_ctr_view, (top1 - vl)^2, |top1 - vl|,
+ *   vl == duration}.  One workgroup, fixed summation order, no floating-point atomics: bit-identical from run to run;
+ *   stream order serialises the batches.  S = the segment count the records were made with (checked only). */
+int segmm_row_metrics(const float* interest, int ld, const int64_t* gt, const int64_t* photo_id, const uint8_t* seen, int64_t n_seen,
+                      int B, int S, int32_t* irec, float* frec, segmm_stream_t stream);
+int segmm_row_metrics_accumulate(const int32_t* irec, const float* frec, int B, int S, double* acc, segmm_stream_t stream);
 /* (f)-1 resident-table feature gather (dataloader_SegMM.py:271-362 + the trainer's L1 normalisation): out[r, :] =
  * table[idx[r], :] (/ (sum|.| + 1e-6) if normalize), mask[r] = 1, for idx[r] in [0, n_lines); zeros / 0 otherwise. */
 int segmm_gather_l1(const float* table, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize, float* out,

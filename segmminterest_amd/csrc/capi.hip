@@ -1590,6 +1590,27 @@ int segmm_survival(const float* interest, int ld, const int64_t* gt, float* surv
     return 0;
 }
 
+int segmm_row_metrics(const float* interest, int ld, const int64_t* gt, const int64_t* photo_id, const uint8_t* seen, int64_t n_seen,
+                      int B, int S, int32_t* irec, float* frec, segmm_stream_t stream) {
+    SEGMM_REQUIRE(interest && gt && irec && frec, "row_metrics: null pointer");
+    SEGMM_REQUIRE(S >= 1 && B >= 0 && ld >= S, "row_metrics: S < 1 / B < 0 / ld < S");
+    SEGMM_REQUIRE(!seen || (photo_id && n_seen >= 0), "row_metrics: a seen table needs photo_id and n_seen >= 0");
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(row_metrics_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, interest, ld, (const long long*)gt,
+                       (const long long*)photo_id, (const unsigned char*)seen, (long long)n_seen, B, S, (int*)irec, frec);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_row_metrics_accumulate(const int32_t* irec, const float* frec, int B, int S, double* acc, segmm_stream_t stream) {
+    SEGMM_REQUIRE(irec && frec && acc, "row_metrics_accumulate: null pointer");
+    SEGMM_REQUIRE(S >= 1 && B >= 0, "row_metrics_accumulate: S < 1 / B < 0");
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(row_metrics_accumulate_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)irec, frec, B, acc);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int segmm_scales_update(const float* arena, const int32_t* site_idx, int n_rows, float* site_scale, float* stats, int target,
                         float* gain, const float* gmax, segmm_stream_t stream) {
     SEGMM_REQUIRE(arena && site_idx && site_scale && stats && n_rows >= 0 && target >= 2 && target <= 15 && (!gain == !gmax), "scales_update: arguments");

@@ -137,6 +137,109 @@ __global__ __launch_bounds__(256) void survival_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------- per-row metrics of the test phase (main_eval_batch,
+// my_evaluation.py:249-266: JaccardSim / LeaveMSE / LeaveCTR / LeaveCTR_view, the argmin of TOP_K_leave(test=1), --eval_cold)
+// One thread per row, like survival_kernel and with ITS recurrence (h += logf(x); surv = expf(h), in position order), so that
+// surv is bit-identical to segmm_survival; the whole input is a few hundred KB, the kernel is bound by latency.  Records are
+// stored field-major: irec [RM_NI, B] = view_length, duration, top1, group; frec [RM_NF, B] = jaccard, pred_view_length,
+// leave_ctr, leave_ctr_view.
+//   view_length = #(gt == 1), duration = #(gt != -2), top1 = argmin interest (lowest index on ties: np.argmin)
+//   group = 1 (cold) iff photo_id is outside [0, n_seen) or seen[photo_id] == 0; 0 (hot) otherwise and without a table
+//   jaccard = (sum_{t < view_length} (1 - |gt[t] - surv[t]|) + (duration - view_length)) / duration   (IoU_Sim "length_aware";
+//             NaN for duration == 0), pred_view_length = sum_{gt[t] != -2} surv[t]   (predict_view_length)
+//   leave_ctr = 1 - interest[k], leave_ctr_view = 1 - surv[k], k = view_length - 1, or S - 1 for view_length == 0 (the
+//             reference indexes [-1] there)
+// The terms are fp32 like the host's; their sums run in double (the host sums the .tolist() of the terms in Python floats).
+constexpr int RM_NI = 4, RM_NF = 4;
+__global__ __launch_bounds__(256) void row_metrics_kernel(const float* __restrict__ interest, int ld, const long long* __restrict__ gt,
+                                                          const long long* __restrict__ photo_id, const unsigned char* __restrict__ seen,
+                                                          long long n_seen, int B, int S, int* __restrict__ irec, float* __restrict__ frec) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const long long* g = gt + (size_t)b * S;
+    const float* x = interest + (size_t)b * ld;
+    int vl = 0, dur = 0;
+    for (int s = 0; s < S; ++s) {
+        const long long v = g[s];
+        vl += v == 1;
+        dur += v != -2;
+    }
+    const int k = vl > 0 ? vl - 1 : S - 1;
+    float h = 0.f, best = x[0], xk = 0.f, sk = 0.f;
+    int top1 = 0;
+    double jac = 0.0, pred = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const float xi = x[s];
+        h += logf(xi);
+        const float surv = expf(h);
+        const long long v = g[s];
+        if (xi < best) { best = xi; top1 = s; }
+        if (s < vl) jac += (double)(1.f - fabsf((float)v - surv));
+        if (v != -2) pred += (double)surv;
+        if (s == k) { xk = xi; sk = surv; }
+    }
+    int group = 0;
+    if (seen) {
+        const long long p = photo_id[b];
+        group = (p < 0 || p >= n_seen || seen[p] == 0) ? 1 : 0;
+    }
+    irec[b] = vl;
+    irec[(size_t)B + b] = dur;
+    irec[2 * (size_t)B + b] = top1;
+    irec[3 * (size_t)B + b] = group;
+    frec[b] = (float)((jac + (double)(dur - vl)) / (double)dur);
+    frec[(size_t)B + b] = (float)pred;
+    frec[2 * (size_t)B + b] = 1.f - xk;
+    frec[3 * (size_t)B + b] = 1.f - sk;
+}
+
+// acc [3, RM_F] double (caller-owned; groups: all rows, cold rows, hot rows) += the sums of a batch's records:
+//   n, jaccard, pred, (pred - vl)^2, |pred - vl|, leave_ctr, leave_ctr_view, (top1 - vl)^2, |top1 - vl|, #(vl == duration).
+// Deterministic: ONE workgroup, every thread sums a fixed strided set of rows in row order, a fixed-order tree in LDS, one
+// thread reads, adds and writes the accumulator (no floating-point atomics); batches are serialised by stream order.
+constexpr int RM_F = 10;
+__global__ __launch_bounds__(256) void row_metrics_accumulate_kernel(const int* __restrict__ irec, const float* __restrict__ frec, int B,
+                                                                     double* acc) {
+    __shared__ double sm[RM_F][256];
+    const int tid = threadIdx.x;
+    for (int grp = 0; grp < 3; ++grp) {
+        double a[RM_F];
+#pragma unroll
+        for (int f = 0; f < RM_F; ++f) a[f] = 0.0;
+        for (int b = tid; b < B; b += 256) {
+            const bool cold = irec[3 * (size_t)B + b] != 0;
+            if (grp != 0 && (grp == 1) != cold) continue;
+            const int vl = irec[b], dur = irec[(size_t)B + b], top1 = irec[2 * (size_t)B + b];
+            const double pred = (double)frec[(size_t)B + b];
+            const double dp = pred - (double)vl, dt = (double)(top1 - vl);
+            a[0] += 1.0;
+            a[1] += (double)frec[b];
+            a[2] += pred;
+            a[3] += dp * dp;
+            a[4] += fabs(dp);
+            a[5] += (double)frec[2 * (size_t)B + b];
+            a[6] += (double)frec[3 * (size_t)B + b];
+            a[7] += dt * dt;
+            a[8] += fabs(dt);
+            a[9] += vl == dur ? 1.0 : 0.0;
+        }
+        __syncthreads();          // (the previous group's sums have been read)
+#pragma unroll
+        for (int f = 0; f < RM_F; ++f) sm[f][tid] = a[f];
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) {
+#pragma unroll
+                for (int f = 0; f < RM_F; ++f) sm[f][tid] += sm[f][tid + o];
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            for (int f = 0; f < RM_F; ++f) acc[grp * RM_F + f] += sm[f][0];
+        }
+    }
+}
+
 // ---------------------------------------------------------------- resident-table feature gather (+ pad, mask, L1 norm)
 // out[r, :] = table[idx[r], :] / (sum|table[idx[r], :]| + 1e-6) for idx[r] in [0, n_lines), zeros and mask 0 otherwise
 // (negative index = padding slot of the collator, dataloader_SegMM.py:345-350).  One wave per output row.

@@ -88,6 +88,8 @@ SIGNATURES = {
     "segmm_rank_leave": [_p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "segmm_auc_counts": [_p, _p, _p, _i, _p, _p],
     "segmm_survival": [_p, _i, _p, _p, _p, _i, _i, _p],
+    "segmm_row_metrics": [_p, _i, _p, _p, _p, _i64, _i, _i, _p, _p, _p],
+    "segmm_row_metrics_accumulate": [_p, _p, _i, _i, _p, _p],
     "segmm_gather_l1": [_p, _i64, _i, _p, _i64, _i, _p, _p, _p, _p, _i, _p, _p, _p],
     "segmm_segment_weighted_sum": [_p, _p, _p, _i64, _i, _p, _p],
     "segmm_colsum3": [_p, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p],
@@ -1115,6 +1117,41 @@ def survival(interest, gt):
     _check(lib().segmm_survival(_ptr(interest), interest.stride(0), _ptr(gt.contiguous()), _ptr(surv), _ptr(label), B, S, _stream()),
            "segmm_survival")
     return surv, label
+
+
+ROW_METRIC_INT_FIELDS = ("view_length", "duration", "top1", "group")
+ROW_METRIC_FLOAT_FIELDS = ("jaccard", "pred_view_length", "leave_ctr", "leave_ctr_view")
+ROW_METRIC_SUMS = ("n", "jaccard", "pred", "sq_err", "abs_err", "leave_ctr", "leave_ctr_view", "top1_sq_err", "top1_abs_err", "n_complete")
+
+
+def row_metrics(interest, gt, photo_id=None, seen=None):
+    """(irec int32 [4, B], frec float32 [4, B]): the per-row records of the test phase; see segmm_row_metrics in include/segmm_hip.h."""
+    _dev(interest, gt)
+    B, S = gt.shape
+    if interest.dtype != torch.float32 or interest.stride(-1) != 1 or gt.dtype != torch.int64 or not gt.is_contiguous():
+        raise RuntimeError("row_metrics: interest float32 with unit inner stride, gt contiguous int64")
+    if (photo_id is None) != (seen is None):
+        raise RuntimeError("row_metrics: photo_id and seen go together")
+    if seen is not None:
+        _dev(photo_id, seen)
+        if photo_id.dtype != torch.int64 or not photo_id.is_contiguous() or photo_id.numel() != B or seen.dtype != torch.uint8 or not seen.is_contiguous():
+            raise RuntimeError("row_metrics: photo_id contiguous int64 [B], seen contiguous uint8")
+    irec = torch.empty((len(ROW_METRIC_INT_FIELDS), B), dtype=torch.int32, device=interest.device)
+    frec = torch.empty((len(ROW_METRIC_FLOAT_FIELDS), B), dtype=torch.float32, device=interest.device)
+    _check(lib().segmm_row_metrics(_ptr(interest), interest.stride(0), _ptr(gt), _ptr(photo_id),
+                                   _ptr(seen), 0 if seen is None else seen.numel(), B, S, _ptr(irec), _ptr(frec), _stream()),
+           "segmm_row_metrics")
+    return irec, frec
+
+
+def row_metrics_accumulate(irec, frec, acc, S):
+    """acc float64 [3, 10] (all / cold / hot rows) += the sums of the records; see segmm_row_metrics_accumulate."""
+    _dev(irec, frec, acc)
+    B = irec.shape[1]
+    if (irec.dtype != torch.int32 or frec.dtype != torch.float32 or not irec.is_contiguous() or not frec.is_contiguous() or frec.shape[1] != B
+            or acc.dtype != torch.float64 or not acc.is_contiguous() or tuple(acc.shape) != (3, len(ROW_METRIC_SUMS))):
+        raise RuntimeError("row_metrics_accumulate: irec int32 [4, B], frec float32 [4, B], acc contiguous float64 [3, 10]")
+    _check(lib().segmm_row_metrics_accumulate(_ptr(irec), _ptr(frec), B, int(S), _ptr(acc), _stream()), "segmm_row_metrics_accumulate")
 
 
 def gather_l1(table, idx, normalize=True, out=None, mask=None, amax=None, po=None):

@@ -10,6 +10,8 @@ Device path: when the interests / labels are HIP tensors, t
 ``main_eval_batch`` compute the integer ranks and the AUC pair counts with the kernels of ``csrc/evalops.h``
 (bit-exact integers; only B view lengths go to the host -- for the np.random permutation parity -- and B ranks or
 three counters come back), instead of moving [B, S] interests, labels and masks to the host like the reference.
+The per-row metrics of the test phase (the row loop at the end of ``main_eval_batch``) have a device form too, opt-in through
+``Trainer.test_model(device_metrics=True)``: ``row_metrics_device`` / ``RowMetricAccumulator`` / ``seen_table``.
 """
 from __future__ import annotations
 
@@ -132,6 +134,96 @@ def wuAUC_device(labels: torch.Tensor, scores: torch.Tensor, users: torch.Tensor
     ok = (c[:, 1] > 0) & (c[:, 2] > 0)
     auc = c[ok, 0] / (2.0 * c[ok, 1] * c[ok, 2])
     return float((n[ok] * auc).sum() / n[ok].sum())
+
+
+class RowRecords(dict):
+    """The per-row records of :func:`row_metrics_device`: field name -> device tensor [B] (views of the two field-major
+    record blocks ``irec`` int32 [4, B] / ``frec`` float32 [4, B] the kernels exchange)."""
+
+    def __init__(self, irec, frec, S):
+        from . import hipabi as H
+        super().__init__()
+        self.irec, self.frec, self.S = irec, frec, int(S)
+        for i, k in enumerate(H.ROW_METRIC_INT_FIELDS):
+            self[k] = irec[i]
+        for i, k in enumerate(H.ROW_METRIC_FLOAT_FIELDS):
+            self[k] = frec[i]
+
+
+def row_metrics_device(interests: torch.Tensor, gt: torch.Tensor, photo_id=None, seen=None):
+    """The per-row metrics of ``main_eval_batch`` (JaccardSim, LeaveMSE, LeaveCTR, LeaveCTR_view: my_evaluation.py:249-266), the
+    argmin of ``TOP_K_leave(test=1)`` and the cold / hot split of ``--eval_cold`` for a batch, computed on the device by
+    ``row_metrics_kernel`` (csrc/evalops.h).  interests [B, S] float32 (any row stride), gt [B, S] int64; ``photo_id`` [B] int64
+    with ``seen`` (:func:`seen_table`) or neither.  Returns a dict of device tensors [B]: view_length, duration, top1, group
+    (int32; group 1 = cold, 0 = hot or no table) and jaccard, pred_view_length, leave_ctr, leave_ctr_view (float32).  Nothing
+    reaches the host."""
+    from . import hipabi as H
+    B, S = gt.shape
+    x = interests.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(-1) != 1 or x.stride(0) < S:
+        x = x.contiguous()
+    if photo_id is not None:
+        photo_id = photo_id.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
+    irec, frec = H.row_metrics(x, gt.contiguous(), photo_id=photo_id, seen=seen)
+    return RowRecords(irec, frec, S)
+
+
+def seen_table(train_videos, device):
+    """The byte table ``row_metrics_device`` takes as ``seen``: table[p] = 1 for every photo id p of ``train_videos`` (the
+    reference's ``--eval_cold`` set; ids >= 0), one byte per id up to the largest.  Built once per test phase."""
+    ids = torch.tensor(sorted(int(p) for p in train_videos), dtype=torch.int64)
+    if ids.numel() and int(ids[0]) < 0:
+        raise ValueError("seen_table: photo ids must be >= 0")
+    table = torch.zeros(int(ids[-1]) + 1 if ids.numel() else 1, dtype=torch.uint8)
+    table[ids] = 1
+    return table.to(device)
+
+
+class RowMetricAccumulator:
+    """Running sums of the per-row records over the batches of a test phase, on the device: ``state`` float64 [3, F], groups
+    (all rows, cold rows, hot rows) x the sums ``hipabi.ROW_METRIC_SUMS``.  ``add`` enqueues one deterministic kernel
+    (``row_metrics_accumulate_kernel``); nothing reaches the host before ``final`` / ``extras``, which each copy the 3 x F
+    doubles once."""
+    GROUPS = {"all": 0, "cold": 1, "hot": 2}
+
+    def __init__(self, device):
+        from . import hipabi as H
+        self.fields = H.ROW_METRIC_SUMS
+        self.state = torch.zeros((3, len(self.fields)), dtype=torch.float64, device=device)
+
+    def add(self, records: RowRecords):
+        from . import hipabi as H
+        H.row_metrics_accumulate(records.irec, records.frec, self.state, records.S)
+
+    def all_reduce(self, comm):
+        """Data parallel: the sums of every rank's rows, by one all-reduce of ``state``."""
+        if comm.active:
+            comm._all_reduce(self.state)
+
+    def _sums(self, group):
+        row = self.state[self.GROUPS[group]].cpu().tolist()
+        return dict(zip(self.fields, row))
+
+    @staticmethod
+    def _mean(v, n):
+        return v / n if n else float("nan")
+
+    def final(self, eval_type_list, group="all"):
+        """The entries ``compute_final_result`` gives for the per-row metrics of ``eval_type_list``: LeaveMSE = mean squared error
+        of the predicted view lengths, JaccardSim / LeaveCTR / LeaveCTR_view their means (NaN for a group without rows)."""
+        s = self._sums(group)
+        src = {"JaccardSim": "jaccard", "LeaveMSE": "sq_err", "LeaveCTR": "leave_ctr", "LeaveCTR_view": "leave_ctr_view"}
+        return {k: self._mean(s[src[k]], s["n"]) for k in eval_type_list if k in src}
+
+    def extras(self, group="all"):
+        """LeaveMAE / TOP1MSE / TOP1MAE (the (MSE, MAE) pairs of the watch-time scripts), ``view_complete`` = the number of fully
+        watched rows (the reference's --count_view_completion counter) and ``rows``."""
+        s = self._sums(group)
+        n = s["n"]
+        return {"LeaveMAE": self._mean(s["abs_err"], n), "TOP1MSE": self._mean(s["top1_sq_err"], n), "TOP1MAE": self._mean(s["top1_abs_err"], n),
+                "view_complete": int(s["n_complete"]), "rows": int(n)}
 
 
 def auc_rank_sum(labels, scores):

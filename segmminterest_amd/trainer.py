@@ -1114,14 +1114,18 @@ class Trainer:
 
     @torch.no_grad()
     def test_model(self, test_batches, eval_type_list, ckpt: Optional["CheckPointer"] = None, threshold: float = 0.5, top_k_mask: int = 0,
-                   top_k_permutation: int = 1, save_logits: bool = False, train_videos: Optional[set] = None, draw_case: int = 0):
+                   top_k_permutation: int = 1, save_logits: bool = False, train_videos: Optional[set] = None, draw_case: int = 0,
+                   device_metrics: bool = False):
         """The test phase of the reference trainer (main_for_seq_leave_earlystop_SegMM.py:365-459): reload the BEST checkpoint
         (``ckpt.load_checkpoint(model, optimizer, mode='best')``, :366-367), eval mode, ``mode="inference"`` over the test split,
         interests = sigmoid(logits) * exposure_prob (:402-403), pred_label = interests > threshold (:404), every batch through
         ``main_eval_batch`` (:415), then ``compute_final_result`` (:434).  ``train_videos`` (the reference's ``--eval_cold``
         set of photo ids seen in training, :417-427): also the cold / hot splits.  ``save_logits`` (:412-414): the
         [interests | gt | user_id | photo_id] rows.  Returns a dict {"final", "results_list"[, "cold_final", "hot_final",
-        "cold_count_inter", "hot_count_inter"][, "saved_logits"]}."""
+        "cold_count_inter", "hot_count_inter"][, "saved_logits"]}.
+        ``device_metrics=True``: the per-row metrics (JaccardSim, LeaveMSE, LeaveCTR, LeaveCTR_view) and the cold / hot split are
+        computed and summed on the device (:meth:`_test_model_device`) instead of in the host row loop of ``main_eval_batch``;
+        same keys, plus "extras"."""
         import argparse
         from .my_evaluation import main_eval_batch
         model = self.model
@@ -1130,6 +1134,8 @@ class Trainer:
             model.load_state_dict(load_dict["model"])
         model.eval()
         margs = argparse.Namespace(TOP_K_mask=top_k_mask, TOP_K_permutation=top_k_permutation, draw_case=draw_case)
+        if device_metrics:
+            return self._test_model_device(test_batches, eval_type_list, margs, threshold, save_logits, train_videos)
 
         def fresh():
             r = {}
@@ -1171,6 +1177,72 @@ class Trainer:
         if cold:
             res.update(cold_final=compute_final_result(cold_results), hot_final=compute_final_result(hot_results),
                        cold_count_inter=cold_n, hot_count_inter=hot_n)
+        if save_logits:
+            res["saved_logits"] = torch.cat(saved, dim=0) if saved else torch.empty((0, 0))
+        return res
+
+    def _test_model_device(self, test_batches, eval_type_list, margs, threshold, save_logits, train_videos):
+        """The batch loop of :meth:`test_model` with the per-row metrics on the device: per batch one ``row_metrics_device`` call and
+        one ``RowMetricAccumulator.add`` (csrc/evalops.h); ``main_eval_batch`` sees only the batch-level metrics (ProbAUC / TOP_K,
+        device kernels already).  Cold / hot rows come from the kernel's ``group`` field and a byte table of ``train_videos``; no
+        [B, S] tensor goes to the host unless ``save_logits`` asks for it.  Data parallel: every rank evaluates the batches it was
+        given, the accumulator is all-reduced once at the end, so the per-row finals are those of all ranks' rows."""
+        from .my_evaluation import RowMetricAccumulator, main_eval_batch, row_metrics_device, seen_table
+        model = self.model
+        per_row = ("JaccardSim", "LeaveMSE", "LeaveCTR", "LeaveCTR_view")
+        batch_level = [e for e in eval_type_list if e not in per_row]
+
+        def fresh():
+            r = {}
+            for eval_type in batch_level:
+                r[eval_type] = []
+            r["view_lengths"] = []
+            return r
+
+        results_list = fresh()
+        cold = train_videos is not None
+        cold_results, hot_results = (fresh(), fresh()) if cold else (None, None)
+        subsets = cold and any(e in ("ProbAUC", "TOP_K") for e in batch_level)
+        saved = []
+        exposure = seen = acc = None
+        for batch in test_batches:
+            out = self.eval_step(batch, mode="inference")
+            logits = out["logits"]
+            if exposure is None:
+                exposure = torch.tensor(model.exposure_prob, dtype=torch.float32, device=logits.device)[: logits.shape[1]]
+                acc = RowMetricAccumulator(logits.device)
+                if cold:
+                    seen = seen_table(train_videos, logits.device)
+            interests = torch.sigmoid(logits) * exposure
+            pred_label = torch.where(interests > threshold, 1.0, 0.0)
+            gt = out["gt"]
+            if save_logits:
+                saved.append(torch.cat((interests.cpu(), gt.cpu().to(torch.float32), batch["user_id"].reshape(-1, 1).cpu().to(torch.float32),
+                                        batch["photo_id"].reshape(-1, 1).cpu().to(torch.float32)), dim=1))
+            results_list = main_eval_batch(margs, interests, gt, pred_label, results_list, type="inference")
+            rec = row_metrics_device(interests, gt, photo_id=batch["photo_id"] if cold else None, seen=seen)
+            acc.add(rec)
+            if subsets:          # the batch-level metrics of the cold / hot rows: today's indexed calls, the rows named by the kernel
+                for grp, sub in ((1, cold_results), (0, hot_results)):
+                    ix = torch.nonzero(rec["group"] == grp).reshape(-1)
+                    if ix.numel():
+                        main_eval_batch(margs, interests[ix], gt[ix], pred_label[ix], sub, type="inference")
+        if acc is None:
+            acc = RowMetricAccumulator(next(model.parameters()).device)
+        acc.all_reduce(self.comm)
+
+        def final(batch_results, group):
+            f = compute_final_result(batch_results)
+            rows = acc.extras(group)["rows"]
+            for k, v in acc.final(eval_type_list, group).items():
+                if rows or k == "LeaveMSE":          # compute_final_result leaves out the mean of an empty list; LeaveMSE is NaN there
+                    f[k] = v
+            return f, rows
+
+        res = {"final": final(results_list, "all")[0], "results_list": results_list, "extras": acc.extras("all")}
+        if cold:
+            (cf, cn), (hf, hn) = final(cold_results, "cold"), final(hot_results, "hot")
+            res.update(cold_final=cf, hot_final=hf, cold_count_inter=cn, hot_count_inter=hn)
         if save_logits:
             res["saved_logits"] = torch.cat(saved, dim=0) if saved else torch.empty((0, 0))
         return res
