@@ -1394,7 +1394,7 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
                        const float* v2_all, int Bg, float* logits_out, float* dlogits, float* parts,
                        segmm_stream_t stream) {
     SEGMM_REQUIRE(logits && gt && exposure && coef && enabled && norms && v_all && v2_all && logits_out && parts, "loss: null pointer");
-    SEGMM_REQUIRE(S >= 1 && S <= 64, "loss: S=%d must be in [1,64]", S);
+    SEGMM_REQUIRE(S >= 1 && S <= 256, "loss: S=%d must be in [1,256]", S);
     SEGMM_REQUIRE((bias_w == nullptr) == (bias_b == nullptr), "loss: bias_w/bias_b must come together");
     if (B <= 0) return 0;
     LossArgs a;
@@ -1406,7 +1406,12 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
     a.use_mask = use_mask; a.norms = norms;
     a.v_all = v_all; a.v2_all = v2_all; a.Bg = Bg;
     a.logits_out = logits_out; a.dlogits = dlogits; a.parts = parts;
-    hipLaunchKernelGGL(loss_fwd_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, a);
+    // one wave per row: a lane owns one segment up to S = 64 (the kernel every earlier result came from), ceil(S / 64) beyond
+    const dim3 grid((B + 3) / 4), block(256);
+    if (S <= 64) hipLaunchKernelGGL(loss_fwd_bwd_kernel, grid, block, 0, (hipStream_t)stream, a);
+    else if (S <= 128) hipLaunchKernelGGL(loss_fwd_bwd_long_kernel<2>, grid, block, 0, (hipStream_t)stream, a);
+    else if (S <= 192) hipLaunchKernelGGL(loss_fwd_bwd_long_kernel<3>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(loss_fwd_bwd_long_kernel<4>, grid, block, 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1715,9 +1720,14 @@ int segmm_rand_ids(int64_t* out, int64_t n, int64_t lo, int64_t hi, uint64_t see
     return 0;
 }
 int segmm_rand_perm_rows(float* out, int rows, int S, uint64_t seed, uint32_t site, segmm_stream_t stream) {
-    SEGMM_REQUIRE(out && rows >= 0 && S >= 1 && S <= 64, "rand_perm_rows: null pointer / S = %d (1 .. 64)", S);
+    SEGMM_REQUIRE(out && rows >= 0 && S >= 1 && S <= 256, "rand_perm_rows: null pointer / S = %d (1 .. 256)", S);
     if (rows == 0) return 0;
-    hipLaunchKernelGGL(rand_perm_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, out, rows, S, make_drop(0.5f, seed, site));
+    const dim3 grid((rows + 3) / 4), block(256);
+    const DropCfg d = make_drop(0.5f, seed, site);
+    if (S <= 64) hipLaunchKernelGGL(rand_perm_rows_kernel, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
+    else if (S <= 128) hipLaunchKernelGGL(rand_perm_rows_long_kernel<2>, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
+    else if (S <= 192) hipLaunchKernelGGL(rand_perm_rows_long_kernel<3>, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
+    else hipLaunchKernelGGL(rand_perm_rows_long_kernel<4>, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
     LAUNCH_CHECK();
     return 0;
 }

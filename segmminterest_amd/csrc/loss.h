@@ -13,7 +13,7 @@ enum { L_BPR = 0, L_FOCAL, L_SCE, L_ICE, L_IKL, L_HUBER, L_HAZARD, L_MSE, L_MSE2
 constexpr int L_PSTRIDE = 12;   // row stride of `parts` (padded to a multiple of 4 for the float4 column sum)
 
 struct LossArgs {
-    int B, S;                       // local rows, segments (S <= 64)
+    int B, S;                       // local rows, segments (S <= 64: loss_fwd_bwd_kernel, 64 < S <= 256: loss_fwd_bwd_long_kernel)
     const float* logits;            // [B,S] head output (before the learnable position bias)
     const long long* gt;            // [B,S] in {1,0,-1,-2}
     const float* bias_w;            // [S] or null   learnable_bias (decoder_leave_focal.py:442-444,497-504)
@@ -206,6 +206,274 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- rows of 64 < S <= 256 segments
+// The same losses, the same LossArgs / parts layout and the same numerical forms as loss_fwd_bwd_kernel (log p, -expm1(h),
+// sigmoid(-z), the 2^64-scaled suffix scan, BPR's clamp), still one wave per interaction row, each lane owning R = ceil(S / 64)
+// segments.  STRIPED layout: segment j sits in lane j & 63, slot j >> 6.  Chosen over the blocked one (R consecutive segments
+// per lane) because every load and store of a slot is then one contiguous 256-byte line per wave, S needs no division by R, and a
+// slot is exactly the 64-lane row of the short kernel: each scan is that kernel's wave scan of the slot plus the carry (the
+// totals) of the slots before it (after it, for the suffix scan), and the value at the leave index v is one shuffle from lane
+// v & 63 of slot v >> 6.  The per-lane values live in arrays of the compile-time length R that are indexed only by fully
+// unrolled loops, so they are registers, never scratch.  Reductions add a lane's R slots in slot order, then the wave.
+template <int R>
+__device__ __forceinline__ float wave_sum_r(const float (&x)[R]) {
+    float t = x[0];
+#pragma unroll
+    for (int r = 1; r < R; ++r) t += x[r];
+    return wave_sum(t);
+}
+template <int R>
+__device__ __forceinline__ float wave_max_r(const float (&x)[R]) {
+    float t = x[0];
+#pragma unroll
+    for (int r = 1; r < R; ++r) t = fmaxf(t, x[r]);
+    return wave_max(t);
+}
+// x of segment v (0 <= v < 64 R; v is the same in every lane)
+template <int R>
+__device__ __forceinline__ float seg_pick_r(const float (&x)[R], int v) {
+    float o = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float t = __shfl(x[r], v & 63, 64);
+        if ((v >> 6) == r) o = t;
+    }
+    return o;
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= a.B) return;
+    const int S = a.S;                                   // 64 (R - 1) < S <= 64 R
+    const float n_valid_bpr = fmaxf(a.norms[0], 1.f);
+    const float Bg = a.norms[1];
+    const float mask_sum_global = fmaxf(a.norms[2], 1.f);
+    bool in[R], m[R];
+    int gt[R];
+    float z[R], p[R], q[R], h[R], surv[R], dz[R], qs[R], hz[R], t0[R], t1[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int j = r * 64 + lane;
+        in[r] = j < S;
+        z[r] = in[r] ? a.logits[(size_t)row * S + j] : 0.f;
+        if (in[r] && a.bias_w) z[r] += (float)(j + 1) * a.bias_w[j] + a.bias_b[j];
+        gt[r] = in[r] ? (int)a.gt[(size_t)row * S + j] : -2;
+        m[r] = in[r] && gt[r] != -2;
+        t0[r] = (in[r] && gt[r] == 1) ? 1.f : 0.f;
+        t1[r] = m[r] ? 1.f : 0.f;
+        dz[r] = 0.f;
+        qs[r] = 0.f;
+    }
+    const int v = (int)wave_sum_r<R>(t0);                // view length = index of the leave segment (counts <= 256: exact)
+    const int dur = (int)wave_sum_r<R>(t1);
+    // survival h_t = sum_(k <= t) log p_k: the wave scan of a slot plus the total of the slots before it
+    {
+        float carry = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            p[r] = sigmoidf_(z[r]);
+            q[r] = sigmoidf_(-z[r]);                     // 1 - p
+            const float logp = in[r] ? fminf(z[r], 0.f) - log1pf(expf(-fabsf(z[r]))) : 0.f;
+            const float sc = wave_scan_incl(logp, lane);
+            h[r] = carry + sc;
+            carry += __shfl(sc, 63, 64);
+            surv[r] = in[r] ? expf(h[r]) : 0.f;
+            hz[r] = m[r] ? -expm1f(h[r]) : 0.f;
+        }
+    }
+    float part[L_NPART];
+#pragma unroll
+    for (int k = 0; k < L_NPART; ++k) part[k] = 0.f;
+
+    // ---- interestBPR
+    if (a.enabled[L_BPR] && v < S) {
+        const float pos = seg_pick_r<R>(z, v);
+        float w[R], sg[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) t0[r] = (in[r] && r * 64 + lane != v) ? z[r] : -INFINITY;
+        const float mx = wave_max_r<R>(t0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) w[r] = (in[r] && r * 64 + lane != v) ? expf(z[r] - mx) : 0.f;
+        const float se = wave_sum_r<R>(w);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool neg = in[r] && r * 64 + lane != v;
+            w[r] = se > 0.f ? w[r] / se : 0.f;
+            sg[r] = neg ? sigmoidf_(z[r] - pos) : 0.f;
+            t0[r] = sg[r] * w[r];
+            t1[r] = w[r] * sg[r] * (1.f - sg[r]);
+        }
+        const float A = wave_sum_r<R>(t0);
+        const float Ac = fminf(fmaxf(A, 1e-8f), 1.0f - 1e-8f);
+        part[L_BPR] = -logf(Ac) / n_valid_bpr;
+        const float dA = (A >= 1e-8f && A <= 1.0f - 1e-8f) ? -1.0f / (A * n_valid_bpr) : 0.f;
+        const float dpos = -wave_sum_r<R>(t1);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool neg = in[r] && r * 64 + lane != v;
+            float gz = neg ? w[r] * (sg[r] * (1.f - sg[r]) + sg[r] - A) : 0.f;
+            if (r * 64 + lane == v) gz = dpos;
+            dz[r] += a.coef[L_BPR] * dA * gz;
+        }
+    }
+    // ---- focal
+    if (a.enabled[L_FOCAL]) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float t = (gt[r] > 0) ? 1.f : 0.f;
+            const float ex = in[r] ? a.exposure[r * 64 + lane] : 1.f;
+            const float ce = bce_logits(z[r], t);
+            const float pe = p[r] * ex;
+            const float pt = pe * t + (1.f - pe) * (1.f - t);
+            const float om = 1.f - pt;
+            t0[r] = m[r] ? 0.5f * ce * om * om : 0.f;
+            if (m[r]) {
+                const float dpt = (2.f * t - 1.f) * ex * p[r] * (1.f - p[r]);
+                dz[r] += a.coef[L_FOCAL] * 0.5f * ((p[r] - t) * om * om - 2.f * ce * om * dpt) / Bg;
+            }
+        }
+        part[L_FOCAL] = wave_sum_r<R>(t0) / Bg;
+    }
+    // ---- surviveCE
+    if (a.enabled[L_SCE]) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const float y = (gt[r] == 1) ? 1.f : 0.f;
+            t0[r] = m[r] ? bce_logits(surv[r], y) : 0.f;
+            if (m[r]) qs[r] += a.coef[L_SCE] * (sigmoidf_(surv[r]) - y) / mask_sum_global;
+        }
+        part[L_SCE] = wave_sum_r<R>(t0) / mask_sum_global;
+    }
+    // ---- interestCE / interestKL
+    if (a.enabled[L_ICE] || a.enabled[L_IKL]) {
+        float ni[R], logni[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) t0[r] = in[r] ? z[r] : -INFINITY;
+        const float mz = wave_max_r<R>(t0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) ni[r] = in[r] ? expf(z[r] - mz) : 0.f;
+        const float sz = wave_sum_r<R>(ni);
+        const float lsz = logf(sz);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            ni[r] = ni[r] / sz;
+            logni[r] = z[r] - mz - lsz;
+        }
+#pragma unroll
+        for (int which = 0; which < 2; ++which) {
+            const int L = which == 0 ? L_ICE : L_IKL;
+            if (!a.enabled[L]) continue;
+            const int rew = which == 0 ? a.gt_rewritten_for_ce : a.gt_rewritten_for_kl;
+            bool nz[R];
+            float ng[R], c[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                nz[r] = in[r] && (rew ? (gt[r] == 1 || gt[r] == -2) : (gt[r] != 0));
+                t0[r] = nz[r] ? 1.f : 0.f;
+            }
+            const float n1 = wave_sum_r<R>(t0);
+            const float gmax = n1 > 0.f ? 1.f : 0.f;
+#pragma unroll
+            for (int r = 0; r < R; ++r) ng[r] = in[r] ? expf((nz[r] ? 1.f : 0.f) - gmax) : 0.f;
+            const float sg = wave_sum_r<R>(ng);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                ng[r] = ng[r] / sg;
+                if (a.use_mask) {
+                    c[r] = m[r] ? ng[r] / (float)dur : 0.f;
+                    t0[r] = (which == 0) ? -c[r] * logni[r] : (m[r] ? c[r] * (logf(ng[r]) - logni[r]) : 0.f);
+                } else {
+                    c[r] = in[r] ? ng[r] : 0.f;
+                    t0[r] = (which == 0) ? (in[r] ? -ng[r] * logni[r] : 0.f) : (in[r] ? ng[r] * (logf(ng[r]) - logni[r]) : 0.f);
+                }
+            }
+            part[L] = wave_sum_r<R>(t0) / Bg;
+            const float csum = wave_sum_r<R>(c);
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (in[r]) dz[r] += a.coef[L] * (ni[r] * csum - c[r]) / Bg;
+        }
+    }
+    // ---- huber and mse / mse2
+    const float ssum_h = wave_sum_r<R>(hz);              // sum of masked hazard
+    {
+        const int dlast = dur > 0 ? dur - 1 : S - 1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            t0[r] = m[r] ? surv[r] : 0.f;
+            t1[r] = in[r] ? (r * 64 + lane == dlast ? 1.f : (m[r] ? surv[r] : 0.f)) : 0.f;
+        }
+        const float ssum = wave_sum_r<R>(t0);            // sum of masked survival
+        const float ssum2 = wave_sum_r<R>(t1);
+        float hub = 0.f, dhub = 0.f, e1 = 0.f, e2 = 0.f;
+        for (int i = lane; i < a.Bg; i += 64) {
+            const float vi = a.v_all[i];
+            if (a.enabled[L_HUBER]) {
+                const float err = ssum_h - vi, ae = fabsf(err);
+                hub += ae < 1.f ? 0.5f * err * err : ae - 0.5f;
+                dhub += ae < 1.f ? err : (err > 0.f ? 1.f : -1.f);
+            }
+            const float d1 = ssum - vi, d2 = ssum2 - a.v2_all[i];
+            e1 += d1 * d1;
+            e2 += d2 * d2;
+        }
+        const float inv = 1.0f / (Bg * Bg);
+        part[L_MSE] = wave_sum(e1) * inv;
+        part[L_MSE2] = wave_sum(e2) * inv;
+        if (a.enabled[L_HUBER]) {
+            part[L_HUBER] = wave_sum(hub) * inv;
+            const float dLds = wave_sum(dhub) * inv;     // d/d(sum of masked hazard)
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (m[r]) qs[r] += a.coef[L_HUBER] * (-dLds);
+        }
+    }
+    // ---- hazard
+    if (a.enabled[L_HAZARD] && v < S) {
+        const float ht = seg_pick_r<R>(hz, v) + 1e-6f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) t0[r] = (in[r] && r * 64 + lane >= v) ? hz[r] : 0.f;
+        const float Rk = wave_sum_r<R>(t0) + 1e-6f;
+        part[L_HAZARD] = -(logf(ht) - logf(Rk)) / Bg;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (m[r]) {
+                float dh = 0.f;
+                if (r * 64 + lane == v) dh -= 1.f / ht;
+                if (r * 64 + lane >= v) dh += 1.f / Rk;
+                qs[r] += a.coef[L_HAZARD] * (dh / Bg) * (-1.f);
+            }
+        }
+    }
+    // ---- survival chain: suffix scan of qs_j surv_j 2^64 (see loss_fwd_bwd_kernel), last slot first: the wave's suffix scan of a
+    // slot plus the total of the slots after it
+    {
+        float carry = 0.f;
+#pragma unroll
+        for (int r = R - 1; r >= 0; --r) {
+            const float sv = h[r] < -80.f ? expf(h[r] + 44.3614196f) : surv[r] * 18446744073709551616.f;
+            const float u = in[r] ? qs[r] * sv : 0.f;
+            const float sc = wave_suffix_incl(u, lane);
+            const float suf = sc + carry;
+            carry += __shfl(sc, 0, 64);
+            if (in[r]) dz[r] += (q[r] * suf) * 5.42101086242752217e-20f;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (in[r]) {
+            a.logits_out[(size_t)row * S + r * 64 + lane] = z[r];
+            if (a.dlogits) a.dlogits[(size_t)row * S + r * 64 + lane] = dz[r];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < L_PSTRIDE; ++k) a.parts[(size_t)row * L_PSTRIDE + k] = k < L_NPART ? part[k] : 0.f;
+    }
+}
+
 // Per-row label statistics (view length v = #(gt==1), v2 = #(gt>=0) on the possibly focal-rewritten
 // labels) and the three cross-row normalisers; one workgroup, deterministic.
 __global__ __launch_bounds__(1024) void label_stats_kernel(const long long* __restrict__ gt, int B, int S, int rewritten,
@@ -361,6 +629,37 @@ __global__ void rand_perm_rows_kernel(float* __restrict__ out, int rows, int S, 
         rank += (kj < key || (kj == key && j < lane)) ? 1 : 0;
     }
     if (lane < S) out[(size_t)row * S + rank] = (float)lane;          // out[row, :] is a permutation of 0 .. S-1 (as floats: frame positions)
+}
+// 64 < S <= 256: the same rank-of-a-key rule with the striped ownership of loss_fwd_bwd_long_kernel -- lane l draws the keys of
+// the indices l, l + 64, ... (R = ceil(S / 64) of them; a stream of its own, counter row * 256 + index) and counts, for each,
+// the (key, index) pairs of the row below it.  The row's keys go through LDS (1 KB per wave): every lane reads key j at the same
+// address, a broadcast read -- 256 cross-lane reads with compile-time lanes put the whole row into scalar registers and
+// spilled them.  Only indices < S are counted, so every rank is < S.
+template <int R>
+__global__ __launch_bounds__(256) void rand_perm_rows_long_kernel(float* __restrict__ out, int rows, int S, DropCfg d0) {
+    __shared__ uint32_t keys[4][256];
+    const DropCfg d = drop_live(d0);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, row = blockIdx.x * 4 + w;
+    uint32_t key[R];
+    int rank[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint2 x = drop_rand_quad(d, (uint64_t)row * 256u + (uint64_t)(r * 64 + lane));
+        key[r] = x.x;
+        rank[r] = 0;
+        keys[w][r * 64 + lane] = x.x;
+    }
+    __syncthreads();
+    if (row >= rows) return;
+    for (int j = 0; j < S; ++j) {
+        const uint32_t kj = keys[w][j];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            rank[r] += (kj < key[r] || (kj == key[r] && j < r * 64 + lane)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (r * 64 + lane < S) out[(size_t)row * S + rank[r]] = (float)(r * 64 + lane);
 }
 
 }  // namespace segmm

@@ -1053,6 +1053,20 @@ class BackboneRun:
         return finish_act(st, a)
 
     # ---------------------------------------------------------------- forward
+    def _require_attn_keys(self, S, Lt):
+        """The attention kernels keep the keys of both blocks, each padded to a multiple of 16, in at most 12 tiles (``attn_fill``,
+        capi.hip).  Checked here, before the pass enqueues anything, for every attention call it would make."""
+        if self.abl in MLP_VARIANTS or self.N < 2:
+            return
+        pad16 = lambda n: (n + 15) & ~15
+        calls = [(0 if self.mode == "cross" else S, 0 if self.mode == "self" else Lt)]
+        if self.N >= 3 and self.mode != "self":
+            calls.append((S, 0 if self.mode == "cross" else Lt))
+        keys = max(pad16(La) + pad16(Lb) for La, Lb in calls)
+        if keys > 192:
+            raise RuntimeError("attn: S=%d video segments and Lt=%d user tokens make %d padded keys > 192 not built "
+                               "(the limit is pad16(S) + pad16(Lt) <= 192)" % (S, Lt, keys))
+
     def forward(self, usr_feat, usr_mask, vid_feat, vid_mask, train: bool, seed: int):
         st, bb, P, d = self.store, self.bb, self.pre, self.d
         p_drop = float(bb.dropout_p) if train else 0.0
@@ -1065,6 +1079,10 @@ class BackboneRun:
         # producer-written planes with delayed scales in training passes; exact split passes otherwise (evaluation stays
         # bitwise reproducible and independent of what ran before)
         self.delayed = st.engine_p and ((train and st.scaling != "exact") or st.scaling == "always")
+        # (sizes the checks below refuse keep their own messages)
+        S0, Lt0 = int(vid_mask.shape[-1]), 1 if bb.id_usr else (int(usr_feat.shape[1]) if usr_feat.dim() == 3 else 0)
+        if S0 <= bb.max_vid_len and Lt0 <= bb.max_usr_len:
+            self._require_attn_keys(S0, Lt0)
         vm = _mask_u8(vid_mask)
         B, S = vm.shape
         if S > bb.max_vid_len:
@@ -1149,7 +1167,7 @@ class BackboneRun:
                 # lives on the device (Trainer(device_state=True): the step may be recorded), drawn on the device: the same
                 # distribution (a uniformly random permutation per row), another bit stream
                 live = st.__dict__.get("live_seed")
-                if live is not None and train and S <= 64:
+                if live is not None and train and S <= 256:
                     fpos = st.buf("nopos_fpos%d" % self.bi, (B, S))
                     H.rand_perm_rows(fpos, B, S, live, SITE_NOPOS + 16 * self.bi)
                 else:
