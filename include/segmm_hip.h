@@ -25,7 +25,8 @@ extern "C" {
 typedef void* segmm_stream_t; /* hipStream_t */
 
 const char* segmm_last_error(void);
-int segmm_abi_version(void);
+#define SEGMM_ABI_VERSION 30
+int segmm_abi_version(void); /* SEGMM_ABI_VERSION of the header the library was built from */
 
 /* a1 -- trainer L1 normalisation  x / (sum|x| + 1e-6)  (main_for_seq_leave_earlystop_SegMM.py:272-273).
  * y may be NULL: then only inv_scale[row] = 1/(sum|x|+1e-6) is produced, for the fused a1+a2 GEMM (row_scale) -- or, with a

@@ -509,7 +509,7 @@ __global__ void step_advance_kernel(StepState* st, float b1, float b2) {
 extern "C" {
 
 const char* segmm_last_error(void) { return g_segmm_err; }
-int segmm_abi_version(void) { return 30; }
+int segmm_abi_version(void) { return SEGMM_ABI_VERSION; }
 int segmm_attn_mode(int mode) { const int prev = attn_f16(); if (mode >= 0 && mode <= 2) g_knobs[K_ATTN].value = mode; return prev; }
 
 static PlaneOut plane_out(uint16_t* planes, int ld2, float* hdr, const float* scale_in) {

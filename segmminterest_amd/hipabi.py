@@ -13,106 +13,22 @@ from typing import Optional
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SEGMM_LIB") or os.path.join(_HERE, "libsegmm_hip.so")      # SEGMM_LIB: A/B builds of the kernels
-ABI_VERSION = 30
 
 _lib = None
 
 _i, _i64, _f, _u64, _u32, _p = C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_uint32, C.c_void_p
 
-# name -> argtypes; the single source of truth for the exported symbol set (tests check it against the header)
-SIGNATURES = {
-    "segmm_l1norm": [_p, _p, _p, _i64, _i, _p, _p, _i, _p, _p, _p],
-    "segmm_gemm": [_i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _p, _i, _f, _u64, _u32, _i, _p, _i, _i, _p],
-    "segmm_gemm_x": [_i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _p, _i, _f, _u64, _u32, _i, _p, _i,
-                     _p, _i64, _p, _i64, _i, _p],
-    "segmm_gemm_h": [_i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _p, _i, _f, _u64, _u32, _i, _p, _i,
-                     _p, _i64, _p, _i64, _p, _i, _p, _i, _p, _p],
-    "segmm_gemm_p": [_i, _i, _i, _i, _p, _i, _p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _i, _f, _u64,
-                     _u32, _i, _p, _i, _p, _p],
-    "segmm_scales_update": [_p, _p, _i, _p, _p, _i, _p, _p, _p],
-    "segmm_probe_mfma_rate": [_i, _i, _p, _p, _p],
-    "segmm_attn_mode": [_i],
-    "segmm_config_set": [_p, _i],
-    "segmm_config_dump": [_p, _i],
-    "segmm_site_fixup": [_p, _p, _p, _p, _p, _p],
-    "segmm_step_bind": [_p],
-    "segmm_step_state_bytes": [],
-    "segmm_step_set": [_u64, _i, _f, _f, _p],
-    "segmm_step_advance": [_f, _f, _p],
-    "segmm_step_get": [_p, _p, _p, _p],
-    "segmm_loss_finish": [_p, _i, _p, _p, _p, _p, _i64, _p, _p, _i, _p, _i, _p],
-    "segmm_split_p32": [_p, _i64, _i, _i, _p, _i, _p, _i, _p],
-    "segmm_split_p32_transpose": [_p, _i, _i, _i, _p, _i, _p, _p],
-    "segmm_wsplit_p32": [_p, _p, _i, _i, _p, _p, _p, _p],
-    "segmm_absmax": [_p, _i64, _i, _i, _p, _i, _p],
-    "segmm_split2h": [_p, _p, _i64, _i64, _p, _i, _p],
-    "segmm_split2h_transpose": [_p, _i, _i, _i, _p, _i64, _p, _i, _p],
-    "segmm_split3": [_p, _p, _i64, _i64, _p],
-    "segmm_split3_transpose": [_p, _i, _i, _i, _p, _i64, _p],
-    "segmm_layernorm_fwd": [_p, _p, _p, _p, _p, _p, _i64, _i, _f, _f, _u64, _u32, _p, _p, _i, _p, _p, _p],
-    "segmm_layernorm_fwd_dot": [_p, _p, _p, _p, _p, _p, _i64, _i, _f, _f, _u64, _u32, _p, _p, _i, _p, _p, _p, _p, _p, _p],
-    "segmm_layernorm_bwd_parts": [_i64, _i],
-    "segmm_layernorm_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _f, _u32, _f, _u32, _u64, _p, _p, _i, _p, _p, _p],
-    "segmm_layernorm_bwd_outer": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _f, _u32, _f, _u32, _u64, _p, _p, _i, _p, _p, _p],
-    "segmm_layernorm_bwd_pos_parts": [_i64, _i, _i],
-    "segmm_layernorm_bwd_pos": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _f, _u32, _f, _u32, _u64, _p, _p, _i, _p, _p, _p, _i, _p],
-    "segmm_colsum_pos": [_p, _i, _i, _i, _p, _p],
-    "segmm_colsum_chunks": [_i64],
-    "segmm_colsum": [_p, _i, _p, _i64, _i, _p, _i, _p, _p],
-    "segmm_attn_fwd": [_i] * 6 + [_p, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _f, _u64, _u32, _p, _p, _p],
-    "segmm_attn_bwd": [_i] * 6 + [_p, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _i,
-                                  _p, _p, _i, _f, _u64, _u32, _p, _p, _p, _i, _p, _p],
-    "segmm_rowdot": [_p, _i, _p, _p, _p, _i64, _i, _i, _p],
-    "segmm_rowscale_bcast": [_p, _p, _p, _i, _i64, _i, _i, _p],
-    "segmm_vecsum": [_p, _i64, _p, _i, _p],
-    "segmm_rowdot_pair": [_p, _i, _p, _i, _p, _i64, _i, _i, _p],
-    "segmm_rowscale_mat": [_p, _p, _i, _p, _i, _i64, _i, _i, _p],
-    "segmm_embed_id_vid": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i64, _p],
-    "segmm_embed_id_usr": [_p, _p, _i, _p, _p, _i, _i64, _p],
-    "segmm_embed_id_bwd": [_p, _i, _i, _i, _i, _p, _p, _p, _i, _i64, _p],
-    "segmm_pe_grad": [_p, _i, _i, _i, _i, _p, _i, _p],
-    "segmm_argsort_ids": [_p, _i, _p, _p],
-    "segmm_argsort_ids_ws": [_p, _i, _p, _p, _p],
-    "segmm_label_stats_unpack": [_p, _i, _i, _p, _p, _p, _p],
-    "segmm_zero_rows": [_p, _i, _p, _i, _i64, _p],
-    "segmm_label_stats": [_p, _i, _i, _i, _p, _p, _p, _p],
-    "segmm_loss_fwd_bwd": [_i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p],
-    "segmm_adamw": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _p],
-    "segmm_adamw_table": [_p, _p, _p, _p, _i64, _i, _p, _i, _p, _f, _f, _f, _f, _f, _i, _i, _p],
-    "segmm_adamw_scaled": [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _p, _p],
-    "segmm_adamw_table_scaled": [_p, _p, _p, _p, _i64, _i, _p, _i, _p, _f, _f, _f, _f, _f, _i, _p, _p],
-    "segmm_grad_norm": [_p, _i64, _f, _p, _p, _p],
-    "segmm_dropout_mult": [_p, _i64, _f, _u64, _u32, _p],
-    "segmm_rank_leave": [_p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p],
-    "segmm_auc_counts": [_p, _p, _p, _i, _p, _p],
-    "segmm_survival": [_p, _i, _p, _p, _p, _i, _i, _p],
-    "segmm_row_metrics": [_p, _i, _p, _p, _p, _i64, _i, _i, _p, _p, _p],
-    "segmm_row_metrics_accumulate": [_p, _p, _i, _i, _p, _p],
-    "segmm_gather_l1": [_p, _i64, _i, _p, _i64, _i, _p, _p, _p, _p, _i, _p, _p, _p],
-    "segmm_segment_weighted_sum": [_p, _p, _p, _i64, _i, _p, _p],
-    "segmm_colsum3": [_p, _p, _p, _i, _i64, _i, _p, _p, _p, _p, _p],
-    "segmm_pool_tokens": [_p, _i, _p, _i, _p, _i, _i, _i, _p],
-    "segmm_pool_tokens_bwd": [_p, _p, _i, _p, _i, _i, _i, _i, _p],
-    "segmm_bias_grad": [_p, _i, _i, _p, _p, _p],
-    "segmm_focal_relabel": [_p, _i64, _p],
-    "segmm_rand_uniform": [_p, _i64, _u64, _u32, _p],
-    "segmm_rand_ids": [_p, _i64, _i64, _i64, _u64, _u32, _p],
-    "segmm_rand_perm_rows": [_p, _i, _i, _u64, _u32, _p],
-    "segmm_fill_zero": [_p, _i64, _p],
-    "segmm_copy_bytes": [_p, _p, _i64, _p],
-    "segmm_cmd_op_count": [],
-    "segmm_run_phase": [_p, _p, _i, _p],
-    "segmm_step_begin": [_p, _p, _i, _p],
-    "segmm_embed_fwd": [_p, _p, _i, _p],
-    "segmm_layer_fwd": [_p, _p, _i, _p],
-    "segmm_head_loss_fwd": [_p, _p, _i, _p],
-    "segmm_head_loss_bwd": [_p, _p, _i, _p],
-    "segmm_layer_bwd": [_p, _p, _i, _p],
-    "segmm_embed_bwd": [_p, _p, _i, _p],
-    "segmm_step_tail": [_p, _p, _i, _p],
-}
+# The mirror of include/segmm_hip.h comes from _abi.py, which tools/gen_cmd_dispatch.py generates from the header (build() refuses
+# a stale one).  segmm_abi_version is left out of the tables: _lib_real binds it by hand, it gates everything else.
+ABI_VERSION = _abi.ABI_VERSION
+_CTYPE = {"i": _i, "i64": _i64, "f": _f, "u64": _u64, "u32": _u32, "p": _p}
+_PROTOS = {n: ps for n, ps in _abi.PROTOTYPES.items() if n != "segmm_abi_version"}
+SIGNATURES = {n: [_CTYPE[c] for _, c in ps] for n, ps in _PROTOS.items()}          # name -> argtypes
+PARAMS = {n: tuple(p for p, _ in ps) for n, ps in _PROTOS.items()}                 # name -> parameter names
 
 
 def lib():
@@ -154,10 +70,12 @@ def _lib_real():
 # include/segmm_hip.h "Recorded launch sequences": the per-op calls of ONE eager training step are recorded (entry point, its
 # arguments, the stream slot) and replayed every step from C by segmm_run_phase / the named phase entry points -- one
 # foreign-function call per part of the step instead of one per kernel (+ the Python that sequences them).
-CMD_MAX_ARGS = 48
-OP_FORK, OP_JOIN = -1, -2
+_K = _abi.CONSTANTS
+CMD_MAX_ARGS = _K["SEGMM_CMD_MAX_ARGS"]
+OP_FORK, OP_JOIN = _K["SEGMM_OP_FORK"], _K["SEGMM_OP_JOIN"]
 (PHASE_STEP_BEGIN, PHASE_EMBED_FWD, PHASE_LAYER_FWD, PHASE_HEAD_LOSS_FWD, PHASE_HEAD_LOSS_BWD, PHASE_LAYER_BWD, PHASE_EMBED_BWD,
- PHASE_STEP_TAIL) = range(8)
+ PHASE_STEP_TAIL) = (_K["SEGMM_PHASE_" + n] for n in ("STEP_BEGIN", "EMBED_FWD", "LAYER_FWD", "HEAD_LOSS_FWD", "HEAD_LOSS_BWD", "LAYER_BWD",
+                                                      "EMBED_BWD", "STEP_TAIL"))
 PHASE_ENTRY = ("segmm_step_begin", "segmm_embed_fwd", "segmm_layer_fwd", "segmm_head_loss_fwd", "segmm_head_loss_bwd",
                "segmm_layer_bwd", "segmm_embed_bwd", "segmm_step_tail")
 
@@ -174,6 +92,17 @@ class Cmd(C.Structure):
 class Phase(C.Structure):
     """segmm_phase_t"""
     _fields_ = [("kind", C.c_int32), ("backbone", C.c_int32), ("layer", C.c_int32), ("n_cmds", C.c_int32), ("cmds", C.POINTER(Cmd))]
+
+
+def _member(ct):
+    """The segmm_arg_t member that carries an argument of ctypes type ``ct`` (what the generated dispatch switch reads it from)."""
+    return "f" if ct is _f else "p" if ct is _p else "i"
+
+
+def cmd_arg(c, name, param):
+    """The value of parameter ``param`` (its name in the header) in the recorded command ``c`` of the entry point ``name``."""
+    k = PARAMS[name].index(param)
+    return getattr(c.a[k], _member(SIGNATURES[name][k]))
 
 
 _op_ids = None
@@ -230,10 +159,11 @@ class Recorder:
             raise RuntimeError("recorder: %s was enqueued on a stream that is neither the step's main, side nor auxiliary stream; this "
                                "launch sequence cannot be replayed (prefetch / third-stream knobs must be off)" % name)
         vals = []
-        for k, (ct, v) in enumerate(zip(at[:-1], args[:-1])):
-            if ct is _f:
+        for ct, v in zip(at[:-1], args[:-1]):
+            fld = _member(ct)
+            if fld == "f":
                 vals.append(("f", float(v)))
-            elif ct is _p:
+            elif fld == "p":
                 if v is None:
                     vals.append(("p", None))
                 elif isinstance(v, int):
@@ -379,6 +309,26 @@ ATTN_PROFILE = None       # ... and every attention launch: (kind, B, H, dh, Lq,
 KERNEL_PROFILE = None     # ... and selected HBM-bound launches: (name, algorithmic bytes, event0, event1)
 
 
+def gemm_record(layout, M, N, K, write_c=None):
+    """What a GEMM_PROFILE entry of one GEMM launch starts with, or None for a launch that is not timed.  ``write_c``: that argument
+    of segmm_gemm_p (None: a launch of segmm_gemm / _x / _h).  A plane-engine launch is listed under 10 + layout (bench.py's
+    per-shape table); its repair launch (write_c bit 1) does no work normally: not a GEMM of the roofline."""
+    if write_c is None:
+        return (layout, M, N, K)
+    return None if write_c & 2 else (10 + layout, M, N, K)
+
+
+def attn_record(B, H, dh, Lq, La, Lb, phase=None, planes=None):
+    """What an ATTN_PROFILE entry of one attention launch starts with.  ``phase`` / ``planes`` (an AttnPlanes or None): those
+    arguments of segmm_attn_bwd; ``phase=None``: a forward launch."""
+    if phase is None:
+        return ("fwd", B, H, dh, Lq, La, Lb)
+    repair = planes is not None and (planes.flags & ATTN_REPAIR)
+    kind = "bwd" if phase == 0 else "bwd4r" if repair else "bwd4" if phase >= 4 else "bwd%d" % phase
+    # (phase 5 / 6 = one key block of the fused backward: its FLOPs are the block's; a repair launch does no work normally)
+    return (kind, B, H, dh, Lq, 0 if phase == 6 else La, 0 if phase == 5 else Lb)
+
+
 class _kprof:
     """``with _kprof(name, nbytes):`` -- HIP events around a launch when bench.py asked for them (KERNEL_PROFILE is a list)."""
 
@@ -423,7 +373,7 @@ ENGINE_F32, ENGINE_BF16X6, ENGINE_F16X3, ENGINE_F16X3P = 0, 1, 2, 3
 # "f16x3p" (default): the same fp16x3 arithmetic with operands PRE-SPLIT into fp16 planes by their producers and staged by
 # LDS-DMA (gemm_p / csrc/gemm_planes.h); raw gemm() calls under it run the on-the-fly fp16x3 kernel.
 GEMM_ENGINE = {"f32": 0, "bf16x6": 1, "f16x3": 2, "f16x3p": 3}[os.environ.get("SEGMM_GEMM", "f16x3p")]
-AMAX_SLOTS = 256          # partial maxima per tensor written by the fused producers (SEGMM_AMAX_SLOTS)
+AMAX_SLOTS = _K["SEGMM_AMAX_SLOTS"]          # partial maxima per tensor written by the fused producers (SEGMM_AMAX_SLOTS)
 AMAX_PARTS = 1024         # ... and by the stand-alone absmax() pass
 LAYOUT_NT, LAYOUT_NN, LAYOUT_TN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_RELU, ACT_DRELU = 0, 1, 2, 3, 4
@@ -473,6 +423,12 @@ def gemm(layout, M, N, K, A, lda, B, ldb, Cout, ldc, bias=None, row_scale=None, 
     eng = GEMM_ENGINE if engine is None else int(engine)
     if eng == ENGINE_F16X3P:
         eng = ENGINE_F16X3
+    # the arguments segmm_gemm / _x / _h share (a null fp32 operand is refused by the library unless its planes are given)
+    head = (layout, M, N, K, None if A is None else A.data_ptr() + a_off * es, lda, None if B is None else B.data_ptr() + b_off * es, ldb,
+            Cout.data_ptr() + c_off * es, ldc, _ptr(bias), _ptr(row_scale), _ptr(residual), ldr, res_period, activation, _ptr(aux), ldaux,
+            float(drop_p), int(seed), int(site), int(splits), _ptr(workspace), int(bool(accumulate)))
+    planes = (None if a_planes is None else a_planes[0].data_ptr() + 2 * a_planes[1], 0 if a_planes is None else a_planes[0].stride(0),
+              None if b_planes is None else b_planes[0].data_ptr() + 2 * b_planes[1], 0 if b_planes is None else b_planes[0].stride(0))
     if eng == ENGINE_F16X3:
         if a_amax is None:
             if a_planes is not None:
@@ -482,42 +438,21 @@ def gemm(layout, M, N, K, A, lda, B, ldb, Cout, ldc, bias=None, row_scale=None, 
             if b_planes is not None:
                 raise RuntimeError("pre-split fp16 planes need the partial maxima they were made with")
             b_amax = absmax(B, N if layout == LAYOUT_NT else K, K if layout == LAYOUT_NT else N, ldb, off=b_off)
-        ap = None if a_planes is None else a_planes[0].data_ptr() + 2 * a_planes[1]
-        aps = 0 if a_planes is None else a_planes[0].stride(0)
-        bp = None if b_planes is None else b_planes[0].data_ptr() + 2 * b_planes[1]
-        bps = 0 if b_planes is None else b_planes[0].stride(0)
-        _check(lib().segmm_gemm_h(layout, M, N, K, None if A is None else A.data_ptr() + a_off * es, lda,
-                                  None if B is None else B.data_ptr() + b_off * es, ldb,
-                                  Cout.data_ptr() + c_off * es, ldc, _ptr(bias), _ptr(row_scale), _ptr(residual), ldr,
-                                  res_period, activation, _ptr(aux), ldaux, float(drop_p), int(seed), int(site),
-                                  int(splits), _ptr(workspace), int(bool(accumulate)), ap, aps, bp, bps,
-                                  a_amax.data_ptr(), a_amax.numel(), b_amax.data_ptr(), b_amax.numel(), _ptr(c_amax),
+        _check(lib().segmm_gemm_h(*head, *planes, a_amax.data_ptr(), a_amax.numel(), b_amax.data_ptr(), b_amax.numel(), _ptr(c_amax),
                                   _stream()), "segmm_gemm_h")
     elif a_planes is None and b_planes is None and nplanes == 3:
-        _check(lib().segmm_gemm(layout, M, N, K, A.data_ptr() + a_off * es, lda, B.data_ptr() + b_off * es, ldb,
-                                Cout.data_ptr() + c_off * es, ldc, _ptr(bias), _ptr(row_scale), _ptr(residual), ldr,
-                                res_period, activation, _ptr(aux), ldaux, float(drop_p), int(seed), int(site),
-                                int(splits), _ptr(workspace), int(bool(accumulate)), eng, _stream()), "segmm_gemm")
+        _check(lib().segmm_gemm(*head, eng, _stream()), "segmm_gemm")
     else:
         if eng != ENGINE_BF16X6:
             raise RuntimeError("pre-split operands / nplanes=2 need the bf16x6 engine")
-        ap = None if a_planes is None else a_planes[0].data_ptr() + 2 * a_planes[1]
-        aps = 0 if a_planes is None else a_planes[0].stride(0)
-        bp = None if b_planes is None else b_planes[0].data_ptr() + 2 * b_planes[1]
-        bps = 0 if b_planes is None else b_planes[0].stride(0)
-        _check(lib().segmm_gemm_x(layout, M, N, K, None if A is None else A.data_ptr() + a_off * es, lda,
-                                  None if B is None else B.data_ptr() + b_off * es, ldb,
-                                  Cout.data_ptr() + c_off * es, ldc, _ptr(bias), _ptr(row_scale), _ptr(residual), ldr,
-                                  res_period, activation, _ptr(aux), ldaux, float(drop_p), int(seed), int(site),
-                                  int(splits), _ptr(workspace), int(bool(accumulate)), ap, aps, bp, bps, int(nplanes),
-                                  _stream()), "segmm_gemm_x")
+        _check(lib().segmm_gemm_x(*head, *planes, int(nplanes), _stream()), "segmm_gemm_x")
     if prof is not None:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
-        prof.append((layout, M, N, K, e0, e1))
+        prof.append(gemm_record(layout, M, N, K) + (e0, e1))
 
 
-SITE_HDR = 8                                  # floats in front of the partial maxima of a plane tensor's site header
+SITE_HDR = _K["SEGMM_SITE_HDR"]          # floats in front of the partial maxima of a plane tensor's site header
 SITE_FLOATS = SITE_HDR + AMAX_SLOTS
 
 
@@ -583,7 +518,9 @@ def gemm_p(layout, M, N, K, A: "PT", B: "PT", Cout, ldc, c_pt: "PT" = None, writ
     ``c_hdr``: site header that only receives the partial maxima of |C| (no plane output).  ``repair``: the REPAIR launch of a
     planes-only NT output (``Cout=None, write_c=False``): same arguments, workgroups leave at once unless the output site's planes
     are unusable under the recorded scale, in which case they are rewritten with the exact scale of the recorded maxima."""
-    prof = GEMM_PROFILE if not repair else None          # (a repair launch does no work normally: not a GEMM of the roofline)
+    wc = int(bool(write_c)) | (2 if repair else 0)
+    head = gemm_record(layout, M, N, K, wc)
+    prof = GEMM_PROFILE if head is not None else None
     if prof is not None:
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -591,14 +528,13 @@ def gemm_p(layout, M, N, K, A: "PT", B: "PT", Cout, ldc, c_pt: "PT" = None, writ
                               B.fptr(), B.ldf, None if Cout is None else Cout.data_ptr() + 4 * c_off, ldc,
                               None if c_pt is None else c_pt.pptr(), 0 if c_pt is None else c_pt.ld2,
                               (None if c_hdr is None else c_hdr.data_ptr()) if c_pt is None else c_pt.hdr.data_ptr(), c_scale_ptr,
-                              int(bool(write_c)) | (2 if repair else 0),
-                              _ptr(bias), _ptr(row_scale), _ptr(residual),
+                              wc, _ptr(bias), _ptr(row_scale), _ptr(residual),
                               ldr, res_period, activation, _ptr(aux), ldaux, float(drop_p), int(seed), int(site), int(splits),
                               _ptr(workspace), int(bool(accumulate)), _ptr(colsum_out), _stream()), "segmm_gemm_p")
     if prof is not None:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
-        prof.append((10 + layout, M, N, K, e0, e1))          # 10 +: a plane-engine launch (bench.py's per-shape table)
+        prof.append(head + (e0, e1))
 
 
 def scales_update(arena, site_idx, n_rows, site_scale, stats, target=12, gain=None, gmax=None):
@@ -805,16 +741,10 @@ def colsum(X, ld, M, N, out, workspace, w=None, accumulate=False, x_off=0, out_o
 
 class AttnPlanes(C.Structure):
     """segmm_attn_planes_t"""
-    _fields_ = [("o", _p), ("ldo2", _i), ("hdr_o", _p), ("sin_o", _p),
-                ("dqa", _p), ("dqb", _p), ("lddq2", _i), ("dka", _p), ("dva", _p), ("lddka2", _i),
-                ("dkb", _p), ("dvb", _p), ("lddkb2", _i), ("hdr_q", _p), ("hdr_ka", _p), ("hdr_kb", _p),
-                ("sin_q", _p), ("sin_ka", _p), ("sin_kb", _p), ("flags", _i),
-                ("qa_in", _p), ("qb_in", _p), ("ldq2_in", _i), ("hdr_q_in", _p),
-                ("ka_in", _p), ("va_in", _p), ("ldka2_in", _i), ("hdr_ka_in", _p),
-                ("kb_in", _p), ("vb_in", _p), ("ldkb2_in", _i), ("hdr_kb_in", _p)]
+    _fields_ = [(n, _CTYPE[c]) for n, c in _abi.ATTN_PLANES_FIELDS]
 
 
-ATTN_PLANES_ONLY, ATTN_REPAIR = 1, 2
+ATTN_PLANES_ONLY, ATTN_REPAIR = _K["SEGMM_ATTN_PLANES_ONLY"], _K["SEGMM_ATTN_REPAIR"]
 
 
 def site_fixup(*hdrs, stats=None):
@@ -865,7 +795,7 @@ def attn_fwd(B, H, dh, Lq, La, Lb, Qa, Qb, ldq, Ka, Va, ldka, Kb, Vb, ldkb, mq, 
     if prof is not None:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
-        prof.append(("fwd", B, H, dh, Lq, La, Lb, e0, e1))
+        prof.append(attn_record(B, H, dh, Lq, La, Lb) + (e0, e1))
 
 
 def attn_bwd(B, H, dh, Lq, La, Lb, Qa, Qb, ldq, Ka, Va, ldka, Kb, Vb, ldkb, mq, mka, mkb, lse, O, ldo, dO, lddo, Dvec,
@@ -893,10 +823,7 @@ def attn_bwd(B, H, dh, Lq, La, Lb, Qa, Qb, ldq, Ka, Va, ldka, Kb, Vb, ldkb, mq, 
     if prof is not None:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
-        repair = planes is not None and (planes.flags & ATTN_REPAIR)
-        kind = "bwd" if phase == 0 else "bwd4r" if repair else "bwd4" if phase >= 4 else "bwd%d" % phase
-        # (phase 5 / 6 = one key block of the fused backward: its FLOPs are the block's; a repair launch does no work normally)
-        prof.append((kind, B, H, dh, Lq, 0 if phase == 6 else La, 0 if phase == 5 else Lb, e0, e1))
+        prof.append(attn_record(B, H, dh, Lq, La, Lb, phase, planes) + (e0, e1))
 
 
 ARGSORT_MAX = 8192

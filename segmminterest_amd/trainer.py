@@ -1012,21 +1012,19 @@ class Trainer:
             for ci in range(ph.n_cmds):
                 c = arr[ci]
                 nm = names.get(c.op)
+                def args(*params, c=c, nm=nm):          # the command's arguments, by the header's parameter names
+                    return [H.cmd_arg(c, nm, p) for p in params]
                 rec = None
-                if nm == "segmm_gemm_p":
-                    if not (c.a[20].i & 2):          # (a repair launch does no work normally: not a GEMM of the roofline)
-                        rec = ("gemm", (10 + c.a[0].i, c.a[1].i, c.a[2].i, c.a[3].i))
-                elif nm in ("segmm_gemm", "segmm_gemm_h"):
-                    rec = ("gemm", (c.a[0].i, c.a[1].i, c.a[2].i, c.a[3].i))
+                if nm in ("segmm_gemm", "segmm_gemm_h"):
+                    rec = ("gemm", H.gemm_record(*args("layout", "M", "N", "K")))
+                elif nm == "segmm_gemm_p":
+                    rec = ("gemm", H.gemm_record(*args("layout", "M", "N", "K", "write_c")))
                 elif nm == "segmm_attn_fwd":
-                    rec = ("attn", ("fwd",) + tuple(c.a[k].i for k in range(6)))
+                    rec = ("attn", H.attn_record(*args("B", "H", "dh", "Lq", "La", "Lb")))
                 elif nm == "segmm_attn_bwd":
-                    phase = c.a[39].i
-                    repair = bool(c.a[40].p) and bool(H.AttnPlanes.from_address(c.a[40].p).flags & H.ATTN_REPAIR)
-                    kind = "bwd" if phase == 0 else "bwd4r" if repair else "bwd4" if phase >= 4 else "bwd%d" % phase
-                    B_, H_, dh_, Lq_, La_, Lb_ = (c.a[k].i for k in range(6))
-                    rec = ("attn", (kind, B_, H_, dh_, Lq_, 0 if phase == 6 else La_, 0 if phase == 5 else Lb_))
-                if rec is None:
+                    planes, = args("planes")
+                    rec = ("attn", H.attn_record(*args("B", "H", "dh", "Lq", "La", "Lb", "phase"), H.AttnPlanes.from_address(planes) if planes else None))
+                if rec is None or rec[1] is None:          # (gemm_record: a repair launch is not timed)
                     continue
                 if ci > lo:
                     plan.append(("run", sub(lo, ci)))

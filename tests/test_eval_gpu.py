@@ -535,6 +535,41 @@ def test_recorded_step_equals_eager_device_state_step(kind, N, B, S, Lt, D, h):
 
 
 @pytest.mark.gpu
+def test_timed_replay_labels_the_launches_like_the_eager_step():
+    """bench.py's roofline pass labels a launch of the timed replay from the recorded command's arguments (Trainer._timed_plan:
+    found by the header's parameter names), the eager step from the wrapper's own (hipabi.GEMM_PROFILE / ATTN_PROFILE).  The
+    recording IS an eager step and both skip the GEMM repair launches, so the two label lists are equal, in order."""
+    import torch
+    from segmminterest_amd import hipabi as H
+    from segmminterest_amd.synth import make_batch
+    from segmminterest_amd.trainer import Trainer, default_args, init_model
+    dev = torch.device("cuda:0")
+    N, B, S, Lt, D, h = 2, 16, 40, 10, 64, 4
+    margs = default_args(num_layers_enc=N, d_model=D, nhead=h, input_type={"user": "image", "photo": "image"}, exposure_prob=[1.0] * S)
+    batch = {k: v.to(dev) for k, v in make_batch(B, S, Lt, D, n_users=50, n_items=500, seed=300).items()}
+    torch.manual_seed(7)
+    model = init_model(margs, n_users=50, n_items=500, input_dim=D, max_vid_len=S, max_usr_len=Lt).to(dev)
+    tr = Trainer(model, lr=1e-3, weight_decay=1e-4, device_state=True)
+    for _ in range(3):
+        tr.train_step(batch)
+    H.GEMM_PROFILE, H.ATTN_PROFILE = [], []
+    try:
+        tr.train_step(batch)
+        eager = ([g[:-2] for g in H.GEMM_PROFILE], [a[:-2] for a in H.ATTN_PROFILE])
+    finally:
+        H.GEMM_PROFILE = H.ATTN_PROFILE = None
+    tr.record(batch)
+    timed = ([], [])
+    tr.run_recorded(batch, timed=timed)
+    torch.cuda.synchronize()
+    print("eager GEMM records:", eager[0], "\ntimed GEMM records:", [g[:-2] for g in timed[0]])
+    print("eager attention records:", eager[1], "\ntimed attention records:", [a[:-2] for a in timed[1]])
+    assert len(eager[0]) >= 10 and len(eager[1]) >= 2
+    assert [g[:-2] for g in timed[0]] == eager[0]
+    assert [a[:-2] for a in timed[1]] == eager[1]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("variant", ["learnable_bias", "focal_first", "noUser", "noUser_SelfAtt", "noPos"])
 def test_recorded_step_covers_every_step_variant_of_the_reference(variant):
     """Round 5: record() accepts the variants it used to refuse because they kept torch ops or host draws inside the step --
