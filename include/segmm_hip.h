@@ -316,9 +316,9 @@ int segmm_loss_finish(const float* parts, int B, const float* coef, float* losse
  * segmm_label_stats fills v[B] = #(gt==1), v2[B] = #(gt>=0) (after the optional focal rewrite) and the device
  * array norms[3] = {#rows with v < S, B, #(gt != -2)}; a data-parallel trainer all-gathers v/v2 and sums norms
  * over ranks before the loss call, so every rank normalises by the GLOBAL counts without a host sync.
- * Segment count: 1 <= S <= 256 (anything else is refused).  One wave per row: up to S = 64 a lane owns one segment (the kernel and
- * the bits of every earlier release), for 64 < S <= 256 a lane owns ceil(S / 64) segments, segment j in lane j & 63 (csrc/loss.h:
- * loss_fwd_bwd_long_kernel; same arguments, same parts layout, same numerical forms). */
+ * Segment count: 1 <= S <= 256 (anything else is refused).  One kernel, one wave per row: a lane owns R = ceil(S / 64) segments,
+ * segment j in lane j & 63 (csrc/loss.h: loss_fwd_bwd_kernel<R>; R = 1, a row of up to 64 segments, gives the bits of every
+ * earlier release). */
 int segmm_label_stats(const int64_t* gt, int B, int S, int rewritten, float* v, float* v2, float* norms,
                       segmm_stream_t stream);
 int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, const float* bias_w,
@@ -512,9 +512,10 @@ int segmm_step_tail(const segmm_phase_t* phase, const segmm_stream_t* streams, i
  * segmm_focal_relabel: focal loss first in the loss list rewrites the labels in place (:534-535): gt > 0 -> 1, gt == -1 -> 0;
  * segmm_rand_uniform / segmm_rand_ids: the noUser ablations' random user features in [0, 1) and random user ids in [lo, hi)
  *   (main_for_seq_leave_earlystop_SegMM.py:275-280), segmm_rand_perm_rows: the noPos ablation's fresh permutation of 0 .. S-1 per
- *   row (encoder.py:428-429; 1 <= S <= 256, written as floats; S <= 64 keeps the bit stream of earlier releases, longer rows draw
- *   from a stream of their own) -- drawn from the counter hash of the dropout streams (seed with bit
- *   63 set: the device-side step words are XORed in): the reference's distributions, not torch's bit streams. */
+ *   row (encoder.py:428-429; 1 <= S <= 256, written as floats; one kernel, a lane ranks the keys of R = ceil(S / 64) indices; rows
+ *   of S <= 64 keep the bit stream of earlier releases, longer rows draw from a stream of their own) -- drawn from the counter
+ *   hash of the dropout streams (seed with bit 63 set: the device-side step words are XORed in): the reference's distributions,
+ *   not torch's bit streams. */
 int segmm_bias_grad(const float* dl, int B, int S, float* g_bias_weight, float* g_bias_bias, segmm_stream_t stream);
 int segmm_focal_relabel(int64_t* gt, int64_t n, segmm_stream_t stream);
 int segmm_rand_uniform(float* out, int64_t n, uint64_t seed, uint32_t site, segmm_stream_t stream);

@@ -1388,6 +1388,15 @@ int segmm_loss_finish(const float* parts, int B, const float* coef, float* losse
     return 0;
 }
 
+// KERNEL<R>, one wave per row of S <= 256 segments (four rows per workgroup), each lane owning R = ceil(S / 64) of them
+#define LAUNCH_ROW_WAVES(KERNEL, ROWS, S, STREAM, ...)                                                                                        \
+    switch (((S) + 63) / 64) {                                                                                                                \
+        case 1: hipLaunchKernelGGL(KERNEL<1>, dim3(((ROWS) + 3) / 4), dim3(256), 0, (hipStream_t)(STREAM), __VA_ARGS__); break;               \
+        case 2: hipLaunchKernelGGL(KERNEL<2>, dim3(((ROWS) + 3) / 4), dim3(256), 0, (hipStream_t)(STREAM), __VA_ARGS__); break;               \
+        case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(((ROWS) + 3) / 4), dim3(256), 0, (hipStream_t)(STREAM), __VA_ARGS__); break;               \
+        default: hipLaunchKernelGGL(KERNEL<4>, dim3(((ROWS) + 3) / 4), dim3(256), 0, (hipStream_t)(STREAM), __VA_ARGS__); break;              \
+    }
+
 int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, const float* bias_w,
                        const float* bias_b, const float* exposure, const float* coef, const int* enabled,
                        int rewritten_ce, int rewritten_kl, int use_mask, const float* norms, const float* v_all,
@@ -1406,12 +1415,7 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
     a.use_mask = use_mask; a.norms = norms;
     a.v_all = v_all; a.v2_all = v2_all; a.Bg = Bg;
     a.logits_out = logits_out; a.dlogits = dlogits; a.parts = parts;
-    // one wave per row: a lane owns one segment up to S = 64 (the kernel every earlier result came from), ceil(S / 64) beyond
-    const dim3 grid((B + 3) / 4), block(256);
-    if (S <= 64) hipLaunchKernelGGL(loss_fwd_bwd_kernel, grid, block, 0, (hipStream_t)stream, a);
-    else if (S <= 128) hipLaunchKernelGGL(loss_fwd_bwd_long_kernel<2>, grid, block, 0, (hipStream_t)stream, a);
-    else if (S <= 192) hipLaunchKernelGGL(loss_fwd_bwd_long_kernel<3>, grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(loss_fwd_bwd_long_kernel<4>, grid, block, 0, (hipStream_t)stream, a);
+    LAUNCH_ROW_WAVES(loss_fwd_bwd_kernel, B, S, stream, a);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1722,12 +1726,8 @@ int segmm_rand_ids(int64_t* out, int64_t n, int64_t lo, int64_t hi, uint64_t see
 int segmm_rand_perm_rows(float* out, int rows, int S, uint64_t seed, uint32_t site, segmm_stream_t stream) {
     SEGMM_REQUIRE(out && rows >= 0 && S >= 1 && S <= 256, "rand_perm_rows: null pointer / S = %d (1 .. 256)", S);
     if (rows == 0) return 0;
-    const dim3 grid((rows + 3) / 4), block(256);
     const DropCfg d = make_drop(0.5f, seed, site);
-    if (S <= 64) hipLaunchKernelGGL(rand_perm_rows_kernel, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
-    else if (S <= 128) hipLaunchKernelGGL(rand_perm_rows_long_kernel<2>, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
-    else if (S <= 192) hipLaunchKernelGGL(rand_perm_rows_long_kernel<3>, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
-    else hipLaunchKernelGGL(rand_perm_rows_long_kernel<4>, grid, block, 0, (hipStream_t)stream, out, rows, S, d);
+    LAUNCH_ROW_WAVES(rand_perm_rows_kernel, rows, S, stream, out, rows, S, d);
     LAUNCH_CHECK();
     return 0;
 }

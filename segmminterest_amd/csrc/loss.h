@@ -13,7 +13,7 @@ enum { L_BPR = 0, L_FOCAL, L_SCE, L_ICE, L_IKL, L_HUBER, L_HAZARD, L_MSE, L_MSE2
 constexpr int L_PSTRIDE = 12;   // row stride of `parts` (padded to a multiple of 4 for the float4 column sum)
 
 struct LossArgs {
-    int B, S;                       // local rows, segments (S <= 64: loss_fwd_bwd_kernel, 64 < S <= 256: loss_fwd_bwd_long_kernel)
+    int B, S;                       // local rows, segments (1 <= S <= 256: loss_fwd_bwd_kernel<R>, R = ceil(S / 64))
     const float* logits;            // [B,S] head output (before the learnable position bias)
     const long long* gt;            // [B,S] in {1,0,-1,-2}
     const float* bias_w;            // [S] or null   learnable_bias (decoder_leave_focal.py:442-444,497-504)
@@ -42,179 +42,15 @@ __device__ __forceinline__ float bce_logits(float x, float t) {
     return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
 }
 
-__global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (row >= a.B) return;
-    const int S = a.S;
-    const bool in = lane < S;
-    const float n_valid_bpr = fmaxf(a.norms[0], 1.f);
-    const float Bg = a.norms[1];
-    const float mask_sum_global = fmaxf(a.norms[2], 1.f);
-    float z = in ? a.logits[(size_t)row * S + lane] : 0.f;
-    if (in && a.bias_w) z += (float)(lane + 1) * a.bias_w[lane] + a.bias_b[lane];
-    const int gt = in ? (int)a.gt[(size_t)row * S + lane] : -2;
-    const bool m = in && gt != -2;
-    const float mf = m ? 1.f : 0.f;
-    const int v = (int)wave_sum((in && gt == 1) ? 1.f : 0.f);       // view length = index of the leave segment
-    const int dur = (int)wave_sum(mf);
-    const float p = sigmoidf_(z);
-    // survival h_t = sum_(k <= t) log p_k, surv = exp(h), hazard = 1 - surv (:511).  Evaluated in forms that keep their relative
-    // accuracy where the literal ones cancel: log p = min(z, 0) - log1p(exp(-|z|)) (logf(p) of a p rounded to 1 keeps only
-    // ulp(1) of a log p ~ -exp(-z)), hazard = -expm1(h), and 1 - p = sigmoid(-z) in the gradient chain below -- a leave right
-    // after segments with p ~ 1 has hazard ~ exp(-z), and d hazard / d logit carries 1 / hazard (tests/test_loss_gpu.py)
-    const float q = sigmoidf_(-z);                       // 1 - p
-    const float logp = in ? fminf(z, 0.f) - log1pf(expf(-fabsf(z))) : 0.f;
-    const float h = wave_scan_incl(logp, lane);
-    const float surv = in ? expf(h) : 0.f;
-    float dz = 0.f;          // d total / d z (this lane's position)
-    float qs = 0.f;          // d total / d surv_j  (survival-based losses share one suffix scan)
-    float part[L_NPART];
-#pragma unroll
-    for (int k = 0; k < L_NPART; ++k) part[k] = 0.f;
-
-    // ---- interestBPR (compute_interest_BPR_all, :163-221)
-    if (a.enabled[L_BPR] && v < S) {
-        const float pos = __shfl(z, v, 64);
-        const bool neg = in && lane != v;
-        const float mx = wave_max(neg ? z : -INFINITY);
-        const float e = neg ? expf(z - mx) : 0.f;
-        const float se = wave_sum(e);
-        const float w = se > 0.f ? e / se : 0.f;         // S = 1: no negative lane -> w = 0, A clamps to 1e-8, zero gradient
-        const float sg = neg ? sigmoidf_(z - pos) : 0.f;
-        const float A = wave_sum(sg * w);
-        const float Ac = fminf(fmaxf(A, 1e-8f), 1.0f - 1e-8f);
-        part[L_BPR] = -logf(Ac) / n_valid_bpr;
-        const float dA = (A >= 1e-8f && A <= 1.0f - 1e-8f) ? -1.0f / (A * n_valid_bpr) : 0.f;
-        const float dpos = -wave_sum(w * sg * (1.f - sg));
-        float gz = neg ? w * (sg * (1.f - sg) + sg - A) : 0.f;
-        if (lane == v) gz = dpos;
-        dz += a.coef[L_BPR] * dA * gz;
-    }
-    // ---- focal (my_sigmoid_focal_loss :35-59, alpha .5, gamma 2, exposure-corrected p; sum/bsz :536-538)
-    if (a.enabled[L_FOCAL]) {
-        float t = (gt > 0) ? 1.f : 0.f;                  // after the in-place rewrite: >0 -> 1, -1 -> 0
-        const float ex = in ? a.exposure[lane] : 1.f;
-        const float ce = bce_logits(z, t);
-        const float pe = p * ex;
-        const float pt = pe * t + (1.f - pe) * (1.f - t);
-        const float om = 1.f - pt;
-        const float fl = m ? 0.5f * ce * om * om : 0.f;
-        part[L_FOCAL] = wave_sum(fl) / Bg;
-        if (m) {
-            const float dpt = (2.f * t - 1.f) * ex * p * (1.f - p);
-            dz += a.coef[L_FOCAL] * 0.5f * ((p - t) * om * om - 2.f * ce * om * dpt) / Bg;
-        }
-    }
-    // ---- surviveCE (compute_leave_prob_CE :68-97): BCE-with-logits on exp(h_t), masked mean
-    if (a.enabled[L_SCE]) {
-        const float y = (gt == 1) ? 1.f : 0.f;
-        const float ce = m ? bce_logits(surv, y) : 0.f;
-        part[L_SCE] = wave_sum(ce) / mask_sum_global;
-        if (m) qs += a.coef[L_SCE] * (sigmoidf_(surv) - y) / mask_sum_global;
-    }
-    // ---- interestCE / interestKL (compute_interest_leave_CE :99-161)
-    if (a.enabled[L_ICE] || a.enabled[L_IKL]) {
-        const float mz = wave_max(in ? z : -INFINITY);
-        const float ez = in ? expf(z - mz) : 0.f;
-        const float sz = wave_sum(ez);
-        const float ni = ez / sz;
-        const float logni = z - mz - logf(sz);
-#pragma unroll
-        for (int which = 0; which < 2; ++which) {
-            const int L = which == 0 ? L_ICE : L_IKL;
-            if (!a.enabled[L]) continue;
-            const int rew = which == 0 ? a.gt_rewritten_for_ce : a.gt_rewritten_for_kl;
-            // gt_nonleave = (gt != 0) on the (possibly rewritten) labels
-            const bool nz = in && (rew ? (gt == 1 || gt == -2) : (gt != 0));
-            const float n1 = wave_sum(nz ? 1.f : 0.f);
-            // softmax of a 0/1 vector the way torch does it (subtract the max)
-            const float gmax = n1 > 0.f ? 1.f : 0.f;
-            const float eg = in ? expf((nz ? 1.f : 0.f) - gmax) : 0.f;
-            const float ng = eg / wave_sum(eg);
-            float c, val;
-            if (a.use_mask) {
-                c = m ? ng / (float)dur : 0.f;
-                val = (which == 0) ? -c * logni : (m ? c * (logf(ng) - logni) : 0.f);
-            } else {
-                c = in ? ng : 0.f;
-                val = (which == 0) ? (in ? -ng * logni : 0.f) : (in ? ng * (logf(ng) - logni) : 0.f);
-            }
-            part[L] = wave_sum(val) / Bg;
-            const float csum = wave_sum(c);
-            if (in) dz += a.coef[L] * (ni * csum - c) / Bg;
-        }
-    }
-    // ---- huber (huber_loss :61-66 on [B] vs [B,1] => [B,B] broadcast, :540) and mse / mse2 (:552-558)
-    const float hz = m ? -expm1f(h) : 0.f;
-    const float ssum_h = wave_sum(hz);                   // sum of masked hazard
-    const float ssum = wave_sum(m ? surv : 0.f);         // sum of masked survival
-    {
-        const int dlast = dur > 0 ? dur - 1 : S - 1;
-        const float ssum2 = wave_sum(in ? (lane == dlast ? 1.f : (m ? surv : 0.f)) : 0.f);
-        float hub = 0.f, dhub = 0.f, e1 = 0.f, e2 = 0.f;
-        for (int i = lane; i < a.Bg; i += 64) {
-            const float vi = a.v_all[i];
-            if (a.enabled[L_HUBER]) {
-                const float err = ssum_h - vi, ae = fabsf(err);
-                hub += ae < 1.f ? 0.5f * err * err : ae - 0.5f;
-                dhub += ae < 1.f ? err : (err > 0.f ? 1.f : -1.f);
-            }
-            const float d1 = ssum - vi, d2 = ssum2 - a.v2_all[i];
-            e1 += d1 * d1;
-            e2 += d2 * d2;
-        }
-        const float inv = 1.0f / (Bg * Bg);
-        part[L_MSE] = wave_sum(e1) * inv;
-        part[L_MSE2] = wave_sum(e2) * inv;
-        if (a.enabled[L_HUBER]) {
-            part[L_HUBER] = wave_sum(hub) * inv;
-            const float dLds = wave_sum(dhub) * inv;     // d/d(sum of masked hazard)
-            if (m) qs += a.coef[L_HUBER] * (-dLds);
-        }
-    }
-    // ---- hazard (compute_partial_likelihood_loss :273-286)
-    if (a.enabled[L_HAZARD] && v < S) {
-        const float ht = __shfl(hz, v, 64) + 1e-6f;
-        const float R = wave_sum((in && lane >= v) ? hz : 0.f) + 1e-6f;
-        part[L_HAZARD] = -(logf(ht) - logf(R)) / Bg;
-        if (m) {
-            float dh = 0.f;                               // d L / d hz_j
-            if (lane == v) dh -= 1.f / ht;
-            if (lane >= v) dh += 1.f / R;
-            qs += a.coef[L_HAZARD] * (dh / Bg) * (-1.f);  // hz = 1 - surv
-        }
-    }
-    // ---- survival chain: d surv_j / d z_k = surv_j (1 - p_k) for k <= j  => suffix sum over j >= k.  Summed as a suffix scan: the
-    // row total minus a prefix scan cancels wherever the survival has dropped to ~0 (saturated logits), leaving an error of
-    // ulp(total) on gradients many orders of magnitude smaller (tests/test_loss_gpu.py).  The terms are carried times 2^64: a
-    // survival below fp32's normal range (h < -87) would otherwise enter as a subnormal of a few bits and be multiplied up by
-    // qs (a power-of-two scaling: exact wherever nothing underflows or overflows; |qs| <= 1e6 / batch keeps qs 2^64 finite).
-    {
-        const float sv = h < -80.f ? expf(h + 44.3614196f) : surv * 18446744073709551616.f;     // surv * 2^64 (64 ln 2 = 44.36)
-        const float u = in ? qs * sv : 0.f;
-        const float suf = wave_suffix_incl(u, lane);
-        if (in) dz += (q * suf) * 5.42101086242752217e-20f;                                      // * 2^-64
-    }
-    if (in) {
-        a.logits_out[(size_t)row * S + lane] = z;
-        if (a.dlogits) a.dlogits[(size_t)row * S + lane] = dz;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < L_PSTRIDE; ++k) a.parts[(size_t)row * L_PSTRIDE + k] = k < L_NPART ? part[k] : 0.f;
-    }
-}
-
-// ---------------------------------------------------------------- rows of 64 < S <= 256 segments
-// The same losses, the same LossArgs / parts layout and the same numerical forms as loss_fwd_bwd_kernel (log p, -expm1(h),
-// sigmoid(-z), the 2^64-scaled suffix scan, BPR's clamp), still one wave per interaction row, each lane owning R = ceil(S / 64)
-// segments.  STRIPED layout: segment j sits in lane j & 63, slot j >> 6.  Chosen over the blocked one (R consecutive segments
-// per lane) because every load and store of a slot is then one contiguous 256-byte line per wave, S needs no division by R, and a
-// slot is exactly the 64-lane row of the short kernel: each scan is that kernel's wave scan of the slot plus the carry (the
-// totals) of the slots before it (after it, for the suffix scan), and the value at the leave index v is one shuffle from lane
-// v & 63 of slot v >> 6.  The per-lane values live in arrays of the compile-time length R that are indexed only by fully
-// unrolled loops, so they are registers, never scratch.  Reductions add a lane's R slots in slot order, then the wave.
+// ---------------------------------------------------------------- loss_fwd_bwd_kernel<R>: rows of 1 <= S <= 256 segments
+// One wave per interaction row, each lane owning R = ceil(S / 64) segments; one kernel for every S (R = 1 is a row of up to 64
+// segments, one per lane).  STRIPED layout: segment j sits in lane j & 63, slot j >> 6.  Chosen over the blocked one (R
+// consecutive segments per lane) because every load and store of a slot is then one contiguous 256-byte line per wave, S needs
+// no division by R, and a slot is a plain 64-lane row: each scan is the wave scan of the slot plus the carry (the totals) of the
+// slots before it (after it, for the suffix scan; with R = 1 the carry is a literal zero), and the value at the leave index v is
+// one shuffle from lane v & 63 of slot v >> 6.  The per-lane values live in arrays of the compile-time length R that are indexed
+// only by fully unrolled loops, so they are registers, never scratch.  Reductions add a lane's R slots in slot order, then the
+// wave.
 template <int R>
 __device__ __forceinline__ float wave_sum_r(const float (&x)[R]) {
     float t = x[0];
@@ -242,7 +78,7 @@ __device__ __forceinline__ float seg_pick_r(const float (&x)[R], int v) {
 }
 
 template <int R>
-__global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a) {
+__global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const LossArgs a) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= a.B) return;
@@ -252,7 +88,8 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
     const float mask_sum_global = fmaxf(a.norms[2], 1.f);
     bool in[R], m[R];
     int gt[R];
-    float z[R], p[R], q[R], h[R], surv[R], dz[R], qs[R], hz[R], t0[R], t1[R];
+    float z[R], p[R], q[R], h[R], surv[R], hz[R], t0[R], t1[R];
+    float dz[R], qs[R];      // d total / d z of a lane's segments; d total / d surv_j (survival-based losses share one suffix scan)
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int j = r * 64 + lane;
@@ -268,7 +105,11 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
     }
     const int v = (int)wave_sum_r<R>(t0);                // view length = index of the leave segment (counts <= 256: exact)
     const int dur = (int)wave_sum_r<R>(t1);
-    // survival h_t = sum_(k <= t) log p_k: the wave scan of a slot plus the total of the slots before it
+    // survival h_t = sum_(k <= t) log p_k (the wave scan of a slot plus the total of the slots before it), surv = exp(h), hazard =
+    // 1 - surv (:511).  Evaluated in forms that keep their relative accuracy where the literal ones cancel: log p = min(z, 0) -
+    // log1p(exp(-|z|)) (logf(p) of a p rounded to 1 keeps only ulp(1) of a log p ~ -exp(-z)), hazard = -expm1(h), and 1 - p =
+    // sigmoid(-z) in the gradient chain below -- a leave right after segments with p ~ 1 has hazard ~ exp(-z), and d hazard /
+    // d logit carries 1 / hazard (tests/test_loss_gpu.py)
     {
         float carry = 0.f;
 #pragma unroll
@@ -287,7 +128,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
 #pragma unroll
     for (int k = 0; k < L_NPART; ++k) part[k] = 0.f;
 
-    // ---- interestBPR
+    // ---- interestBPR (compute_interest_BPR_all, :163-221)
     if (a.enabled[L_BPR] && v < S) {
         const float pos = seg_pick_r<R>(z, v);
         float w[R], sg[R];
@@ -300,7 +141,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const bool neg = in[r] && r * 64 + lane != v;
-            w[r] = se > 0.f ? w[r] / se : 0.f;
+            w[r] = se > 0.f ? w[r] / se : 0.f;           // S = 1: no negative lane -> w = 0, A clamps to 1e-8, zero gradient
             sg[r] = neg ? sigmoidf_(z[r] - pos) : 0.f;
             t0[r] = sg[r] * w[r];
             t1[r] = w[r] * sg[r] * (1.f - sg[r]);
@@ -318,11 +159,11 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
             dz[r] += a.coef[L_BPR] * dA * gz;
         }
     }
-    // ---- focal
+    // ---- focal (my_sigmoid_focal_loss :35-59, alpha .5, gamma 2, exposure-corrected p; sum/bsz :536-538)
     if (a.enabled[L_FOCAL]) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const float t = (gt[r] > 0) ? 1.f : 0.f;
+            const float t = (gt[r] > 0) ? 1.f : 0.f;     // after the in-place rewrite: >0 -> 1, -1 -> 0
             const float ex = in[r] ? a.exposure[r * 64 + lane] : 1.f;
             const float ce = bce_logits(z[r], t);
             const float pe = p[r] * ex;
@@ -336,7 +177,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
         }
         part[L_FOCAL] = wave_sum_r<R>(t0) / Bg;
     }
-    // ---- surviveCE
+    // ---- surviveCE (compute_leave_prob_CE :68-97): BCE-with-logits on exp(h_t), masked mean
     if (a.enabled[L_SCE]) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -346,7 +187,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
         }
         part[L_SCE] = wave_sum_r<R>(t0) / mask_sum_global;
     }
-    // ---- interestCE / interestKL
+    // ---- interestCE / interestKL (compute_interest_leave_CE :99-161)
     if (a.enabled[L_ICE] || a.enabled[L_IKL]) {
         float ni[R], logni[R];
 #pragma unroll
@@ -366,7 +207,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
             const int L = which == 0 ? L_ICE : L_IKL;
             if (!a.enabled[L]) continue;
             const int rew = which == 0 ? a.gt_rewritten_for_ce : a.gt_rewritten_for_kl;
-            bool nz[R];
+            bool nz[R];                                  // gt_nonleave = (gt != 0) on the (possibly rewritten) labels
             float ng[R], c[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -374,7 +215,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
                 t0[r] = nz[r] ? 1.f : 0.f;
             }
             const float n1 = wave_sum_r<R>(t0);
-            const float gmax = n1 > 0.f ? 1.f : 0.f;
+            const float gmax = n1 > 0.f ? 1.f : 0.f;     // softmax of a 0/1 vector the way torch does it (subtract the max)
 #pragma unroll
             for (int r = 0; r < R; ++r) ng[r] = in[r] ? expf((nz[r] ? 1.f : 0.f) - gmax) : 0.f;
             const float sg = wave_sum_r<R>(ng);
@@ -396,7 +237,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
                 if (in[r]) dz[r] += a.coef[L] * (ni[r] * csum - c[r]) / Bg;
         }
     }
-    // ---- huber and mse / mse2
+    // ---- huber (huber_loss :61-66 on [B] vs [B,1] => [B,B] broadcast, :540) and mse / mse2 (:552-558)
     const float ssum_h = wave_sum_r<R>(hz);              // sum of masked hazard
     {
         const int dlast = dur > 0 ? dur - 1 : S - 1;
@@ -430,7 +271,7 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
                 if (m[r]) qs[r] += a.coef[L_HUBER] * (-dLds);
         }
     }
-    // ---- hazard
+    // ---- hazard (compute_partial_likelihood_loss :273-286)
     if (a.enabled[L_HAZARD] && v < S) {
         const float ht = seg_pick_r<R>(hz, v) + 1e-6f;
 #pragma unroll
@@ -440,25 +281,29 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_long_kernel(const LossArgs a
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             if (m[r]) {
-                float dh = 0.f;
+                float dh = 0.f;                          // d L / d hz_j
                 if (r * 64 + lane == v) dh -= 1.f / ht;
                 if (r * 64 + lane >= v) dh += 1.f / Rk;
-                qs[r] += a.coef[L_HAZARD] * (dh / Bg) * (-1.f);
+                qs[r] += a.coef[L_HAZARD] * (dh / Bg) * (-1.f);      // hz = 1 - surv
             }
         }
     }
-    // ---- survival chain: suffix scan of qs_j surv_j 2^64 (see loss_fwd_bwd_kernel), last slot first: the wave's suffix scan of a
-    // slot plus the total of the slots after it
+    // ---- survival chain: d surv_j / d z_k = surv_j (1 - p_k) for k <= j  => suffix sum over j >= k.  Summed as a suffix scan: the
+    // row total minus a prefix scan cancels wherever the survival has dropped to ~0 (saturated logits), leaving an error of
+    // ulp(total) on gradients many orders of magnitude smaller (tests/test_loss_gpu.py).  The terms are carried times 2^64: a
+    // survival below fp32's normal range (h < -87) would otherwise enter as a subnormal of a few bits and be multiplied up by
+    // qs (a power-of-two scaling: exact wherever nothing underflows or overflows; |qs| <= 1e6 / batch keeps qs 2^64 finite).
+    // Last slot first: the wave's suffix scan of a slot plus the total of the slots after it.
     {
         float carry = 0.f;
 #pragma unroll
         for (int r = R - 1; r >= 0; --r) {
-            const float sv = h[r] < -80.f ? expf(h[r] + 44.3614196f) : surv[r] * 18446744073709551616.f;
+            const float sv = h[r] < -80.f ? expf(h[r] + 44.3614196f) : surv[r] * 18446744073709551616.f;     // surv * 2^64 (64 ln 2 = 44.36)
             const float u = in[r] ? qs[r] * sv : 0.f;
             const float sc = wave_suffix_incl(u, lane);
             const float suf = sc + carry;
             carry += __shfl(sc, 0, 64);
-            if (in[r]) dz[r] += (q[r] * suf) * 5.42101086242752217e-20f;
+            if (in[r]) dz[r] += (q[r] * suf) * 5.42101086242752217e-20f;                                       // * 2^-64
         }
     }
 #pragma unroll
@@ -615,36 +460,23 @@ __global__ void rand_ids_kernel(long long* __restrict__ out, long long n, long l
         if (2 * q + 1 < n) out[2 * q + 1] = lo + (long long)(((unsigned long long)r.y * span) >> 32);
     }
 }
-// noPos (encoder.py:428-429: a fresh torch.randperm(S) per row): one wave per row, lane i < S draws a 32-bit key; its position in
-// the permutation is the number of lanes with a smaller (key, index) -- a uniformly random permutation
-__global__ void rand_perm_rows_kernel(float* __restrict__ out, int rows, int S, DropCfg d0) {
-    const DropCfg d = drop_live(d0);
-    const int lane = threadIdx.x & 63, row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const uint2 r = drop_rand_quad(d, (uint64_t)row * 64u + (uint64_t)lane);
-    const uint32_t key = lane < S ? r.x : 0xffffffffu;
-    int rank = 0;
-    for (int j = 0; j < S; ++j) {
-        const uint32_t kj = (uint32_t)__shfl((int)key, j, 64);
-        rank += (kj < key || (kj == key && j < lane)) ? 1 : 0;
-    }
-    if (lane < S) out[(size_t)row * S + rank] = (float)lane;          // out[row, :] is a permutation of 0 .. S-1 (as floats: frame positions)
-}
-// 64 < S <= 256: the same rank-of-a-key rule with the striped ownership of loss_fwd_bwd_long_kernel -- lane l draws the keys of
-// the indices l, l + 64, ... (R = ceil(S / 64) of them; a stream of its own, counter row * 256 + index) and counts, for each,
-// the (key, index) pairs of the row below it.  The row's keys go through LDS (1 KB per wave): every lane reads key j at the same
-// address, a broadcast read -- 256 cross-lane reads with compile-time lanes put the whole row into scalar registers and
-// spilled them.  Only indices < S are counted, so every rank is < S.
+// noPos (encoder.py:428-429: a fresh torch.randperm(S) per row): one wave per row, striped as in loss_fwd_bwd_kernel -- lane l
+// draws the 32-bit keys of the indices l, l + 64, ... (R = ceil(S / 64) of them) and counts, for each, the (key, index) pairs of
+// the row below it: the index's position in the permutation, a uniformly random one.  The row's keys go through LDS (256 R bytes
+// per wave): every lane reads key j at the same address, a broadcast read -- 256 cross-lane reads with compile-time lanes put
+// the whole row into scalar registers and spilled them.  Only indices < S are counted, so every rank is < S.
 template <int R>
-__global__ __launch_bounds__(256) void rand_perm_rows_long_kernel(float* __restrict__ out, int rows, int S, DropCfg d0) {
-    __shared__ uint32_t keys[4][256];
+__global__ __launch_bounds__(256) void rand_perm_rows_kernel(float* __restrict__ out, int rows, int S, DropCfg d0) {
+    __shared__ uint32_t keys[4][64 * R];
+    // counter stride of a row: 64 for S <= 64 (R = 1), 256 beyond -- rows of up to 64 keep the stream recorded noPos steps drew from
+    constexpr uint64_t kStride = R == 1 ? 64u : 256u;
     const DropCfg d = drop_live(d0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, row = blockIdx.x * 4 + w;
     uint32_t key[R];
     int rank[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const uint2 x = drop_rand_quad(d, (uint64_t)row * 256u + (uint64_t)(r * 64 + lane));
+        const uint2 x = drop_rand_quad(d, (uint64_t)row * kStride + (uint64_t)(r * 64 + lane));
         key[r] = x.x;
         rank[r] = 0;
         keys[w][r * 64 + lane] = x.x;
@@ -659,7 +491,7 @@ __global__ __launch_bounds__(256) void rand_perm_rows_long_kernel(float* __restr
     }
 #pragma unroll
     for (int r = 0; r < R; ++r)
-        if (r * 64 + lane < S) out[(size_t)row * S + rank[r]] = (float)(r * 64 + lane);
+        if (r * 64 + lane < S) out[(size_t)row * S + rank[r]] = (float)(r * 64 + lane);      // row: a permutation of 0 .. S-1 (floats)
 }
 
 }  // namespace segmm

@@ -1,6 +1,6 @@
-"""Videos of more than 64 segments on the MI355X: the long-row loss kernel (csrc/loss.h: loss_fwd_bwd_long_kernel, 64 < S <= 256) under
-the float64 rule of helpers.loss_check -- the rule, tau and the checks of test_loss_gpu.run_case unchanged --, the device
-permutation draws up to S = 256, the attention kernels at key blocks of up to 176 + 16 tokens, whole models, the trainer and the
+"""Videos of more than 64 segments on the MI355X: the loss kernel (csrc/loss.h: loss_fwd_bwd_kernel<R>, R = ceil(S / 64) segments per
+lane, here R = 2, 3, 4) under the float64 rule of helpers.loss_check -- the rule, tau and the checks of test_loss_gpu.run_case
+unchanged --, the device permutation draws up to S = 256, the attention kernels at key blocks of up to 176 + 16 tokens, whole models, the trainer and the
 evaluation kernels at S in (64, 176].  The yardstick at these sizes is the CPU oracle (oracle/segmm_oracle.py) in float64, which
 the golden fixtures pin to the reference at S = 20 and 40.  Run with ``pytest -m gpu``.
 
@@ -194,9 +194,9 @@ def test_device_permutations_refuse_257():
 
 
 def test_device_permutations_keep_their_stream_up_to_64():
-    """S <= 64 stays on the one-segment-per-lane kernel: rank of lane i's key r.x of counter row * 64 + i (recorded noPos steps
-    depend on the stream).  Restated on the host for one row through the same kernel's own output at another S: the first 40
-    keys of a row are the same at S = 40 and S = 64, so the relative order of 0 .. 39 agrees."""
+    """S <= 64 (rand_perm_rows_kernel<1>, one index per lane) keeps its stream: rank of index i's key r.x of counter row * 64 + i
+    (recorded noPos steps depend on the stream).  Restated on the host for one row through the same kernel's own output at
+    another S: the first 40 keys of a row are the same at S = 40 and S = 64, so the relative order of 0 .. 39 agrees."""
     H = _abi()
     a, b = torch.empty(8, 40, device=DEV), torch.empty(8, 64, device=DEV)
     H.rand_perm_rows(a, 8, 40, 99, 3)

@@ -1,5 +1,5 @@
-"""K8, the leave/skip losses (csrc/loss.h: label_stats -> loss_fwd_bwd -> loss_finish), through the C ABI against the float64
-oracle (oracle/segmm_oracle.compute_loss with autograd) under the rule of helpers.loss_check: every loss slot, the total and
+"""K8, the leave/skip losses (csrc/loss.h: label_stats -> loss_fwd_bwd_kernel<R>, here R = 1: S <= 64 -> loss_finish), through the
+C ABI against the float64 oracle (oracle/segmm_oracle.compute_loss with autograd) under the rule of helpers.loss_check: every loss slot, the total and
 d total / d logits, at every in-domain label row, at sizes where the kernels' loops take more than one trip, and at logit
 magnitudes a trained model reaches.  Label statistics, the unpack of the data-parallel record and loss_finish's gmax / delayed
 scales are compared exactly.  Run with ``pytest -m gpu``.
