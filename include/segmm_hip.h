@@ -121,7 +121,10 @@ int segmm_split_p32(const float* x, int64_t rows, int cols, int ld, uint16_t* pl
  * desc: device array of n_mats records {int64 flat offset (floats); int32 R, C, needs_transpose, first_tile, tile_cols}
  * (32 x 32 tiles, n_tiles in total, matrices in ascending first_tile order); hdr: [n_mats][SEGMM_SITE_HDR +
  * SEGMM_AMAX_SLOTS] zeroed site headers (receive maxima and scale); W planes at wpl + 2 * offset (ld2 = 2 C), W^T planes
- * at wTpl + 2 * offset (ld2 = 2 R).  C % 32 == 0 (and R % 32 == 0 for transposed matrices). */
+ * at wTpl + 2 * offset (ld2 = 2 R).  C % 32 == 0 (and R % 32 == 0 for transposed matrices).  Every record's offset is a
+ * multiple of 4 floats (the absmax pass reads 16 bytes at a time; the plane blocks of a matrix then start 16-byte aligned
+ * too).  wTpl may be NULL only if no record asks for a transpose.  The headers need no zero-fill between calls: every call
+ * rewrites all SEGMM_AMAX_SLOTS maxima, the scale and the flag of every matrix. */
 int segmm_wsplit_p32(const float* flat, const void* desc, int n_mats, int n_tiles, float* hdr, uint16_t* wpl, uint16_t* wTpl,
                      segmm_stream_t stream);
 /* P32 planes of the transpose of x[R, C]: plane row c holds x[:, c] (R % 32 == 0), scale hdr[0]. */

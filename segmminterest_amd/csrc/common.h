@@ -229,7 +229,9 @@ __device__ __forceinline__ bool site_planes_ok(const float* hdr, float s, int la
 // (x0, x1) * s -> packed fp16 (hi0, hi1), (lo0, lo1); hi + lo = x s up to 2^-22 |x s|.
 // Four VALU instructions per pair: v_fma_mix{lo,hi}_f16 multiply in fp32, round ONCE to fp16 and write one half
 // of the destination, and take the fp16 hi term straight back as the addend of the lo term
-// (lo = rn16(x s - hi), the fma is exact before that rounding).
+// (lo = rn16(x s - hi), the fma is exact before that rounding).  fp16 subnormal lo terms are kept.  The hi term is x s + 0:
+// x = -0 is stored as hi = +0, lo = -0 (tests/p32_ref.py states the format on the host; the cast-and-fmaf form of
+// gemm_planes.h's weight split compiles to the same two instructions).
 __device__ __forceinline__ void splith_pair(float x0, float x1, float s, uint32_t& ph, uint32_t& pl) {
     uint32_t h, l;
     asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(x0), "v"(s));

@@ -567,17 +567,21 @@ __global__ __launch_bounds__(256) void split_p32_kernel(const float* __restrict_
     const int c4n = cols >> 2;
     const long long n4 = rows * c4n;
     float am = 0.f;
+    bool nan = false;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const long long r = i / c4n;
         const int c = (int)(i - r * c4n) << 2;
         const f32x4 v = *(const f32x4*)(x + r * ld + c);
         plane_store4_pair(planes, ld2, r, c, v, s);      // i even <-> c % 8 == 0: lane pairs share a row (cols % 8 == 0)
         am = absmax4(am, v);
+        nan |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
     }
     if (mode == 0) {
         if (blockIdx.x == 0 && threadIdx.x == 0) { hdr[0] = s; hdr[1] = 0.f; }
     } else {
         site_commit(hdr, am, blockIdx.x * 4 + (threadIdx.x >> 6), s);
+        // fmaxf drops a NaN operand, so the maxima never show one: its planes hold NaN terms, the flag says so
+        if (nan && s > 0.f) ((volatile unsigned int*)hdr)[1] = 1u;
     }
 }
 // planes of the TRANSPOSE: out row c (of Cc), column r (of R) = x[r * ld + c]; P32 over the R axis (R % 32 == 0)
@@ -598,7 +602,7 @@ __global__ __launch_bounds__(256) void split_p32_transpose_kernel(const float* _
         const int c = c0 + ty + 8 * k, r = r0 + tx;
         if (c < Cc && r < R) {
             const float v = tile[tx][ty + 8 * k];
-            const _Float16 h = (_Float16)(v * s);
+            const _Float16 h = (_Float16)__builtin_fmaf(v, s, 0.f);      // x s + 0, as splith_pair forms it: a zero is stored as hi = +0 whatever its sign
             const _Float16 l = (_Float16)__builtin_fmaf(v, s, -(float)h);
             _Float16* o = planes + (size_t)c * ld2 + ((r >> 5) << 6) + (r & 31);
             o[0] = h; o[32] = l;
@@ -644,7 +648,7 @@ __global__ __launch_bounds__(256) void wsplit_kernel(const float* __restrict__ f
         const float v = (r < m.R && c < m.Cc) ? x[(size_t)r * m.Cc + c] : 0.f;
         tile[ty + 8 * k][tx] = v;
         if (r < m.R && c < m.Cc) {
-            const _Float16 hi = (_Float16)(v * s);
+            const _Float16 hi = (_Float16)__builtin_fmaf(v, s, 0.f);      // (x s + 0: see split_p32_transpose_kernel)
             const _Float16 lo = (_Float16)__builtin_fmaf(v, s, -(float)hi);
             _Float16* o = wpl + 2 * m.off + (size_t)r * (2 * m.Cc) + ((c >> 5) << 6) + (c & 31);
             o[0] = hi; o[32] = lo;
@@ -657,7 +661,7 @@ __global__ __launch_bounds__(256) void wsplit_kernel(const float* __restrict__ f
         const int c = c0 + ty + 8 * k, r = r0 + tx;          // plane row c of the transpose, column r
         if (c < m.Cc && r < m.R) {
             const float v = tile[tx][ty + 8 * k];
-            const _Float16 hi = (_Float16)(v * s);
+            const _Float16 hi = (_Float16)__builtin_fmaf(v, s, 0.f);      // (x s + 0: see split_p32_transpose_kernel)
             const _Float16 lo = (_Float16)__builtin_fmaf(v, s, -(float)hi);
             _Float16* o = wTpl + 2 * m.off + (size_t)c * (2 * m.R) + ((r >> 5) << 6) + (r & 31);
             o[0] = hi; o[32] = lo;

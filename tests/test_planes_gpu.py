@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from helpers import MODEL_CASES, build_model, call_model, load_case      # noqa: E402
+import p32_ref as P32      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -37,6 +38,12 @@ def _ref_planes(H, x, rows, cols, scale):
     hdr[0] = scale
     pl = torch.empty((rows, 2 * cols), dtype=torch.float16, device=x.device)
     H.split_p32(x, rows, cols, cols, pl, 2 * cols, hdr, mode=1)
+    # ... and is itself held to the host statement of the format (tests/p32_ref.py) before anything is compared with it
+    xh = x.detach().cpu().numpy().reshape(rows, cols)
+    want, _ = P32.pack(xh, scale)
+    got = pl.cpu().view(torch.int16).numpy().view(want.dtype).reshape(-1)
+    assert (got == want).all(), "split_p32 departs from the host split in %d halves" % int((got != want).sum())
+    assert bool(hdr[1].cpu().view(torch.int32).item() != 0) is P32.overflow_flag(xh, scale)
     return pl, hdr
 
 
