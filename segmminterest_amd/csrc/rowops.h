@@ -599,12 +599,17 @@ __global__ __launch_bounds__(256) void pe_grad_kernel(const float* __restrict__ 
 
 // One AdamW update of four elements.  Floating-point contraction is OFF: adamw_kernel and the two table kernels below must give
 // bit-identical results for the same element whatever the surrounding code lets the compiler fuse.
+// The moments are updated in torch's operation order, which decides what a non-finite or huge gradient leaves behind
+// (tests/test_adamw_gpu.py): m as exp_avg.lerp_(g, 1 - b1) = m + (g - m) (1 - b1) -- an infinite gradient makes m NaN on the next
+// step, as in torch; m b1 + g (1 - b1) would keep it at inf -- and v as exp_avg_sq.mul_(b2).addcmul_(g, g, value = 1 - b2) =
+// v b2 + ((1 - b2) g) g: g g alone overflows from |g| = 1.8e19 on, where (1 - b2) g^2 still fits fp32; v would become inf and the
+// element would never move again (sqrt(v) = inf in every later denominator).
 __device__ __forceinline__ void adamw_elem4(f32x4& pp, const f32x4 gg, f32x4& mm, f32x4& vv, float lr, float b1, float b2, float eps, float wd,
                                             float step, float bc2_sqrt) {
 #pragma clang fp contract(off)
     pp *= (1.0f - lr * wd);
-    mm = mm * b1 + gg * (1.0f - b1);
-    vv = vv * b2 + gg * gg * (1.0f - b2);
+    mm = mm + (gg - mm) * (1.0f - b1);
+    vv = vv * b2 + gg * (1.0f - b2) * gg;
     f32x4 den;
     den.x = sqrtf(vv.x) / bc2_sqrt + eps; den.y = sqrtf(vv.y) / bc2_sqrt + eps;
     den.z = sqrtf(vv.z) / bc2_sqrt + eps; den.w = sqrtf(vv.w) / bc2_sqrt + eps;
