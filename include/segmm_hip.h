@@ -418,6 +418,48 @@ int segmm_row_metrics_accumulate(const int32_t* irec, const float* frec, int B, 
  * table[idx[r], :] (/ (sum|.| + 1e-6) if normalize), mask[r] = 1, for idx[r] in [0, n_lines); zeros / 0 otherwise. */
 int segmm_gather_l1(const float* table, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize, float* out,
                     uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in, segmm_stream_t stream);
+/* (f)-1, the step before the gather: index batches assembled on the device from a COMPILED interaction table
+ * (FrameDatasetSeq_SegMM._getitem, dataloader_SegMM.py:295-357, as an integer function of data resolved once on the host;
+ * segmminterest_amd/feature_store.py: InteractionTable.compile builds the table, DeviceBatches drives this entry point).
+ * The descriptor is a HOST struct of DEVICE pointers, read when the call is made:
+ *   items   item_ptr [n_items + 1], item_line [item_ptr[n_items]]: line of frame f of item i at item_line[item_ptr[i] + f], -1 = the
+ *           key "item-f" is not in the line map (a hole);
+ *   users   own_ptr [n_users + 1], own_line [...]: the user's own frames as lines, unresolvable ones already dropped (no -1);
+ *   rows    row_info [n_rows, 4] = {item of the video, number of video frames n, user, 0}; row_cols [n_rows, 7] = photo_id,
+ *           photo_identity_id, user_id, user_identity_id, time_ms, play_time, duration; hist_ptr [n_rows + 1] and hist_pair [..., 2] =
+ *           the history as (item, watched frames nf) pairs; label [n_rows, label_S] padded with -2 or cut to label_S;
+ *   max_cand  the largest candidate count (video frames or user candidates) of any row; selects the kernel instance.
+ * Per batch slot b with r = row_ids[b]:
+ *   video   candidates = the lines of frames 0 .. n-1 of the row's item (n is cut to the item's length).  n <= S: photo_idx[b, :n] =
+ *           them in order, the rest -1.  n > S: S of them, drawn as below.
+ *   user    candidates = for each history pair in order the lines of frames 0 .. min(nf, item length) - 1 of its item, holes
+ *           skipped, then the user's own lines; m of them.  m <= Lt: user_idx[b, :m] = them in order, the rest -1 (m = 0: all
+ *           -1).  m > Lt: Lt of them, drawn as below.
+ *   label[b, :] = the row's label, cols[k, b] = row_cols[r, k] (cols is [7, B]: every column a contiguous tensor).
+ *   r outside [0, n_rows), or a row with more candidates than SEGMM_ASSEMBLE_MAX_CAND (InteractionTable.compile refuses such
+ *   a table): an all-padding slot -- indices -1, label -2, columns 0 (segmm_gather_l1's convention for bad indices).
+ * The draw (count candidates, cap = S or Lt, count > cap): candidate j -- its position in the hole-free candidate list -- gets the
+ *   32-bit key  SECOND word of the dropout counter hash at counter q = (r << 13) | (stream << 12) | j,  stream = 0 for the video
+ *   and 1 for the user list:  k = seed_lo ^ (site * 0x9E3779B9) ^ ((q >> 32) * 0x85EBCA6B), a = mix32((q & 0xFFFFFFFF) ^ k),
+ *   key = mix32(a ^ seed_hi ^ 0x68E31DA4);  seed_lo = bits 0..31 and seed_hi = bits 32..62 of `seed`, all arithmetic mod 2^32,
+ *   mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   Chosen are the cap smallest (key, j) pairs; a chosen candidate is written at its rank among them.  That is a uniformly random
+ *   cap-subset in uniformly random order (np.random.choice(n, S, replace=False) / random.sample: the reference's distributions,
+ *   not its bit streams), a function of (seed, site, r) only -- not of the batch, the slot or the rank that assembles the row.
+ *   Lists that fit (count <= cap) never touch the hash.  The device step state is never read: a seed with bit 63 set is refused.
+ * Limits: 1 <= S <= 256, S == label_S, 1 <= Lt <= SEGMM_ASSEMBLE_MAX_CAND, max_cand <= SEGMM_ASSEMBLE_MAX_CAND = 4096 (the
+ *   row's keys and lines sit in LDS: 8 bytes per candidate and wave), n_rows <= 2^50 (q has 64 bits), lines < 2^31.
+ * One wave per row; instances of 1024 candidates (4 rows per workgroup, 32 KB LDS) and 4096 (2 rows, 64 KB), by max_cand. */
+#define SEGMM_ASSEMBLE_MAX_CAND 4096
+typedef struct {
+    const int64_t *item_ptr; const int32_t *item_line;
+    const int64_t *own_ptr; const int32_t *own_line;
+    const int64_t *hist_ptr; const int32_t *hist_pair;
+    const int32_t *row_info; const int64_t *row_cols; const int8_t *label;
+    int64_t n_rows; int n_items; int n_users; int label_S; int max_cand;
+} segmm_itable_t;
+int segmm_assemble_rows(const segmm_itable_t* table, const int64_t* row_ids, int B, int S, int Lt, uint64_t seed, uint32_t site,
+                        int64_t* photo_idx, int64_t* user_idx, int64_t* label, int64_t* cols, segmm_stream_t stream);
 /* Delayed scaling, end of a pass: arena = the pass's n_rows site headers, site_idx[r] = index of row r's tensor site in
  * site_scale (< 0: none).  site_scale[idx] = the power of two s with max|x| * s in [2^(target-1), 2^target) for every row
  * that was produced; stats[0] += number of rows whose planes were outside the fp16 window.  gain / gmax non-NULL (backward pass):

@@ -17,6 +17,7 @@
 #include "gemm_planes4.h"
 #include "loss.h"
 #include "rowops.h"
+#include "assemble.h"
 
 // compute units of the current device (cached; persistent kernels launch one workgroup per CU)
 static int num_cus() {
@@ -1637,6 +1638,33 @@ int segmm_gather_l1(const float* table, int64_t n_lines, int D, const int64_t* i
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(gather_l1_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, (long long)n_lines, D,
                        (const long long*)idx, (long long)rows, normalize, out, mask, amax, plane_out(planes, ld2, hdr, scale_in));
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_assemble_rows(const segmm_itable_t* table, const int64_t* row_ids, int B, int S, int Lt, uint64_t seed, uint32_t site,
+                        int64_t* photo_idx, int64_t* user_idx, int64_t* label, int64_t* cols, segmm_stream_t stream) {
+    SEGMM_REQUIRE(table && row_ids && photo_idx && user_idx && label && cols, "assemble_rows: null pointer");
+    SEGMM_REQUIRE(S >= 1 && S <= 256, "assemble_rows: S = %d (1 .. 256)", S);
+    SEGMM_REQUIRE(Lt >= 1 && Lt <= SEGMM_ASSEMBLE_MAX_CAND, "assemble_rows: Lt = %d (1 .. %d)", Lt, SEGMM_ASSEMBLE_MAX_CAND);
+    SEGMM_REQUIRE(!(seed >> 63), "assemble_rows: a live seed (bit 63 set) is refused -- the draw is a function of (seed, site, row id) and never reads "
+                  "the device step state");
+    const segmm_itable_t& t = *table;
+    SEGMM_REQUIRE(t.item_ptr && t.item_line && t.own_ptr && t.own_line && t.hist_ptr && t.hist_pair && t.row_info && t.row_cols && t.label,
+                  "assemble_rows: null pointer in the table descriptor");
+    SEGMM_REQUIRE(t.n_rows >= 0 && t.n_rows <= (1ll << 50) && t.n_items >= 0 && t.n_users >= 0 && aligned16(t.row_info),
+                  "assemble_rows: table counts (n_rows <= 2^50) / row_info alignment");
+    SEGMM_REQUIRE(t.label_S == S, "assemble_rows: S = %d, the table's labels were compiled for S = %d", S, t.label_S);
+    SEGMM_REQUIRE(t.max_cand >= 0 && t.max_cand <= SEGMM_ASSEMBLE_MAX_CAND, "assemble_rows: the table has a row of %d candidates (limit %d)", t.max_cand,
+                  SEGMM_ASSEMBLE_MAX_CAND);
+    if (B <= 0) return 0;
+    const DropCfg d = make_drop(0.5f, seed, site);
+    if (t.max_cand <= 1024)
+        hipLaunchKernelGGL((assemble_rows_kernel<1024, 4>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, t, (const long long*)row_ids, B, S, Lt, d,
+                           (long long*)photo_idx, (long long*)user_idx, (long long*)label, (long long*)cols);
+    else
+        hipLaunchKernelGGL((assemble_rows_kernel<SEGMM_ASSEMBLE_MAX_CAND, 2>), dim3((B + 1) / 2), dim3(128), 0, (hipStream_t)stream, t, (const long long*)row_ids, B,
+                           S, Lt, d, (long long*)photo_idx, (long long*)user_idx, (long long*)label, (long long*)cols);
     LAUNCH_CHECK();
     return 0;
 }

@@ -1096,6 +1096,32 @@ def gather_l1(table, idx, normalize=True, out=None, mask=None, amax=None, po=Non
     return out, mask.view(torch.bool)
 
 
+class ITable(C.Structure):
+    """segmm_itable_t: the compiled interaction table as device pointers + counts (feature_store.InteractionTable.descriptor)"""
+    _fields_ = [(n, _CTYPE[c]) for n, c in _abi.STRUCT_FIELDS["segmm_itable_t"]]
+
+
+ASSEMBLE_MAX_CAND = _K["SEGMM_ASSEMBLE_MAX_CAND"]          # candidates (video frames / user list) a row may have, and the largest Lt
+ASSEMBLE_COLS = ("photo_id", "photo_identity_id", "user_id", "user_identity_id", "time_ms", "play_time", "duration")
+
+
+def assemble_rows(desc: "ITable", row_ids, S, Lt, seed, site):
+    """``segmm_assemble_rows``: row_ids int64 [B] (device) -> photo_idx [B, S], user_idx [B, Lt] (-1 = padding), label [B, S] and
+    the seven scalar columns as cols [7, B] (ASSEMBLE_COLS order), all int64, fresh tensors.  ``desc``: the table's descriptor,
+    whose tensors the caller keeps alive."""
+    _dev(row_ids)
+    if row_ids.dtype != torch.int64 or row_ids.dim() != 1 or not row_ids.is_contiguous():
+        raise RuntimeError("assemble_rows: row_ids must be a contiguous int64 vector")
+    B, dev = row_ids.numel(), row_ids.device
+    photo = torch.empty((B, int(S)), dtype=torch.int64, device=dev)
+    user = torch.empty((B, int(Lt)), dtype=torch.int64, device=dev)
+    label = torch.empty((B, int(S)), dtype=torch.int64, device=dev)
+    cols = torch.empty((len(ASSEMBLE_COLS), B), dtype=torch.int64, device=dev)
+    _check(lib().segmm_assemble_rows(C.addressof(desc), row_ids.data_ptr(), B, int(S), int(Lt), int(seed), int(site), photo.data_ptr(),
+                                     user.data_ptr(), label.data_ptr(), cols.data_ptr(), _stream()), "segmm_assemble_rows")
+    return photo, user, label, cols
+
+
 def segment_weighted_sum(pred, weight=None, duration=None):
     """sum_seg pred * weight * (seg < duration) over the last axis."""
     _dev(pred)

@@ -4,7 +4,8 @@
   segmminterest_amd/csrc/cmd_dispatch.inc   the switch that lets segmm_run_phase call any stream-taking entry point from a
                                             recorded command (op id + 8-byte argument slots)
   segmminterest_amd/_abi.py                 plain data for the ctypes binding (hipabi.py): every prototype's parameter names and
-                                            type codes, the ABI version, the integer constants, the fields of segmm_attn_planes_t
+                                            type codes, the ABI version, the integer constants, the fields of segmm_attn_planes_t and of the
+                                            other descriptor structs (segmm_itable_t)
 
     python tools/gen_cmd_dispatch.py          # rewrite both files
     python tools/gen_cmd_dispatch.py --check  # fail if either is stale (__graft_entry__.build() and the tests run this)
@@ -26,6 +27,9 @@ SKIP = {"segmm_step_get", "segmm_probe_mfma_rate", "segmm_run_phase", "segmm_ste
 
 # by-value C type -> type code of _abi.py (hipabi.py maps the codes to ctypes); every pointer and segmm_stream_t is "p"
 CODES = {"int": "i", "int64_t": "i64", "float": "f", "uint64_t": "u64", "uint32_t": "u32"}
+
+# descriptor structs an entry point takes by pointer, besides segmm_attn_planes_t: their fields go into STRUCT_FIELDS of _abi.py
+DESCRIPTORS = ("segmm_itable_t",)
 
 
 def strip_comments(txt):
@@ -132,7 +136,11 @@ def abi_py(txt):
     lines += ['    "%s": %d,' % kv for kv in consts.items()]
     lines += ["}", "ATTN_PLANES_FIELDS = ("]
     lines += ['    ("%s", "%s"),' % f for f in struct_fields(txt, "segmm_attn_planes_t")]
-    lines += [")", "# entry point -> ((parameter name, type code), ...) in declaration order", "PROTOTYPES = {"]
+    lines += [")", "# descriptor struct -> ((field name, type code), ...) in declaration order", "STRUCT_FIELDS = {"]
+    for name in DESCRIPTORS:
+        if re.search(r"\}\s*%s\s*;" % re.escape(name), strip_comments(txt)):
+            lines.append('    "%s": (%s),' % (name, "".join('("%s", "%s"), ' % f for f in struct_fields(txt, name)).rstrip()))
+    lines += ["}", "# entry point -> ((parameter name, type code), ...) in declaration order", "PROTOTYPES = {"]
     for n, ps in prototypes(txt):
         lines.append('    "%s": (%s),' % (n, "".join('("%s", "%s"), ' % (p, type_code(ty)) for ty, p in ps).rstrip()))
     lines += ["}", ""]
