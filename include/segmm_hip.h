@@ -492,6 +492,42 @@ int segmm_config_dump(char* buf, int n);
 int segmm_segment_weighted_sum(const float* pred, const float* weight, const int64_t* duration, int64_t rows, int S, float* out,
                                segmm_stream_t stream);
 
+/* (f)-3 on the device: the logit store the inference pass fills (inference/save_logits_for_all_leave_SegMM.py:105-146) answers the
+ * recommender's 'c_interest_weight' lookups (SegRec/models/BaseModel.py:241-286) and feeds ClipRec's sum without a [B, I, S] tensor.
+ * Index of a store (device tensors): keys int64 [n, 3] = (user, item, time_ms), sorted lexicographically (signed) and unique; rows
+ *   int32 [n], rows[k] = the row of the value matrix vals (float32 [m, S], m >= n) of key k.  A key added more than once is listed
+ *   once, with the row of its LAST occurrence (the reference's dict assignment).
+ * segmm_store_lookup: queries user [B], item [B, I] (column 0 = the target), time [B], int64; the target index (keys, rows, n >= 0);
+ *   a negatives index (neg_keys, neg_rows, n_neg >= 0), n_neg < 0 = none given; dense id maps user_map [n_um] / item_map [n_im]
+ *   (int64, null = identity) applied to the ids first (the non-KuaiRand branch, :264-286).  rowidx int32 [B, I], miss int64 [2], which
+ *   the caller initialises to INT64_MAX.  Per row b, t = the row of (user, item[b, 0], time) in the target index:
+ *     t absent                                -> rowidx[b, :] = -1 ("ones");
+ *     t present, no negatives index or I <= 2 -> rowidx[b, :] = t (the reference's len(item_ids) > 2: at I == 2 a negatives file
+ *                                                is ignored);
+ *     t present, negatives index and I > 2    -> rowidx[b, 0] = t, rowidx[b, j] = -2 - r with r = the row of (user, item[b, j], time)
+ *                                                in the negatives index; that key absent: rowidx[b, j] = -1, miss[0] = min(miss[0], b * I + j).
+ *   An id outside its map or a map entry < 0 counts as an absent key -- a bad user or target: t absent, miss[1] = min(miss[1], b * I);
+ *   a bad item j >= 1 (every item is mapped when item_map is given, as the reference does): rowidx[b, j] = -1, miss[1] =
+ *   min(miss[1], b * I + j).  Both slots are minima: deterministic, the first offender in row-major order.
+ *   One workgroup per row b; the target key is searched once per workgroup; a search compares three 64-bit words.  B == 0 launches nothing.
+ * segmm_store_head: out[r] = sum_s pred[r, s] * w(r)[s] * (s < duration[r]) over the rows r = (b, i) of pred [rows, S], with
+ *   w(r) = ones for rowidx[r] == -1, vals[rowidx[r]] for rowidx[r] >= 0, neg_vals[-2 - rowidx[r]] for rowidx[r] <= -2 (vals [m, S],
+ *   neg_vals [m_neg, S]).  duration int64 [rows] or null (no mask).  weight_out non-null: also weight_out[r, :] = w(r) (float32
+ *   [rows, S]); pred == null and out == null: only that.  A rowidx outside its value matrix (or into a null one) touches no memory:
+ *   its weight is NaN, so the result shows it (segmm_embed_id_vid's convention for bad ids).  Any S >= 1; rows == 0 launches nothing.
+ *   Each product is rounded once and multiplied by the mask's 0 or 1; the summation order is a function of S and the pointers'
+ *   alignment only: bit-identical from run to run.  m, m_neg < 2^31 - 1.
+ * segmm_store_head_bwd: dpred[r, s] = (g[r] * w(r)[s]) * (s < duration[r]) -- one rounded product, then a multiplication by 0 or 1.
+ *   w(r) from rowidx + the value matrices as above, or from an explicit weight [rows, S] (rowidx null), or ones (both null). */
+int segmm_store_lookup(const int64_t* user, const int64_t* item, const int64_t* time, int B, int I, const int64_t* keys,
+                       const int32_t* rows, int64_t n, const int64_t* neg_keys, const int32_t* neg_rows, int64_t n_neg,
+                       const int64_t* user_map, int64_t n_um, const int64_t* item_map, int64_t n_im, int32_t* rowidx, int64_t* miss,
+                       segmm_stream_t stream);
+int segmm_store_head(const float* pred, const int32_t* rowidx, const float* vals, int64_t m, const float* neg_vals, int64_t m_neg,
+                     const int64_t* duration, int64_t rows, int S, float* out, float* weight_out, segmm_stream_t stream);
+int segmm_store_head_bwd(const float* g, const int32_t* rowidx, const float* vals, int64_t m, const float* neg_vals, int64_t m_neg,
+                         const float* weight, const int64_t* duration, int64_t rows, int S, float* dpred, segmm_stream_t stream);
+
 /* up to three column sums out_i[n] = sum_m X_i[m, n] of same-shaped matrices in one launch pair (X1/X2 may be null);
  * workspace: 3 * segmm_colsum_chunks(M) * N floats.  Used for the partial buffers of segmm_layernorm_bwd. */
 int segmm_colsum3(const float* X0, const float* X1, const float* X2, int ld, int64_t M, int N, float* out0, float* out1,

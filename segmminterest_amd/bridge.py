@@ -10,7 +10,8 @@ SegRec/models/BaseModel.py:228-288), which ``ClipRec.forward`` multiplies into t
 ``LogitStore`` keeps the same mapping as three int64 key columns + one float32 [n, S] matrix, writes the reference's
 JSON byte-for-byte (same key format, ``json.dump`` of python floats converted from fp32 like ``tensor.tolist()``) and a
 binary ``.npz`` that loads without parsing 40 floats per row from text; ``weights`` answers a whole batch of lookups
-with one vectorised search and ``weighted_head`` is the device kernel for the ClipRec sum."""
+with one vectorised search and ``weighted_head`` is the device kernel for the ClipRec sum.  ``DeviceLogitStore`` is the same store
+with the values resident on the device: lookups and the head run as kernels (csrc/storeops.h)."""
 from __future__ import annotations
 
 import json
@@ -135,7 +136,191 @@ class LogitStore:
         return w.to(device) if device is not None else w
 
 
+def _dense_map(d, device):
+    """A str-keyed id dict of the reference (``id2user`` / ``id2item``) as the dense int64 map of ``segmm_store_lookup``: entry k = the
+    value of key str(k), -1 where the dict has none."""
+    ks = np.fromiter((int(k) for k in d), np.int64, len(d))
+    if len(ks) and ks.min() < 0:
+        raise ValueError("DeviceLogitStore: an id map with negative keys has no dense form")
+    m = np.full((int(ks.max()) + 1 if len(ks) else 0,), -1, np.int64)
+    m[ks] = np.fromiter((int(v) for v in d.values()), np.int64, len(d))
+    return torch.from_numpy(m).to(device)
+
+
+class DeviceLogitStore:
+    """``LogitStore`` with the logits resident on the device from the forward that produced them to the head that consumes them.
+    ``add_batch`` keeps device tensors and never synchronises; ``finalize`` sorts the three key columns on the host once (the
+    values stay where they are) and uploads the index; ``lookup`` / ``weights`` / ``head`` answer the reader's rule
+    (``LogitStore.weights``) with ``segmm_store_lookup`` and ``segmm_store_head`` (include/segmm_hip.h).  ``head`` forms no
+    [B, I, S] tensor and is differentiable in ``pred``."""
+
+    def __init__(self, S: int = 40, device="cuda"):
+        self.S = S
+        self.device = torch.device(device)
+        self._keys = []          # device [n_i, 3] int64 blocks
+        self._vals = []          # device [n_i, S] float32 blocks
+        self._index = None       # (keys [n, 3] int64, rows [n] int32) on the device
+        self._maps = {}          # id(dict) -> (dict, its length, dense device map): the last MAX_MAPS dicts
+
+    # ---- writer side
+    def add_batch(self, user_id, photo_id, time_ms, logits):
+        k = torch.stack([torch.as_tensor(v).to(self.device, torch.int64).reshape(-1) for v in (user_id, photo_id, time_ms)], 1)
+        v = torch.as_tensor(logits).detach().to(self.device, torch.float32, copy=True).reshape(k.shape[0], -1)          # a copy: forward buffers are reused
+        if v.shape[1] != self.S:
+            raise ValueError("logits have %d segments, store expects %d" % (v.shape[1], self.S))
+        self._keys.append(k)
+        self._vals.append(v)
+        self._index = None
+
+    def _cat(self):
+        if len(self._keys) > 1:
+            self._keys, self._vals = [torch.cat(self._keys, 0)], [torch.cat(self._vals, 0)]
+        if not self._keys:
+            self._keys = [torch.zeros((0, 3), dtype=torch.int64, device=self.device)]
+            self._vals = [torch.zeros((0, self.S), dtype=torch.float32, device=self.device)]
+        return self._keys[0], self._vals[0]
+
+    def __len__(self):
+        return sum(k.shape[0] for k in self._keys)
+
+    def finalize(self):
+        """Builds the index by ``LogitStore``'s rule (lexicographic order, last occurrence of a key wins): ONE device-to-host copy
+        of the key columns, the sort on the host, the sorted keys and their value rows back up."""
+        if self._index is None:
+            k, _ = self._cat()
+            h = LogitStore(self.S)
+            h._keys, h._vals = [k.cpu().numpy()], [np.zeros((k.shape[0], 0), np.float32)]
+            h._build_index()
+            ks, rows = h._index
+            self._index = (torch.from_numpy(np.ascontiguousarray(ks)).to(self.device),
+                           torch.from_numpy(rows.astype(np.int32)).to(self.device))
+        return self
+
+    @classmethod
+    def from_store(cls, store: LogitStore, device="cuda"):
+        k, v = store._cat()
+        st = cls(S=store.S, device=device)
+        st._keys, st._vals = [torch.from_numpy(np.ascontiguousarray(k, np.int64)).to(st.device)], [torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(st.device)]
+        return st
+
+    def to_store(self) -> LogitStore:
+        """The host store of the same batches (one copy of the keys and the values): ``save_json`` / ``save_binary`` of it write the
+        bytes a ``LogitStore`` fed the same batches writes."""
+        k, v = self._cat()
+        st = LogitStore(self.S)
+        if k.shape[0]:
+            st._keys, st._vals = [k.cpu().numpy()], [v.cpu().numpy()]
+        return st
+
+    # ---- reader side
+    MAX_MAPS = 4          # id dicts whose dense form is kept (a store sees one id2user and one id2item)
+
+    def _map(self, m):
+        """The dense device map of an id dict, converted once and kept while the dict is the same object of the same length (a dict
+        that is changed in place without changing its length must not be passed again: its dense form would be stale).  Device
+        tensors pass through."""
+        if m is None or torch.is_tensor(m):
+            return None if m is None else m.to(self.device, torch.int64).contiguous()
+        hit = self._maps.get(id(m))
+        if hit is None or hit[0] is not m or hit[1] != len(m):
+            self._maps.pop(id(m), None)
+            while len(self._maps) >= self.MAX_MAPS:
+                self._maps.pop(next(iter(self._maps)))          # the oldest entry
+            hit = self._maps[id(m)] = (m, len(m), _dense_map(m, self.device))
+        return hit[2]
+
+    def _query(self, user_id, item_ids, time_ms):
+        q = [torch.as_tensor(x).to(self.device, torch.int64) for x in (user_id, item_ids, time_ms)]
+        return q[0].reshape(-1).contiguous(), q[1].contiguous(), q[2].reshape(-1).contiguous()
+
+    def lookup(self, user_id, item_ids, time_ms, neg: "Optional[DeviceLogitStore]" = None, id2user=None, id2item=None, check=True):
+        """rowidx int32 [B, I] of the batch (``segmm_store_lookup``: -1 = ones, r >= 0 = this store's value row r, r <= -2 = row
+        -2 - r of ``neg``).  ``check=True`` reads the two miss slots once and raises what ``LogitStore.weights`` raises; ``check=False``
+        returns (rowidx, miss) and does not synchronise."""
+        from . import hipabi as H
+        self.finalize()
+        u, it, t = self._query(user_id, item_ids, time_ms)
+        um, im = self._map(id2user), self._map(id2item)
+        nidx = neg.finalize()._index if neg is not None else (None, None)
+        rowidx, miss = H.store_lookup(u, it, t, *self._index, neg_keys=nidx[0], neg_rows=nidx[1], user_map=um, item_map=im)
+        if not check:
+            return rowidx, miss
+        m0, m1 = miss.tolist()
+        if m1 != H.STORE_MISS_NONE:          # the id maps are applied first, users before items (LogitStore.weights)
+            for ids, mp in ((u, um), (it.reshape(-1), im)):
+                if mp is not None:
+                    bad = (ids < 0) | (ids >= mp.numel())
+                    bad = bad | (mp[ids.clamp(0, max(mp.numel() - 1, 0))] < 0) if mp.numel() else torch.ones_like(bad)
+                    if bool(bad.any()):
+                        raise KeyError(str(int(ids[int(torch.nonzero(bad)[0])])))
+        if m0 != H.STORE_MISS_NONE:
+            b, j = divmod(m0, it.shape[1])
+            uu, ii = (int(u[b]) if um is None else int(um[u[b]])), (int(it[b, j]) if im is None else int(im[it[b, j]]))
+            raise KeyError("Inference, Key %d-%d-%d not found in clip_weight" % (uu, ii, int(t[b])))
+        return rowidx
+
+    def _neg_vals(self, neg):
+        return None if neg is None else neg._cat()[1]
+
+    def weights(self, user_id, item_ids, time_ms, neg: "Optional[DeviceLogitStore]" = None, id2user=None, id2item=None):
+        """``LogitStore.weights`` on the device: float32 [B, I, S], a copy of the stored rows."""
+        from . import hipabi as H
+        rowidx = self.lookup(user_id, item_ids, time_ms, neg=neg, id2user=id2user, id2item=id2item)
+        return H.store_head(None, rowidx, self._cat()[1], self._neg_vals(neg))
+
+    def head(self, pred, user_id, item_ids, time_ms, duration=None, neg: "Optional[DeviceLogitStore]" = None, id2user=None, id2item=None,
+             check=True):
+        """ClipRec's ``(clip_predictions * c_interest_weight * mask).sum(-1)`` for a batch of queries: pred [B, I, S] -> [B, I],
+        the weights read from the store's rows by the kernel; differentiable in ``pred`` (the backward keeps rowidx, not weights).
+        ``check=False`` does not synchronise and returns (out, miss): a missing negatives key or id counts as ones in ``out``, and
+        ``miss`` (``lookup``'s two slots) is how the caller finds out."""
+        r = self.lookup(user_id, item_ids, time_ms, neg=neg, id2user=id2user, id2item=id2item, check=check)
+        rowidx, miss = (r, None) if check else r
+        if duration is not None:
+            duration = torch.as_tensor(duration).to(self.device, torch.int64).contiguous()
+        out = _StoreHead.apply(pred, rowidx, self._cat()[1], self._neg_vals(neg), duration)
+        return out if check else (out, miss)
+
+
+class _StoreHead(torch.autograd.Function):
+    """``segmm_store_head`` / ``segmm_store_head_bwd``: the weights are constants named by rowidx"""
+
+    @staticmethod
+    def forward(ctx, pred, rowidx, vals, neg_vals, duration):
+        from . import hipabi as H
+        ctx.save_for_backward(rowidx, vals, neg_vals, duration)
+        ctx.S = pred.shape[-1]
+        return H.store_head(pred.detach().contiguous(), rowidx, vals, neg_vals, duration)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import hipabi as H
+        rowidx, vals, neg_vals, duration = ctx.saved_tensors
+        return H.store_head_bwd(g.contiguous(), ctx.S, rowidx=rowidx, vals=vals, neg_vals=neg_vals, duration=duration), None, None, None, None
+
+
+class _WeightedHead(torch.autograd.Function):
+    """``segmm_segment_weighted_sum`` forward; d pred = g * weight * mask (``segmm_store_head_bwd`` with an explicit weight)"""
+
+    @staticmethod
+    def forward(ctx, pred, weight, duration):
+        from . import hipabi as H
+        ctx.save_for_backward(weight, duration)
+        ctx.S = pred.shape[-1]
+        return H.segment_weighted_sum(pred.detach(), weight, duration)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import hipabi as H
+        weight, duration = ctx.saved_tensors
+        return H.store_head_bwd(g.contiguous(), ctx.S, weight=None if weight is None else weight.contiguous(),
+                                duration=None if duration is None else duration.contiguous()), None, None
+
+
 def weighted_head(pred: torch.Tensor, weight: Optional[torch.Tensor] = None, duration: Optional[torch.Tensor] = None):
-    """ClipRec.forward's ``(clip_predictions * interest_weight * mask).sum(-1)`` (ClipRec.py:163-181) on the device."""
+    """ClipRec.forward's ``(clip_predictions * interest_weight * mask).sum(-1)`` (ClipRec.py:163-181) on the device; differentiable in
+    ``pred`` (``weight`` and ``duration`` are constants)."""
     from . import hipabi as H
-    return H.segment_weighted_sum(pred, weight, duration)
+    if not pred.requires_grad or not torch.is_grad_enabled():
+        return H.segment_weighted_sum(pred, weight, duration)
+    return _WeightedHead.apply(pred, weight, duration)

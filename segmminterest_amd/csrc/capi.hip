@@ -18,6 +18,7 @@
 #include "loss.h"
 #include "rowops.h"
 #include "assemble.h"
+#include "storeops.h"
 
 // compute units of the current device (cached; persistent kernels launch one workgroup per CU)
 static int num_cus() {
@@ -1675,6 +1676,82 @@ int segmm_segment_weighted_sum(const float* pred, const float* weight, const int
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(segment_weighted_sum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pred, weight,
                        (const long long*)duration, (long long)rows, S, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_store_lookup(const int64_t* user, const int64_t* item, const int64_t* time, int B, int I, const int64_t* keys,
+                       const int32_t* rows, int64_t n, const int64_t* neg_keys, const int32_t* neg_rows, int64_t n_neg,
+                       const int64_t* user_map, int64_t n_um, const int64_t* item_map, int64_t n_im, int32_t* rowidx, int64_t* miss,
+                       segmm_stream_t stream) {
+    SEGMM_REQUIRE(B >= 0 && I >= 1 && (int64_t)B * I < (1ll << 40), "store_lookup: B = %d, I = %d (I >= 1)", B, I);
+    SEGMM_REQUIRE(n >= 0 && n < 0x7fffffffll && n_neg < 0x7fffffffll, "store_lookup: n = %lld, n_neg = %lld (0 <= n < 2^31 - 1)", (long long)n,
+                  (long long)n_neg);
+    SEGMM_REQUIRE((n == 0 || (keys && rows)) && (n_neg <= 0 || (neg_keys && neg_rows)), "store_lookup: null index of %lld / %lld keys",
+                  (long long)n, (long long)n_neg);
+    SEGMM_REQUIRE((!user_map || n_um >= 0) && (!item_map || n_im >= 0), "store_lookup: negative id map length");
+    if (B == 0) return 0;
+    SEGMM_REQUIRE(user && item && time && rowidx && miss, "store_lookup: null pointer");
+    hipLaunchKernelGGL(store_lookup_kernel, dim3((unsigned)B), dim3(I > 128 ? 256 : 64), 0, (hipStream_t)stream, (const long long*)user,
+                       (const long long*)item, (const long long*)time, I, (const long long*)keys, (const int*)rows, (long long)n,
+                       (const long long*)neg_keys, (const int*)neg_rows, (long long)n_neg, (const long long*)user_map, (long long)n_um,
+                       (const long long*)item_map, (long long)n_im, (int*)rowidx, (long long*)miss);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// the head kernels' layout for rows of S floats: V floats per access, 2^lg lanes per row, the grid (grid-stride beyond it)
+struct StoreHeadPlan { int V, lg; bool one; unsigned blocks; };
+static StoreHeadPlan store_head_plan(int64_t rows, int S, bool all_aligned, bool pair) {
+    StoreHeadPlan p;
+    p.V = (S % 4 == 0 && all_aligned) ? 4 : 1;
+    p.lg = 0;
+    while ((1 << p.lg) < S / p.V && p.lg < 6) ++p.lg;
+    p.one = S / p.V <= 64;          // a row is one round of chunks: the forward takes SEGMM_STORE_HEAD_U row groups per trip
+    const int64_t per_block = 4ll * (64 >> p.lg) * (pair && p.one ? SEGMM_STORE_HEAD_U : 1);
+    const int64_t need = (rows + per_block - 1) / per_block;
+    p.blocks = (unsigned)(need < 4096 ? need : 4096);
+    return p;
+}
+
+int segmm_store_head(const float* pred, const int32_t* rowidx, const float* vals, int64_t m, const float* neg_vals, int64_t m_neg,
+                     const int64_t* duration, int64_t rows, int S, float* out, float* weight_out, segmm_stream_t stream) {
+    SEGMM_REQUIRE(S >= 1 && rows >= 0 && m >= 0 && m_neg >= 0 && m < 0x7fffffffll && m_neg < 0x7fffffffll,
+                  "store_head: S = %d, rows = %lld, m = %lld, m_neg = %lld (S >= 1, 0 <= m < 2^31 - 1)", S, (long long)rows, (long long)m, (long long)m_neg);
+    SEGMM_REQUIRE((pred != nullptr) == (out != nullptr) && (out || weight_out), "store_head: pred and out go together; without them weight_out");
+    if (rows == 0) return 0;
+    SEGMM_REQUIRE(rowidx, "store_head: null rowidx");
+    const StoreW w{(const int*)rowidx, vals, (long long)m, neg_vals, (long long)m_neg, nullptr};
+    const StoreHeadPlan p = store_head_plan(rows, S, aligned16(pred) && aligned16(vals) && aligned16(neg_vals) && aligned16(weight_out), true);
+#define SEGMM_STORE_HEAD(V, ONE)                                                                                                        \
+    hipLaunchKernelGGL((store_head_kernel<V, ONE>), dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, pred, w, (const long long*)duration, \
+                       (long long)rows, S, p.lg, out, weight_out)
+    if (p.V == 4) {
+        if (p.one) SEGMM_STORE_HEAD(4, true); else SEGMM_STORE_HEAD(4, false);
+    } else {
+        if (p.one) SEGMM_STORE_HEAD(1, true); else SEGMM_STORE_HEAD(1, false);
+    }
+#undef SEGMM_STORE_HEAD
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_store_head_bwd(const float* g, const int32_t* rowidx, const float* vals, int64_t m, const float* neg_vals, int64_t m_neg,
+                         const float* weight, const int64_t* duration, int64_t rows, int S, float* dpred, segmm_stream_t stream) {
+    SEGMM_REQUIRE(S >= 1 && rows >= 0 && m >= 0 && m_neg >= 0 && m < 0x7fffffffll && m_neg < 0x7fffffffll,
+                  "store_head_bwd: S = %d, rows = %lld, m = %lld, m_neg = %lld (S >= 1, 0 <= m < 2^31 - 1)", S, (long long)rows, (long long)m,
+                  (long long)m_neg);
+    SEGMM_REQUIRE(!(rowidx && weight), "store_head_bwd: rowidx and an explicit weight exclude each other");
+    if (rows == 0) return 0;
+    SEGMM_REQUIRE(g && dpred, "store_head_bwd: null pointer");
+    const StoreW w{(const int*)rowidx, vals, (long long)m, neg_vals, (long long)m_neg, weight};
+    const StoreHeadPlan p = store_head_plan(rows, S, aligned16(vals) && aligned16(neg_vals) && aligned16(weight) && aligned16(dpred), false);
+    if (p.V == 4)
+        hipLaunchKernelGGL(store_head_bwd_kernel<4>, dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, g, w, (const long long*)duration,
+                           (long long)rows, S, p.lg, dpred);
+    else
+        hipLaunchKernelGGL(store_head_bwd_kernel<1>, dim3(p.blocks), dim3(256), 0, (hipStream_t)stream, g, w, (const long long*)duration,
+                           (long long)rows, S, p.lg, dpred);
     LAUNCH_CHECK();
     return 0;
 }

@@ -1134,6 +1134,115 @@ def segment_weighted_sum(pred, weight=None, duration=None):
     return out
 
 
+STORE_MISS_NONE = (1 << 63) - 1          # what both slots of store_lookup's ``miss`` hold when nothing was missed
+
+
+def _i64c(t, name, shape=None):
+    if t.dtype != torch.int64 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError("%s must be contiguous int64%s (got %s %s, contiguous=%s)"
+                           % (name, "" if shape is None else " " + str(list(shape)), t.dtype, list(t.shape), t.is_contiguous()))
+    return t
+
+
+def _store_index(keys, rows, name):
+    """(keys, rows, n) of one index of ``segmm_store_lookup`` after the argument checks; ``(None, None, n)`` for an empty one."""
+    _dev(keys, rows)
+    n = keys.shape[0]
+    _i64c(keys, name + " keys", (n, 3))
+    if rows.dtype != torch.int32 or not rows.is_contiguous() or tuple(rows.shape) != (n,):
+        raise RuntimeError("%s rows must be contiguous int32 [%d]" % (name, n))
+    return (keys, rows, n) if n else (None, None, 0)
+
+
+def store_lookup(user, item, time, keys, rows, neg_keys=None, neg_rows=None, user_map=None, item_map=None, miss=None):
+    """``segmm_store_lookup``: user [B], item [B, I] (column 0 = the target), time [B] (device int64) against the target index
+    (keys int64 [n, 3], rows int32 [n]) and, when given, the negatives index and the dense id maps -> (rowidx int32 [B, I], miss
+    int64 [2]).  miss[0] / miss[1]: the first flat index b * I + j whose negatives key / whose id was missing, STORE_MISS_NONE when
+    none was.  Never synchronises."""
+    _dev(user, item, time, user_map, item_map)
+    if item.dim() != 2:
+        raise RuntimeError("store_lookup: item must be [B, I]")
+    B, I = item.shape
+    _i64c(user, "store_lookup: user", (B,)), _i64c(item, "store_lookup: item"), _i64c(time, "store_lookup: time", (B,))
+    keys, rows, n = _store_index(keys, rows, "store_lookup: target")
+    if (neg_keys is None) != (neg_rows is None):
+        raise RuntimeError("store_lookup: neg_keys and neg_rows go together")
+    nk, nr, nn = _store_index(neg_keys, neg_rows, "store_lookup: negatives") if neg_keys is not None else (None, None, -1)
+    for mp, nm in ((user_map, "user_map"), (item_map, "item_map")):
+        if mp is not None:
+            _i64c(mp, "store_lookup: " + nm, (mp.numel(),))
+    rowidx = torch.empty((B, I), dtype=torch.int32, device=item.device)
+    if miss is None:
+        miss = torch.full((2,), STORE_MISS_NONE, dtype=torch.int64, device=item.device)
+    else:
+        _dev(miss), _i64c(miss, "store_lookup: miss", (2,))
+    _check(lib().segmm_store_lookup(_ptr(user), _ptr(item), _ptr(time), B, I, _ptr(keys), _ptr(rows), n, _ptr(nk), _ptr(nr), nn,
+                                    _ptr(user_map), 0 if user_map is None else user_map.numel(), _ptr(item_map),
+                                    0 if item_map is None else item_map.numel(), _ptr(rowidx), _ptr(miss), _stream()), "segmm_store_lookup")
+    return rowidx, miss
+
+
+def _store_vals(vals, S, name):
+    """(pointer, rows) of a value matrix [m, S]; a missing or empty one is (None, 0): an index into it gives NaN weights"""
+    if vals is None or vals.shape[0] == 0:
+        return None, 0
+    _dev(vals)
+    if vals.dim() != 2 or vals.shape[1] != S:
+        raise RuntimeError("%s must be [m, %d] (got %s)" % (name, S, list(vals.shape)))
+    return _ptr(_f32c(vals, name)), vals.shape[0]
+
+
+def _store_rows(rowidx, duration, shape, what):
+    _dev(rowidx, duration)
+    if rowidx is not None and (rowidx.dtype != torch.int32 or not rowidx.is_contiguous() or tuple(rowidx.shape) != tuple(shape)):
+        raise RuntimeError("%s: rowidx must be contiguous int32 %s" % (what, list(shape)))
+    if duration is not None:
+        _i64c(duration, what + ": duration", shape)
+
+
+def store_head(pred, rowidx, vals, neg_vals=None, duration=None, weight_out=False):
+    """``segmm_store_head``: out[..., i] = sum_s pred[..., i, s] * w(rowidx[..., i])[s] * (s < duration[..., i]); rowidx -1 = ones,
+    r >= 0 = vals[r], r <= -2 = neg_vals[-2 - r].  ``weight_out=True``: returns (out, weights [..., S]) as well.  ``pred=None``: only
+    the weights, of ``vals``' segment count."""
+    _dev(pred, rowidx)
+    if pred is None:
+        if vals is None:
+            raise RuntimeError("store_head: without pred the segment count comes from vals")
+        S, shape, weight_out = vals.shape[1], tuple(rowidx.shape), True
+    else:
+        S, shape = pred.shape[-1], tuple(pred.shape[:-1])
+        _f32c(pred, "store_head: pred")
+    _store_rows(rowidx, duration, shape, "store_head")
+    vp, m = _store_vals(vals, S, "store_head: vals")
+    ngp, mn = _store_vals(neg_vals, S, "store_head: neg_vals")
+    out = None if pred is None else torch.empty(shape, dtype=torch.float32, device=rowidx.device)
+    w = torch.empty(shape + (S,), dtype=torch.float32, device=rowidx.device) if weight_out else None
+    rows = rowidx.numel()
+    with _kprof("store_head", rows * (4 * S * ((pred is not None) + (w is not None)) + 8 + 8 * (duration is not None))):
+        _check(lib().segmm_store_head(_ptr(pred), _ptr(rowidx), vp, m, ngp, mn, _ptr(duration), rows, S, _ptr(out), _ptr(w), _stream()),
+               "segmm_store_head")
+    return w if pred is None else (out, w) if weight_out else out
+
+
+def store_head_bwd(g, S, rowidx=None, vals=None, neg_vals=None, weight=None, duration=None):
+    """``segmm_store_head_bwd``: dpred[..., i, s] = (g[..., i] * w[s]) * (s < duration[..., i]) with w from rowidx + the value
+    matrices, from an explicit ``weight`` [..., S], or ones."""
+    _dev(g, weight)
+    shape, S = tuple(g.shape), int(S)
+    _f32c(g, "store_head_bwd: g")
+    if rowidx is not None and weight is not None:
+        raise RuntimeError("store_head_bwd: rowidx and an explicit weight exclude each other")
+    _store_rows(rowidx, duration, shape, "store_head_bwd")
+    if weight is not None and (tuple(weight.shape) != shape + (S,) or weight.dtype != torch.float32 or not weight.is_contiguous()):
+        raise RuntimeError("store_head_bwd: weight must be contiguous float32 %s" % list(shape + (S,)))
+    vp, m = _store_vals(vals, S, "store_head_bwd: vals")
+    ngp, mn = _store_vals(neg_vals, S, "store_head_bwd: neg_vals")
+    dpred = torch.empty(shape + (S,), dtype=torch.float32, device=g.device)
+    _check(lib().segmm_store_head_bwd(_ptr(g), _ptr(rowidx), vp, m, ngp, mn, _ptr(weight), _ptr(duration), g.numel(), S, _ptr(dpred),
+                                      _stream()), "segmm_store_head_bwd")
+    return dpred
+
+
 def pool_tokens(U, Lu, V, Lv, out, B, d, bins):
     """AdaptiveAvgPool1d(bins) over the tokens of cat(U[B,Lu,d], V[B,Lv,d]) (CrossMLP ablation)."""
     _dev(U, V, out)

@@ -1257,6 +1257,22 @@ class Trainer:
         return model(usr_image=usr, usr_id=batch["user_identity_id"], usr_mask=um, vid_image=vid,
                      vid_id=batch["photo_identity_id"], vid_mask=vm, gt=batch["label"], mode=mode)
 
+    @torch.no_grad()
+    def dump_logits(self, splits, store=None):
+        """The dump loop of the reference's inference script (inference/save_logits_for_all_leave_SegMM.py:105-146): eval mode,
+        ``mode="inference"`` over every batch of every split in order, ``test_logits["<user_id>-<photo_id>-<time_ms>"] = logits`` --
+        into a :class:`bridge.DeviceLogitStore`, so the logits stay on the device and no batch synchronises with the host.  ``splits``:
+        an iterable of batch iterables (train, valid, test; ``DeviceBatches`` yields the three key columns on the device)."""
+        from .bridge import DeviceLogitStore
+        for batches in splits:
+            for batch in batches:
+                logits = self.eval_step(batch, mode="inference")["logits"]
+                if store is None:
+                    store = DeviceLogitStore(S=logits.shape[1], device=logits.device)
+                store.add_batch(batch["user_id"], batch["photo_id"], batch["time_ms"], logits)
+        if store is None:
+            store = DeviceLogitStore(device=next(self.model.parameters()).device)
+        return store
 
     @torch.no_grad()
     def valid_model(self, batches, metrics=("valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"),
