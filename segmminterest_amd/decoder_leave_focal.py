@@ -9,8 +9,6 @@ and ``HeadLossFn``).
 """
 from __future__ import annotations
 
-import contextlib
-
 import torch
 import torch.nn as nn
 
@@ -159,10 +157,10 @@ class HeadLossFn(torch.autograd.Function):
         dv2 = torch.empty(M, d, device=v1.device) if v2 is not None else None
         model._head_bwd(v1, v2, dl, dv1, dv2, ctx.T, M, d, B, S, gbuf)
         if gbuf is None and st.bucket_hook is not None:
-            st.bucket_hook("head", after_side=st.head_side)
+            st.bucket_hook("head", after_side=True)
         ctx.dlogits = ctx.T = None
         if not st.direct_grads or gbuf is not None:
-            # the head's weight / bias gradients were written on the side stream (head_side): autograd consumes the views it is
+            # the head's weight / bias gradients were written on the side stream: autograd consumes the views it is
             # handed at once on THIS stream (hooks, AccumulateGrad's += on a second backward, clones) and a fresh ``gbuf`` may be
             # recycled by the caching allocator while the side stream still writes it -- join first.  The trainer's direct
             # delivery (views of the persistent flat buffer, ordered by the DP hook / the end-of-backward join) stays unjoined.
@@ -323,8 +321,8 @@ class MultiScaleTemporalDetrLeaveFocal(nn.Module):
                 H.rowscale_bcast(dl, st.p(wname), dx, d, M, d, w_off=w_off)
             # the head's own weight / bias gradients feed nothing in the backward: on the side stream, off the chain
             # loss -> d(features) -> LayerNorm backward -> first input-gradient GEMM that the main stream is waiting on
-            with (E.side_work(st) if st.head_side else contextlib.nullcontext()):
-                if st.head_side and st.overlap:          # x and dl are autograd-owned tensors: the allocator must not hand their
+            with E.side_work(st):
+                if st.overlap:          # x and dl are autograd-owned tensors: the allocator must not hand their
                     side = st.side_stream()               # memory out again before the side stream has read them
                     x.record_stream(side)
                     dl.record_stream(side)
@@ -357,7 +355,7 @@ class MultiScaleTemporalDetrLeaveFocal(nn.Module):
             for h in range(fh):
                 # dx_h += dT_h . W_h^T ; dW_h = x_h^T . dT_h
                 H.gemm(H.LAYOUT_NT, M, hx, hx, dT, d, wxy, hx, dv1, d, accumulate=True, a_off=h * hx, b_off=h * hx * hx, c_off=h * hx)
-                splits = E._splits_for(hx, hx, M)
+                splits = E._splits_for(hx, hx, M, st.split_target, st.gemm_bn)
                 ws = st.buf("splitk_ws", (max(splits, 1) * hx * hx,)) if splits > 1 else None
                 H.gemm(H.LAYOUT_TN, hx, hx, M, v1, d, dT, d, gw, hx, splits=splits, workspace=ws, a_off=h * hx, b_off=h * hx,
                        c_off=h * hx * hx)

@@ -18,12 +18,12 @@ from __future__ import annotations
 
 import contextlib
 import math
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import hipabi as H
+from . import switches
 
 # dropout site ids (distinct hash streams): site = backbone*4096 + layer*32 + kind
 K_EMB_V, K_EMB_U, K_ATT_V, K_ATT_U, K_AO_V, K_AO_U, K_MI_V, K_MI_U, K_MO_V, K_MO_U = range(1, 11)
@@ -152,79 +152,40 @@ class ParamStore:
         self.row_exchange = None
         self._side_stream = None
         self._on_side = False
-        self.overlap = os.environ.get("SEGMM_OVERLAP", "1") != "0"
-        # weight gradients of a layer's ff / MLP Linears enqueued (side stream) right before the attention backward instead of
-        # next to their input-gradient GEMMs; the LayerNorm-backward column sums on the side stream.  Both were measured +-0 / -2 %
-        # while the host enqueued the step launch by launch; with the recorded step (host 0.3 ms) and the round-4 attention
-        # kernels: config 2 133.5 -> 136.2 k/s together (same box, alternating runs: +1.2 % and +0.4 % alone) -- the attention
-        # backward leaves CUs idle while its workgroups wait on memory, and a GEMM tile that gets such a CU is productive -- but
-        # config 3 (20 segments: short attention launches, K = 512 GEMMs) 185.4 -> 181.8 k/s.  "auto" (default): on for
-        # segment axes > 32 on the plane engine (BackboneRun.backward); SEGMM_DEFER_WGRAD / SEGMM_LN_SIDE = 0 / 1 force them.
-        self.ln_pos = os.environ.get("SEGMM_LN_POS", "1") != "0"          # embedding LayerNorm backward leaves per-position sums (_ln_bwd)
-        self.lazy_head_grad = os.environ.get("SEGMM_LAZY_HEAD_GRAD", "1") != "0"          # head gradient formed inside the first LayerNorm backward
-        self.head_dot = os.environ.get("SEGMM_HEAD_DOT", "1") != "0"          # ... and the head's logits inside the last LayerNorm forward
-        self._defer_wgrad_env = os.environ.get("SEGMM_DEFER_WGRAD", "auto")
-        self._ln_side_env = os.environ.get("SEGMM_LN_SIDE", "auto")
-        self.defer_wgrad = self._defer_wgrad_env not in ("0", "auto")
-        self.tail_balance = os.environ.get("SEGMM_TAIL_BALANCE", "1") != "0"
-        self.attn_planes_only = int(os.environ.get("SEGMM_ATTN_PLANES_ONLY", "1"))
-        # round 5: the attention forward reads the Q / K / V planes the fused projection GEMMs write (csrc/attention_pl.h)
-        # 1 (default): with the projection outputs Yv / Yu as planes ONLY (no fp32 copy: the planes-in backward reads them too, a repair
-        # launch of the GEMM covers a wrong delayed scale); 2: planes beside the fp32 copy, forward only (measured -1.5 %); 0: off
-        self.attn_pl = int(os.environ.get("SEGMM_ATT_PL", "1"))
-        self.eu_planes_only = os.environ.get("SEGMM_EU_PLANES_ONLY", "1") != "0"          # user embedding as planes only (N = 2, trainer's step)
-        self.head_side = os.environ.get("SEGMM_HEAD_SIDE", "1") != "0"
-        self.input_planes_only = os.environ.get("SEGMM_INPUT_PLANES_ONLY", "1") != "0"
-        self.attn_two_streams = os.environ.get("SEGMM_ATTN_TWO_STREAMS", "0") == "1"
-        # attention backward as D-kernel, then dQ (third stream) next to dK/dV (main stream).  Measured (same box, alternating
-        # runs): 80.3 k -> 79.6 k interactions/s, the union of the attention intervals unchanged at 1.10-1.14 ms/step -- the two
-        # kernels share the same vector-memory pipeline and simply slow each other down.  OFF by default.
-        self.attn_split = os.environ.get("SEGMM_ATTN_SPLIT", "0") != "0"
-        self.attn_fused = os.environ.get("SEGMM_ATTN_FUSED", "1") != "0"      # fused dQ+dK+dV kernel (<= 12 key tiles per block)
-        self._attn_stream = None
-        # forward: user-token chain (input Linear -> LayerNorm -> fused user projection) on the side stream next to the
-        # video-token chain.  On-the-fly engines: -0.3 % (off); plane engine (one workgroup per CU: the tail of one kernel and the
-        # HBM-bound LayerNorms fill under the other chain's GEMMs): +1.2 %, same-box alternating runs (on)
-        self.fwd_side = os.environ.get("SEGMM_FWD_SIDE", "1" if H.GEMM_ENGINE == H.ENGINE_F16X3P else "0") != "0"
-        # full layers (N >= 3): the user-token chain of a layer (attention with user queries -> ff -> LayerNorm -> MLP -> LayerNorm,
-        # and its backward) is independent of the video-token chain between the fused projections and the next layer: it runs on
-        # the side stream.  At config 3 its GEMMs have M = 1024 rows (4 - 12 tiles on 256 CUs) and used to sit on the main stream
-        # between the video side's kernels.
-        self.usr_side = os.environ.get("SEGMM_USR_SIDE", "1") != "0"
-        self.ln_side = self._ln_side_env not in ("0", "auto")          # (see defer_wgrad above)
-        # pre-split bf16 planes of the weights for the bf16x6 GEMM engine: W planes (forward) and W^T planes (dgrad
-        # in the NT form), refreshed when the parameters change (one split pass per optimizer step)
-        # (fp16x3 engine: two fp16 planes scaled by one power of two derived from ``wamax``, the partial maxima of
-        # |parameters|, which the GEMMs also need for weights they read as fp32)
+        # ---- switches (switches.py lists them; read here, when the store is constructed)
+        sw = switches.read("engine")
+        self.overlap, self.lazy_head_grad, self.head_dot = sw["overlap"], sw["lazy_head_grad"], sw["head_dot"]
+        self.side_priority = sw["side_priority"]
+        # auto | 0 | 1 as None | False | True; ``defer_wgrad`` / ``ln_side`` are what is in force (auto: BackboneRun.backward decides)
+        self.defer_wgrad_forced, self.ln_side_forced = sw["defer_wgrad"], sw["ln_side"]
+        self.defer_wgrad, self.ln_side = bool(self.defer_wgrad_forced), bool(self.ln_side_forced)
+        self.attn_planes_only, self.attn_pl = sw["attn_planes_only"], sw["attn_pl"]
+        self.eu_planes_only, self.input_planes_only = sw["eu_planes_only"], sw["input_planes_only"]
+        self.scaling, self.scale_target, self.loss_relative = sw["scaling"], sw["scale_target"], sw["loss_relative"]
+        self.wgrad_planes, self.gemm_bn = sw["wgrad_planes"], sw["gemm_bn"]
+        self.split_target, self.split_target_p, self.split_target_few = sw["split_target"], sw["split_target_p"], sw["split_target_few"]
+        # ---- GEMM engine
         self.engine_p = H.GEMM_ENGINE == H.ENGINE_F16X3P      # plane-operand GEMMs (gemm_planes.h); implies the fp16x3 arithmetic
         self.engine_h = H.GEMM_ENGINE in (H.ENGINE_F16X3, H.ENGINE_F16X3P)
-        self.use_planes = H.GEMM_ENGINE in (H.ENGINE_BF16X6, H.ENGINE_F16X3) and os.environ.get("SEGMM_PLANES", "1") != "0"
+        # bf16x6 / on-the-fly f16x3: pre-split planes of the weights, W (forward) and W^T (dgrad in the NT form), refreshed when the
+        # parameters change; f16x3: two fp16 planes scaled by one power of two from ``wamax``, the partial maxima of |parameters|
+        self.use_planes = H.GEMM_ENGINE in (H.ENGINE_BF16X6, H.ENGINE_F16X3) and sw["planes"]
         self.wamax = None
+        self.wplanes = self.wTplanes = None
         # engine_p: P32 planes of every weight matrix a GEMM reads (W: forward operand; W^T: the input-gradient GEMM in NT form),
         # one site header per matrix (own scale: LayerNorm gammas and biases are not part of any of them)
         self.wpt: Dict[str, "H.PT"] = {}
         self.wTpt: Dict[str, "H.PT"] = {}
         self._wmats: List[Tuple[str, int, int, int, bool]] = []      # (first parameter name, flat offset, rows, cols, needs W^T)
+        self.whdr = None
+        self.wpl = self.wTpl = None
         # delayed scaling of producer-written planes (common.h PlaneOut): one persistent scale per tensor SITE (a named
         # activation / gradient of the model), refreshed at the end of every pass from the maxima that pass recorded
         # (segmm_scales_update); a site is "calibrated" once it has been produced at least once
-        self.scaling = os.environ.get("SEGMM_SCALING", "delayed")      # delayed | exact (split pass after every producer) | always
-        # the scale puts the maxima of the LAST pass at 2^target, in the middle of the window the consumers accept
-        # (gemm_planes.h site_planes_ok: 2^-2 <= max * s < 2^16): 7 = 256x of headroom before an element overflows fp16 and
-        # 512x before the lo terms of a SHRUNKEN tensor sink into the subnormals; outside the window the consuming GEMM takes
-        # its fp32 fallback.  The attention-backward gradients of a nearly converged BPR model jump up to 45x from one batch to
-        # the next (tools/overflow_sites.py; target 12 = 16x headroom took the fallback 38 times in 400 steps).
-        self.scale_target = int(os.environ.get("SEGMM_SCALE_TARGET", "7"))
-        # backward sites: scale predicted from the site's recorded gain x THIS step's max |d loss / d logits| (they are linear in it)
-        self.loss_relative = os.environ.get("SEGMM_LOSS_RELATIVE", "1") != "0"
         self.site_index: Dict[str, int] = {}
         self.site_scale = None          # [MAX_SITES + 8] floats: scales, then [MAX_SITES] = count of overflowed tensors
         self.calibrated = set()
         self._site_idx_cache: Dict[tuple, torch.Tensor] = {}
-        self.whdr = None
-        self.wpl = self.wTpl = None
-        self.wgrad_planes = 2 if os.environ.get("SEGMM_WGRAD", "x6") == "x3" else 3      # x3 = opt-in, see DESIGN.md
-        self.wplanes = self.wTplanes = None
         self.fused_version = 0
         self._planes_key = None
         self._transposes: List[Tuple[int, int, int]] = []
@@ -388,31 +349,25 @@ class ParamStore:
     # slower than the same model alone (49.5 k -> 43.6 k interactions/s on the fp32 engine).
     _shared_streams = {}
 
-    @classmethod
-    def _shared_stream(cls, device, kind):
-        key = (str(device), kind)
-        s = cls._shared_streams.get(key)
+    def _shared_stream(self, kind):
+        key = (str(self.flat.device), kind)
+        s = self._shared_streams.get(key)
         if s is None:
-            # LOWEST priority: the side stream's weight-gradient GEMMs fill idle CUs, they must not starve the main
+            # LOWEST priority by default: the side stream's weight-gradient GEMMs fill idle CUs, they must not starve the main
             # stream's kernels (a 49 us LayerNorm backward was seen taking 470 us next to a same-priority GEMM)
-            s = cls._shared_streams[key] = torch.cuda.Stream(device=device, priority=int(os.environ.get("SEGMM_SIDE_PRIORITY", "1")))
+            s = self._shared_streams[key] = torch.cuda.Stream(device=self.flat.device, priority=self.side_priority)
         return s
 
     def side_stream(self):
         if self._side_stream is None or self._side_stream.device != self.flat.device:
-            self._side_stream = self._shared_stream(self.flat.device, "side")
+            self._side_stream = self._shared_stream("side")
         return self._side_stream
 
     def aux_stream(self):
         a = self.__dict__.get("_aux_stream")
         if a is None or a.device != self.flat.device:
-            a = self._aux_stream = self._shared_stream(self.flat.device, "aux")
+            a = self._aux_stream = self._shared_stream("aux")
         return a
-
-    def attn_stream(self):
-        if self._attn_stream is None or self._attn_stream.device != self.flat.device:
-            self._attn_stream = torch.cuda.Stream(device=self.flat.device)
-        return self._attn_stream
 
     # -- layout
     def _layout(self):
@@ -637,33 +592,23 @@ def _empty(ref, *shape, dtype=torch.float32):
     return torch.empty(shape, dtype=dtype, device=ref.device)
 
 
-_SPLIT_TARGET = int(os.environ.get("SEGMM_SPLIT_TARGET", "1024"))     # workgroups a split-K weight gradient aims for
-
-
-_BN_ENV = os.environ.get("SEGMM_GEMM_BN", "")
-
-
-def _splits_for(M, N, K):
-    """Split-K factor of a weight-gradient GEMM (TN); mirrors the tile-width choice of segmm_gemm_h (capi.hip)."""
-    wide = (H.GEMM_ENGINE == H.ENGINE_F16X3 and N > 128 and _BN_ENV != "128"
-            and (_BN_ENV == "256" or ((M + 127) // 128) * ((N + 255) // 256) >= 36))
+def _splits_for(M, N, K, target, bn=""):
+    """Split-K factor of a weight-gradient GEMM (TN) that aims for ``target`` workgroups; mirrors the tile-width choice of
+    segmm_gemm_h (capi.hip; ``bn``: the width forced by SEGMM_GEMM_BN)."""
+    wide = (H.GEMM_ENGINE == H.ENGINE_F16X3 and N > 128 and bn != "128"
+            and (bn == "256" or ((M + 127) // 128) * ((N + 255) // 256) >= 36))
     bn = 256 if wide else 128
     tiles = ((M + 127) // 128) * ((N + bn - 1) // bn)
     ktiles = (K + 31) // 32
-    return max(1, min(32, ktiles, (_SPLIT_TARGET + tiles - 1) // tiles))
+    return max(1, min(32, ktiles, (target + tiles - 1) // tiles))
 
 
-_SPLIT_TARGET_P = int(os.environ.get("SEGMM_SPLIT_TARGET_P", "256"))     # workgroups a plane-operand weight gradient aims for
-
-
-_SPLIT_TARGET_FEW = int(os.environ.get("SEGMM_SPLIT_TARGET_FEW", "256"))     # ... of the few-tile matrices that take gemm_pl_tn4 (capi.hip: <= 9 tiles, width >= 768)
-
-
-def _splits_for_p(M, N, K):
-    """Split-K factor of a plane-operand weight-gradient GEMM (256 x 256 tiles, one workgroup per CU): fill the 256 CUs once."""
+def _splits_for_p(M, N, K, target, target_few):
+    """Split-K factor of a plane-operand weight-gradient GEMM (256 x 256 tiles, one workgroup per CU): fill the 256 CUs once.
+    ``target_few``: the target of the few-tile matrices that take gemm_pl_tn4 (capi.hip: <= 9 tiles, width >= 768)."""
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     ktiles = (K + 31) // 32
-    target = _SPLIT_TARGET_FEW if (tiles <= 9 and M >= 768 and N >= 768) else _SPLIT_TARGET_P
+    target = target_few if (tiles <= 9 and M >= 768 and N >= 768) else target
     return max(1, min(64, ktiles, target // tiles if tiles <= target else 1))
 
 
@@ -829,8 +774,8 @@ def _needs_f32(act, what):
     """A launch is about to read ``act.t``: refuse if its producers wrote planes only (engine._layer_bwd, planes-only protocol)."""
     if getattr(act, "no_f32", False):
         raise RuntimeError("%s reads the fp32 copy of an operand whose producers wrote planes only (attention gradients: set "
-                           "SEGMM_ATTN_PLANES_ONLY=0; L1-normalised input features: SEGMM_INPUT_PLANES_ONLY=0 -- needed together with "
-                           "SEGMM_FEW_TILES / a non-plane GEMM engine)" % what)
+                           "SEGMM_ATTN_PLANES_ONLY=0; L1-normalised input features: SEGMM_INPUT_PLANES_ONLY=0 -- needed for operands "
+                           "a plane GEMM cannot take)" % what)
 
 
 def _wgrad(store, dY, y_off, X, x_off, Mrows, n_out, n_in, gW, accumulate=False, gb=None):
@@ -838,7 +783,7 @@ def _wgrad(store, dY, y_off, X, x_off, Mrows, n_out, n_in, gW, accumulate=False,
     ``gb``: the bias gradient [n_out] = column sums of the same dY columns -- formed inside the weight-gradient kernel on the
     plane engine (one more MFMA pair per k-step in a third of the workgroups), by a column-sum pass otherwise."""
     if store.engine_p and dY.planes is not None and X.planes is not None and n_out % 32 == 0 and n_in % 32 == 0:
-        splits = _splits_for_p(n_out, n_in, Mrows)
+        splits = _splits_for_p(n_out, n_in, Mrows, store.split_target_p, store.split_target_few)
         ws = store.buf("splitk_ws_side" if store._on_side else "splitk_ws", (max(splits, 1) * (n_out * n_in + n_out),)) if splits > 1 else None
         H.gemm_p(H.LAYOUT_TN, n_out, n_in, Mrows, dY.pt(y_off, n_out), X.pt(x_off, n_in), gW, n_in, splits=splits, workspace=ws,
                  accumulate=accumulate, colsum_out=gb)
@@ -847,38 +792,23 @@ def _wgrad(store, dY, y_off, X, x_off, Mrows, n_out, n_in, gW, accumulate=False,
     _needs_f32(X, "the on-the-fly weight-gradient GEMM")
     if gb is not None:
         _colsum(store, dY.t, dY.cols, Mrows, n_out, gb, x_off=y_off, accumulate=accumulate)
-    splits = _splits_for(n_out, n_in, Mrows)
+    splits = _splits_for(n_out, n_in, Mrows, store.split_target, store.gemm_bn)
     ws = store.buf("splitk_ws_side" if store._on_side else "splitk_ws", (max(splits, 1) * n_out * n_in,)) if splits > 1 else None
     H.gemm(H.LAYOUT_TN, n_out, n_in, Mrows, dY.t, dY.cols, X.t, X.cols, gW, n_in, splits=splits, workspace=ws,
            accumulate=accumulate, a_off=y_off, b_off=x_off, nplanes=store.wgrad_planes if H.GEMM_ENGINE == H.ENGINE_BF16X6 else 3,
            a_amax=dY.slots, b_amax=X.slots)
 
 
-# Launches with fewer 256 x 256 output tiles than this go to the 128 x 128 on-the-fly kernel.  Round 2: 48 (the plane kernel
-# had one tile shape and left most CUs idle).  Round 3: 0 -- gemm_pl_nt8 picks 256 x 128 tiles for such launches and is faster
-# on every config-3 shape (user-side GEMMs with M = 1024: 44-189 us -> 37-111 us; 160.0 -> 168.6 k interactions/s)
-_FEW_TILES = int(os.environ.get("SEGMM_FEW_TILES", "0"))
-
-
-def _few_tiles(M, N):
-    return ((M + 255) // 256) * ((N + 255) // 256) < _FEW_TILES
-
-
 def _lin_fwd(store, M, N, K, X, wname, out, ldo, c_act=None, **kw):
     """out[M,N] = X[M,K] . W[N,K]^T (+ epilogue); X: Act; W = the parameter (or fused group starting at) ``wname``;
     ``c_act``: the Act that ``out`` belongs to (receives the partial maxima of |out|)."""
     w = store.wpt.get(wname) if store.engine_p else None
-    if not (w is not None and X.planes is not None and not _few_tiles(M, N)):
+    plane = w is not None and X.planes is not None
+    if not plane:
         _needs_f32(X, "the on-the-fly forward GEMM")
-    if w is not None and X.planes is not None and _few_tiles(M, N):
-        # a handful of 256 x 256 tiles would leave most of the 256 CUs idle (config 3: 1024 user tokens): the 128 x 128
-        # on-the-fly kernel has 4x the workgroups; it takes the fp32 operands and the same partial maxima
-        H.gemm(H.LAYOUT_NT, M, N, K, X.t, K, store.p(wname), K, out, ldo, a_amax=X.slots, b_amax=w.hdr[H.SITE_HDR:],
-               c_amax=None if c_act is None else c_act.slots, **kw)
-        return
-    if out is None and not (w is not None and X.planes is not None and not _few_tiles(M, N) and c_act is not None and c_act.po is not None):
+    if out is None and not (plane and c_act is not None and c_act.po is not None):
         raise RuntimeError("a planes-only output needs the plane GEMM with a calibrated output site (%s)" % wname)
-    if w is not None and X.planes is not None:
+    if plane:
         if c_act is not None and c_act.po is not None:
             H.gemm_p(H.LAYOUT_NT, M, N, K, X.pt(), w, out, ldo, c_pt=c_act.pt(), c_scale_ptr=c_act.scale_ptr, write_c=out is not None, **kw)
             if out is None:
@@ -900,12 +830,6 @@ def _lin_dgrad(store, M, n_in, n_out, dY, wname, out, c_act=None, **kw):
     """out[M,n_in] = dY[M,n_out] . W[n_out,n_in] (+ epilogue); dY: Act.  With W^T planes this is the NT form (both operands
     k-contiguous), otherwise the NN layout on the fp32 weights."""
     wT = store.wTpt.get(wname) if store.engine_p else None
-    if not (wT is not None and dY.planes is not None and not _few_tiles(M, n_in)):
-        _needs_f32(dY, "the on-the-fly input-gradient GEMM")
-    if wT is not None and dY.planes is not None and _few_tiles(M, n_in):
-        H.gemm(H.LAYOUT_NN, M, n_in, n_out, dY.t, n_out, store.p(wname), n_in, out, n_in, a_amax=dY.slots, b_amax=wT.hdr[H.SITE_HDR:],
-               c_amax=None if c_act is None else c_act.slots, **kw)
-        return
     if wT is not None and dY.planes is not None:
         if c_act is not None and c_act.po is not None:
             H.gemm_p(H.LAYOUT_NT, M, n_in, n_out, dY.pt(), wT, out, n_in, c_pt=c_act.pt(), c_scale_ptr=c_act.scale_ptr, **kw)
@@ -913,6 +837,7 @@ def _lin_dgrad(store, M, n_in, n_out, dY, wname, out, c_act=None, **kw):
         else:
             H.gemm_p(H.LAYOUT_NT, M, n_in, n_out, dY.pt(), wT, out, n_in, c_hdr=None if c_act is None else c_act.hdr, **kw)
         return
+    _needs_f32(dY, "the on-the-fly input-gradient GEMM")
     ca = None if c_act is None else c_act.slots
     if store.use_planes and n_out % 8 == 0:
         H.gemm(H.LAYOUT_NT, M, n_in, n_out, dY.t, n_out, None, n_out, out, n_in, b_planes=(store.wTplanes, store.index[wname][0]),
@@ -936,10 +861,9 @@ def _ln_bwd(store, dy, x, mean, rstd, gname, bname, gbuf, dx, dx_drop, rows, d, 
     it leaves are returned ([4 * parts, d], partial row p = position p mod L; None when no such grid exists) -- the
     positional-embedding gradient then is a sum over ~40 partial rows per position instead of a pass over dx."""
     # (worth it when the second pass it saves is long: short sequences / small tensors keep the plain column sum)
-    pparts = H.layernorm_bwd_pos_parts(rows, pos_period, d) if (pos_period >= 8 and store.ln_pos and rows * d >= (1 << 23)) else 0
+    pparts = H.layernorm_bwd_pos_parts(rows, pos_period, d) if (pos_period >= 8 and rows * d >= (1 << 23)) else 0
     parts = pparts if pparts > 0 else H.layernorm_bwd_parts(rows, d)
-    # partial buffers named after the parameter so that their reductions MAY run on the side stream (SEGMM_LN_SIDE=1;
-    # measured 2 % slower than keeping these tiny launches on the main stream, so off by default)
+    # partial buffers named after the parameter: their reductions may run on the side stream (store.ln_side)
     pg = store.buf("ln_pg:" + gname, (parts, d))
     pb = store.buf("ln_pb:" + gname, (parts, d))
     ps = store.buf("ln_ps:" + gname, (parts, d)) if dsum_to is not None else None
@@ -961,43 +885,6 @@ def _ln_bwd(store, dy, x, mean, rstd, gname, bname, gbuf, dx, dx_drop, rows, d, 
         Xs = [pg, pb] + ([ps] if ps is not None else [])
         H.colsum3(Xs, d, parts, d, outs, ws)          # one launch pair instead of three
     return pp
-
-
-def _attn_bwd(store, *args, **kw):
-    """Attention backward.  SEGMM_ATTN_SPLIT=1: Dvec = rowsum(dO * O) first (one small kernel), then the dQ kernel on a third
-    stream CONCURRENTLY with the dK/dV kernel on the main stream (no gain measured, see ParamStore.attn_split).  The
-    partial-maxima slots they share are integer atomic maxima (order-independent), the outputs are disjoint column blocks."""
-    B_, H_, dh_, Lq_, La_, Lb_ = args[:6]
-    if store.attn_fused and max((La_ + 15) // 16, (Lb_ + 15) // 16) <= 12:
-        # dQ + dK + dV in ONE kernel per key block: one workgroup per (b, h, block) with the query side staged in LDS and
-        # D = rowsum(dO * O) formed during the staging (attention.h: attn_bwd_fused_kernel); 848 -> ~540 us at config 2
-        pl = kw.get("planes")
-        if store.attn_two_streams and store.overlap and La_ > 0 and Lb_ > 0 and not (pl is not None and (pl.flags & H.ATTN_REPAIR)):
-            # the two key blocks' launches are independent (disjoint outputs; shared maxima slots are integer atomic maxima):
-            # block a (the shorter one at config 2) on the side stream, block b on the main stream
-            with side_work(store):
-                H.attn_bwd(*args, phase=5, **kw)
-            H.attn_bwd(*args, phase=6, **kw)
-            join_side(store)
-            return
-        H.attn_bwd(*args, phase=4, **kw)
-        return
-    if not (store.overlap and store.attn_split):
-        H.attn_bwd(*args, **kw)
-        return
-    H.attn_bwd(*args, phase=1, **kw)
-    main, att = torch.cuda.current_stream(), store.attn_stream()
-    ev = torch.cuda.Event()
-    ev.record(main)
-    att.wait_event(ev)
-    with torch.cuda.stream(att):
-        H.attn_bwd(*args, phase=2, **kw)
-    H.attn_bwd(*args, phase=3, **kw)
-    main.wait_stream(att)
-
-
-def vq_tiles(L):
-    return (L + 15) // 16
 
 
 def _mask_u8(m: torch.Tensor) -> torch.Tensor:
@@ -1109,27 +996,26 @@ class BackboneRun:
         use_pe = bool(getattr(bb, "use_pe", 1))          # --use_pe 0: no positional-embedding add (encoder.py:450-471)
         usr_is_operand = (layered and self.mode != "self") or self.abl == "CrossMLP"      # does any GEMM read the user embedding?
         # ---- embedding (encoder.py:425-473).  The user-token chain (input Linear -> LayerNorm -> the first layer's fused
-        # user-token projection) and the video-token chain are independent until the first attention: with SEGMM_FWD_SIDE=1
-        # the user chain is enqueued on the side stream.  Measured on one box, alternating runs: 83.8 k -> 83.6 k
-        # interactions/s -- the GEMMs of both chains share the same power-limited matrix pipes, so the knob is OFF by default.
-        # Every buffer is allocated HERE, on the main stream (the caching allocator must never hand a side-stream block to
-        # the next step while main-stream kernels of this step still read it).
+        # user-token projection) and the video-token chain are independent until the first attention: on the plane engine (one
+        # workgroup per CU: one chain's kernel tails and HBM-bound LayerNorms fill under the other chain's GEMMs) the user chain
+        # is enqueued on the side stream.  Every buffer is allocated HERE, on the main stream (the caching allocator must never
+        # hand a side-stream block to the next step while main-stream kernels of this step still read it).
         H.mark(H.PHASE_EMBED_FWD, self.bi)
         pre_u = _empty(ref, Mu, d)
         meu, reu = _empty(ref, Mu), _empty(ref, Mu)
-        # The user embedding as PLANES ONLY (round 5): in the trainer's own step of a model whose first layer is not full (N = 2:
+        # The user embedding as PLANES ONLY: in the trainer's own step of a model whose first layer is not full (N = 2:
         # BASELINE configs 2 / 4 / 5) nothing reads its fp32 values -- it is the operand of the fused user projection and of that
         # projection's weight gradient -- so the LayerNorm writes the planes alone, with the scale of its output bound (no history,
         # no overflow, no repair: segmm_layernorm_fwd with y = NULL), 157 MB less on the chain that bounds the forward
         eu_po = bool(self.delayed and st.eu_planes_only and st.__dict__.get("_trusted") and not bb.id_usr and layered and self.N == 2 and
-                     self.mode != "self" and d % 32 == 0 and _FEW_TILES == 0)
+                     self.mode != "self" and d % 32 == 0)
         if eu_po:
             Eu = Act(None, am.new(P + "Eu"), Mu, d, torch.empty((Mu, 2 * d), dtype=torch.float16, device=st.flat.device))
             Eu.po, Eu.no_f32 = H.PO(Eu.planes, 2 * d, Eu.hdr, None), True
         else:
             Eu = new_act(st, am, Mu, d, planes=usr_is_operand, site=P + "Eu", delayed=self.delayed)
         Yu0 = None
-        fwd_side = st.overlap and st.fwd_side and not bb.id_usr and layered and self.mode != "self"
+        fwd_side = st.overlap and st.engine_p and not bb.id_usr and layered and self.mode != "self"
         if bb.id_usr:
             uids = _as(usr_feat, torch.int64, "the user ids")
             sv["usr_ids"] = uids
@@ -1321,8 +1207,7 @@ class BackboneRun:
         (12 key tiles), lengths % 4, knob ATT_FWD_PL.  A layer whose projection outputs exist as planes ONLY cannot fall back to the
         fp32-operand kernels, so a single refused call keeps the fp32 buffers for the whole pass (SEGMM_ATT_PL=0: never)."""
         st = self.store
-        if not (self.delayed and st.engine_p and st.attn_pl and st.attn_fused and self.dh % 16 == 0 and self.dh <= 48 and
-                self.d % 32 == 0 and _FEW_TILES == 0):
+        if not (self.delayed and st.engine_p and st.attn_pl and self.dh % 16 == 0 and self.dh <= 48 and self.d % 32 == 0):
             return False
         if H.knob("ATT_FWD_PL") == 0:
             return False
@@ -1399,7 +1284,6 @@ class BackboneRun:
         if (Yv is None or (nu and Yu is None)) and (pin_v is None or (full and pin_u is None)):
             raise RuntimeError("planes-only projection outputs without input planes for every attention call of the layer")
         X2u = None
-        usr_ctx = None
         if full:
             # the user-token chain: every buffer allocated here, on the main stream, then the launches on the side stream
             lse_u = _empty(Xv.t, 2, B, Hh, Lt)
@@ -1412,10 +1296,9 @@ class BackboneRun:
                            seed=self.seed, site=_site(self.bi, i, K_ATT_U), amax_o=Au.slots, po=Au.po, pin=pin_u)
                 finish_act(st, produced(Au))
                 return self._side_post(i, L, "usr", Xu, Au, Mu, (K_AO_U, K_MI_U, K_MO_U), out_is_operand=True, bufs=bufs_u)
-            if st.usr_side and st.overlap:
+            if st.overlap:
                 with side_work(st):          # (both fused projections are enqueued on the main stream: the fork orders the chain behind them)
                     X2u, sv_u = usr_chain()
-                usr_ctx = True
         H.attn_fwd(B, Hh, dh, S, vq["La"], vq["Lb"], vq["Qa"], vq["Qb"], vq["ldq"], vq["Ka"], vq["Va"], vq["ldka"], vq["Kb"], vq["Vb"],
                    vq["ldkb"], self.vm, self.vm, self.um, Av.t, d, lse_v, drop_p=self.p_drop, seed=self.seed,
                    site=_site(self.bi, i, K_ATT_V), amax_o=Av.slots, po=Av.po, pin=pin_v)
@@ -1424,7 +1307,7 @@ class BackboneRun:
         X2v, sv_v = self._side_post(i, L, "vid", Xv, Av, Mv, (K_AO_V, K_MI_V, K_MO_V), out_is_operand=i < self.N - 2, head_dot=hd)
         rec["v"] = sv_v
         if full:
-            if usr_ctx:
+            if st.overlap:
                 join_side(st)          # the next layer's projections (main stream) read the user chain's output
             else:
                 X2u, sv_u = usr_chain()
@@ -1484,11 +1367,9 @@ class BackboneRun:
         L = "%sencoder.layers.%d." % (P, i)
         ca = L + "cross_attn."
         Yv, Yu = rec["Yv"], rec["Yu"]
-        # one site per fused dY buffer: both attentions fold into it.  Only the fused backward kernel writes planes itself.
-        fused = st.attn_fused and max((vq_tiles(S), vq_tiles(Lt))) <= 12
-        dly = self.delayed and fused
-        dYv = new_act(st, self.amb, Mv, nv * d, key="dYv%d" % i, site="%sdYv%d" % (P, i), delayed=dly)
-        dYu = new_act(st, self.amb, Mu, nu * d, key="dYu%d" % i, site="%sdYu%d" % (P, i), delayed=dly) if nu else None
+        # one site per fused dY buffer: both attentions fold into it; the fused backward kernel writes its planes itself
+        dYv = new_act(st, self.amb, Mv, nv * d, key="dYv%d" % i, site="%sdYv%d" % (P, i), delayed=self.delayed)
+        dYu = new_act(st, self.amb, Mu, nu * d, key="dYu%d" % i, site="%sdYu%d" % (P, i), delayed=self.delayed) if nu else None
         vq, uq = self._attn_views(full, Yv, Yu, nv, nu)
         dvq, duq = self._attn_views(full, dYv.t, dYu.t if nu else None, nv, nu)
         Dv = st.buf("attnD", (B * Hh * max(S, Lt),))
@@ -1499,12 +1380,12 @@ class BackboneRun:
         # the producers (leaves at once unless a site's planes are unusable) and the consumers get no fp32 fallback.
         # (short query sides -- config 3: 20 and 1 queries -- keep the copies: the tensors are small and the extra launches of the
         # repair pass cost as much as the stores they save; SEGMM_ATTN_PLANES_ONLY=2 forces the protocol for every shape)
-        ponly = dly and st.attn_planes_only and dYv.po is not None and (not nu or dYu.po is not None) and \
+        ponly = self.delayed and st.attn_planes_only and dYv.po is not None and (not nu or dYu.po is not None) and \
             (S > 32 or st.attn_planes_only > 1)
 
         def planes_of(dq, dka_, dkb_, views, pflags=0):
             """segmm_attn_planes_t for one fused-backward call: query-side buffer dq, key-block buffers dka_ / dkb_ (Acts)."""
-            if not dly or dq.po is None:
+            if not self.delayed or dq.po is None:
                 return None
             pl = H.AttnPlanes()
 
@@ -1523,7 +1404,7 @@ class BackboneRun:
         deferred = [] if st.defer_wgrad else None
         attn_u = None
         dR1u = None
-        usr_on_side = full and st.usr_side and st.overlap
+        usr_on_side = full and st.overlap
         if full:
             Dv_u = st.buf("attnD_u", (B * Hh * max(S, Lt),))
 
@@ -1532,11 +1413,11 @@ class BackboneRun:
                 flush_deferred(st, deferred)
 
                 def attn_u_(pflags):
-                    _attn_bwd(st, B, Hh, dh, Lt, uq["La"], uq["Lb"], uq["Qa"], uq["Qb"], uq["ldq"], uq["Ka"], uq["Va"], uq["ldka"], uq["Kb"],
+                    H.attn_bwd(B, Hh, dh, Lt, uq["La"], uq["Lb"], uq["Qa"], uq["Qb"], uq["ldq"], uq["Ka"], uq["Va"], uq["ldka"], uq["Kb"],
                                uq["Vb"], uq["ldkb"], self.um, self.vm, self.um, rec["lse_u"], rec["u"]["A"].t, d, dAu, d, Dv_u,
                                duq["Qa"], duq["Qb"], duq["ldq"], duq["Ka"], duq["Va"], duq["ldka"], duq["Kb"], duq["Vb"], duq["ldkb"],
                                drop_p=self.p_drop, seed=self.seed, site=_site(self.bi, i, K_ATT_U),
-                               amax_q=sl_u, amax_ka=sl_v, amax_kb=sl_u, planes=planes_of(dYu, dYv, dYu, duq, pflags), pin=rec.get("pin_u"))
+                               amax_q=sl_u, amax_ka=sl_v, amax_kb=sl_u, phase=4, planes=planes_of(dYu, dYv, dYu, duq, pflags), pin=rec.get("pin_u"))
                 attn_u_(H.ATTN_PLANES_ONLY if ponly else 0)
                 return dR1u_, attn_u_
             if usr_on_side:
@@ -1548,10 +1429,10 @@ class BackboneRun:
         dR1v, dAv = self._side_post_bwd(i, L, "vid", rec["v"], dXv_out, Mv, (K_AO_V, K_MI_V, K_MO_V), gbuf, "v%d" % i, deferred)
         flush_deferred(st, deferred)          # the three weight-gradient GEMMs of this side run under the attention backward
         def attn_v(pflags):
-            _attn_bwd(st, B, Hh, dh, S, vq["La"], vq["Lb"], vq["Qa"], vq["Qb"], vq["ldq"], vq["Ka"], vq["Va"], vq["ldka"], vq["Kb"], vq["Vb"],
+            H.attn_bwd(B, Hh, dh, S, vq["La"], vq["Lb"], vq["Qa"], vq["Qb"], vq["ldq"], vq["Ka"], vq["Va"], vq["ldka"], vq["Kb"], vq["Vb"],
                        vq["ldkb"], self.vm, self.vm, self.um, rec["lse_v"], rec["v"]["A"].t, d, dAv, d, Dv, dvq["Qa"], dvq["Qb"], dvq["ldq"],
                        dvq["Ka"], dvq["Va"], dvq["ldka"], dvq["Kb"], dvq["Vb"], dvq["ldkb"], drop_p=self.p_drop, seed=self.seed,
-                       site=_site(self.bi, i, K_ATT_V), amax_q=sl_v, amax_ka=sl_v, amax_kb=sl_u,
+                       site=_site(self.bi, i, K_ATT_V), amax_q=sl_v, amax_ka=sl_v, amax_kb=sl_u, phase=4,
                        planes=planes_of(dYv, dYv, dYu, dvq, pflags), pin=rec.get("pin_v"))
         attn_v(H.ATTN_PLANES_ONLY if ponly else 0)
         if full:
@@ -1568,7 +1449,7 @@ class BackboneRun:
             dYv.no_f32 = dYv.po is not None
             if nu:
                 dYu.no_f32 = dYu.po is not None
-        if dly:          # every column block of a dY buffer must have been written WITH planes, else fall back to the split pass
+        if self.delayed:          # every column block of a dY buffer must have been written WITH planes, else fall back to the split pass
             produced(dYv)
             if nu:
                 produced(dYu)
@@ -1611,9 +1492,9 @@ class BackboneRun:
                 H.rowscale_bcast(lazy[1], lazy[2], dXv, d, dXv.shape[0], d)
             else:
                 self._lazy_dy = lazy
-        if st._defer_wgrad_env == "auto":          # (plane engine only: on the exact-fp32 engine the deferral costs 1.5 %)
+        if st.defer_wgrad_forced is None:          # auto (plane engine only: on the exact-fp32 engine the deferral costs 1.5 %)
             st.defer_wgrad = S > 32 and st.engine_p
-        if st._ln_side_env == "auto":
+        if st.ln_side_forced is None:
             st.ln_side = S > 32 and st.engine_p
         self.amb = AmaxArena(st, 4 + 8 * max(self.N - 1, 0) + 2 * (self.n_mlp + 2))
         if self.abl in MLP_VARIANTS:
@@ -1728,7 +1609,7 @@ class BackboneRun:
             # The backward ends with the side stream still working through the big projection weight gradients while the
             # main stream runs dry: the video-side embedding weight gradient (the main stream's last GEMM-sized job
             # before the user side) therefore runs on the MAIN stream, the user-side one on the side stream.
-            ctx = contextlib.nullcontext() if (side == "vid" and st.tail_balance) else side_work(st)
+            ctx = contextlib.nullcontext() if side == "vid" else side_work(st)
             with ctx:
                 _wgrad(st, dpre_act, 0, x, 0, M, d, Din, gtab)
                 # bias gradient = sum over all tokens of dpre = sum over positions of the positional-embedding
@@ -1771,7 +1652,7 @@ def next_seed(store=None) -> int:
     if live is not None:
         return live
     s = int(torch.randint(0, 2 ** 62, (1,)).item())
-    rank = int(os.environ.get("RANK", "0"))
+    rank = switches.launcher_rank()
     return (s ^ (rank * 0x9E3779B97F4A7C15)) & (2 ** 62 - 1) if rank else s
 
 

@@ -29,6 +29,7 @@ import torch.nn as nn
 
 from . import engine as E
 from . import hipabi as H
+from . import switches
 from .decoder_leave_focal import MultiScaleTemporalDetrLeaveFocal
 from .encoder import SegFormerX
 
@@ -258,7 +259,7 @@ class DPComm:
         # every collective of the step is issued iff ``active``: more than one rank -- or SEGMM_DP_FORCE=1 with an initialised
         # process group of ONE rank, which sends the single-GPU step through the real RCCL calls (tests/test_dp_gpu.py: the
         # only way to execute the nccl code path on a one-GPU box; results must equal the plain step bit for bit)
-        self.active = self.world > 1 or (dist.is_initialized() and os.environ.get("SEGMM_DP_FORCE", "0") == "1")
+        self.active = self.world > 1 or (switches.read("comm")["force"] and dist.is_initialized())
         self.pending = []
         # gloo has no device collectives for every op: device tensors are staged through the host.
         # Only the test harness uses that (two ranks sharing one GPU); production is nccl = RCCL.
@@ -467,17 +468,17 @@ class Trainer:
         st.bucket_hook = self._on_bucket if self.comm.active else None
         # id mode under DP: the embedding tables' gradients travel as B rows per rank (DPComm.gather_rows) and their flat
         # ranges are cut out of the dense all-reduce; ``sparse_tables=False`` keeps the dense all-reduce (A/B, tests)
-        self.sparse_tables = bool(sparse_tables) and self.comm.active and os.environ.get("SEGMM_SPARSE_TABLES", "1") != "0"
+        sw = switches.read("trainer")
+        self.sparse_tables = bool(sparse_tables) and self.comm.active and sw["sparse_tables"]
         st.row_exchange = self.comm.gather_rows if self.sparse_tables else None
         if self.sparse_tables:
             # dist.new_group is COLLECTIVE over the default group: create the row-exchange group here, where every rank
             # constructs its Trainer, not lazily inside the first backward (ranks that skip the id-table path on
             # their first step, or a DPComm on a sub-group, would deadlock)
             self.comm._row_group()
-        self.per_bucket_adamw = os.environ.get("SEGMM_BUCKET_ADAMW", "1") != "0"
-        self.table_two_pass = os.environ.get("SEGMM_TABLE_TWO_PASS", "1") != "0"
-        self.begin_overlap = os.environ.get("SEGMM_BEGIN_OVERLAP", "1") != "0"          # head of the step on two streams (_features)
-        self.bucket_bytes = int(float(os.environ.get("SEGMM_DP_BUCKET_MB", "8")) * (1 << 20))      # merge threshold of _on_bucket
+        self.per_bucket_adamw, self.table_two_pass, self.begin_overlap = sw["per_bucket_adamw"], sw["table_two_pass"], sw["begin_overlap"]
+        self.bucket_bytes = int(sw["bucket_mb"] * (1 << 20))      # merge threshold of _on_bucket
+        self.side_priority = sw["side_priority"]
         self._bucket_works = []
         self._pending_range = None
         self._norm = {}
@@ -752,7 +753,7 @@ class Trainer:
             return
         main = torch.cuda.current_stream()
         if self._pf_stream is None:          # lowest priority, like the engine's side stream: it must not starve the step in flight
-            self._pf_stream = torch.cuda.Stream(device=st.flat.device, priority=int(os.environ.get("SEGMM_SIDE_PRIORITY", "1")))
+            self._pf_stream = torch.cuda.Stream(device=st.flat.device, priority=self.side_priority)
         rows = st.hdr_rows(2) if st.engine_h else None          # taken (and, at a ring quarter, cleared) in main-stream order
         ev = torch.cuda.Event()
         ev.record(main)                                            # behind this step's scales_update of the input sites

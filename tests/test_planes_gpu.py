@@ -917,7 +917,7 @@ def test_attention_backward_planes_only_repair_pass(factor):
         model = init_model(margs, n_users=1, n_items=1, input_dim=D, max_vid_len=S, max_usr_len=Lt).cuda()
         tr = Trainer(model, dropout=False, lr=0.0, weight_decay=0.0)          # lr 0: both twins keep identical parameters
         st = model._store
-        if not (st.engine_p and st.attn_planes_only and st.attn_fused):
+        if not (st.engine_p and st.attn_planes_only):
             pytest.skip("planes-only attention backward disabled")
         st.scaling = "always"          # delayed scales although dropout is off (deterministic twins)
         st.attn_planes_only = 2          # also for this test's short query side

@@ -103,9 +103,10 @@ def main():
             X = torch.randn(K, N, device=dev)
             pdy, px = H.to_planes(dY, K, M), H.to_planes(X, K, N)
             Cp, Cl = torch.empty(M, N, device=dev), torch.empty(M, N, device=dev)
-            from segmminterest_amd import engine as E
-            sp_l = E._splits_for(M, N, K)
-            sp_p = E._splits_for_p(M, N, K) if hasattr(E, "_splits_for_p") else sp_l
+            from segmminterest_amd import engine as E, switches
+            sw = switches.read("engine")
+            sp_l = E._splits_for(M, N, K, sw["split_target"], sw["gemm_bn"])
+            sp_p = E._splits_for_p(M, N, K, sw["split_target_p"], sw["split_target_few"])
             ws = torch.empty(max(sp_l, sp_p) * M * N, device=dev)
             try:
                 H.gemm_p(H.LAYOUT_TN, M, N, K, pdy, px, Cp, N, splits=sp_p, workspace=ws)

@@ -3,6 +3,8 @@ import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from segmminterest_amd import hipabi as H
 from segmminterest_amd import engine as E
+from segmminterest_amd import switches
+SW = switches.read("engine")
 lay, M, N, K = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 dev = torch.device("cuda")
 torch.manual_seed(0)
@@ -19,7 +21,7 @@ else:
     if ZERO:
         dY.zero_(); X.zero_()
     pa, pw = H.to_planes(dY, K, M), H.to_planes(X, K, N)
-    sp = E._splits_for_p(M, N, K)
+    sp = E._splits_for_p(M, N, K, SW["split_target_p"], SW["split_target_few"])
     ws = torch.empty(sp * M * N, device=dev)
     fn = lambda: H.gemm_p(H.LAYOUT_TN, M, N, K, pa, pw, C, N, splits=sp, workspace=ws)
 for _ in range(5):

@@ -10,6 +10,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from segmminterest_amd import engine as E          # noqa: E402
 from segmminterest_amd import hipabi as H          # noqa: E402
+from segmminterest_amd import switches          # noqa: E402
+
+SW = switches.read("engine")
 
 
 def timeit(fn, iters=30):
@@ -37,7 +40,7 @@ def main():
         pdy, px = H.to_planes(dY, K, M), H.to_planes(X, K, N)
         C = torch.empty(M, N, device=dev)
         ws = torch.empty(max(counts) * M * N, device=dev)
-        pick = E._splits_for_p(M, N, K)
+        pick = E._splits_for_p(M, N, K, SW["split_target_p"], SW["split_target_few"])
         cells = []
         for c in sorted(set(counts) | {pick}):
             if c > (K + 31) // 32:
