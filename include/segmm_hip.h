@@ -202,6 +202,11 @@ int segmm_colsum(const float* X, int ld, const float* w, int64_t M, int N, float
  * columns [h*dh, (h+1)*dh).  Masks are uint8 (torch.bool).  lse: [2, B, H, Lq] floats
  * (plane 0 = softmax row max, plane 1 = 1/row sum, written by the forward); Dvec: [B, H, Lq] floats.
  * One key block may be empty (La == 0 or Lb == 0, its pointers null): the CrossAtt / SelfAtt ablations.
+ * Sizes: Lq <= 256, La <= 256, Lb <= 256.  Up to 192 padded keys (each key block rounded up to a multiple of 16) every form
+ * below is available.  Beyond that the forward and phases 0-3 of the backward run on the streamed kernels (key tiles in a
+ * run-time loop, online softmax; fp32 views, plane OUTPUT of the forward still written); the fused phases 4-6 and input
+ * planes (*_in) are refused there.  Knob ATT_STREAM = 1 sends every fp32-view forward and every phase 0-3 backward to
+ * the streamed kernels at any size; with them phases 1 + 2 + 3 give the bits of phase 0.
  * segmm_attn_bwd phase: 0 = whole backward on `stream` (dQ kernel, which also writes Dvec, then dK/dV kernel);
  * 1 = Dvec = rowsum(dO * O) only; 2 = dQa/dQb only (Dvec not written); 3 = dKa/dVa/dKb/dVb only (reads Dvec) -- phases 2
  * and 3 are independent once phase 1 is complete and may run concurrently on two streams; 4 = dQ, dK and dV in ONE kernel

@@ -8,6 +8,7 @@
 #include "../../include/segmm_hip.h"
 #include "attention16.h"
 #include "attention_pl.h"
+#include "attention_stream.h"
 #include "common.h"
 #include "evalops.h"
 #include "gemm.h"
@@ -63,6 +64,7 @@ StepState* segmm_step_current() {
 
 using namespace segmm;
 
+static inline int attn_keys_p(int La, int Lb) { return ((La + 15) & ~15) + ((Lb + 15) & ~15); }          // both key blocks, each padded to whole tiles
 static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, const float* Qa, const float* Qb, int ldq,
                      const float* Ka, const float* Va, int ldka, const float* Kb, const float* Vb, int ldkb,
                      const uint8_t* mq, const uint8_t* mka, const uint8_t* mkb, float drop_p, uint64_t seed,
@@ -78,8 +80,9 @@ static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, 
     SEGMM_REQUIRE(dh == 4 || dh == 8 || dh == 16 || dh == 32 || dh == 48 || dh == 64, "attn: head dim %d not built (4,8,16,32,48,64)", dh);
     SEGMM_REQUIRE(ldq % 4 == 0 && ldka % 4 == 0 && ldkb % 4 == 0, "attn: leading dims %% 4");
     SEGMM_REQUIRE(aligned16(Qa) && aligned16(Qb) && aligned16(Ka) && aligned16(Va) && aligned16(Kb) && aligned16(Vb), "attn: alignment");
-    const int Tp = ((La + 15) & ~15) + ((Lb + 15) & ~15);
-    SEGMM_REQUIRE(Tp <= 16 * 12, "attn: %d padded keys > 192 not built", Tp);
+    // More than 192 padded keys (12 tiles) go to the streamed kernels (attention_stream.h), which take any tile count; the limit
+    // of 256 per axis is what the rest of the project is built and tested for (the segment axis of the loss and evaluation kernels)
+    SEGMM_REQUIRE(Lq <= 256 && La <= 256 && Lb <= 256, "attn: Lq=%d, La=%d, Lb=%d not built (at most 256 queries and 256 keys per key block)", Lq, La, Lb);
     a.B = B; a.H = H; a.Lq = Lq; a.La = La; a.Lb = Lb;
     a.Qa = Qa; a.Qb = Qb; a.ldq = ldq; a.Ka = Ka; a.Va = Va; a.ldka = ldka; a.Kb = Kb; a.Vb = Vb; a.ldkb = ldkb;
     a.mq = mq; a.mka = mka; a.mkb = mkb;
@@ -101,7 +104,7 @@ static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, 
 // launch path.  Knobs whose non-default values give WRONG results (timing probes) do not exist in this build: they are compiled
 // in by -DSEGMM_ATT_PROBE / -DSEGMM_GEMM_PROBE only.
 enum {
-    K_ATTN, K_ATT_FWD_PL, K_ATT_FWD_LDS, K_ATT_FWD_KSPLIT, K_ATT_FWD_LDS_PAD, K_ATT_FUSED_LAUNCH, K_ATT_MERGE, K_ATT_LDS_PAD, K_ATT_WAVES, K_ATT_WAVES_PL, K_ATT_REPAIR_WALK,
+    K_ATTN, K_ATT_FWD_PL, K_ATT_FWD_LDS, K_ATT_FWD_KSPLIT, K_ATT_FWD_LDS_PAD, K_ATT_STREAM, K_ATT_FUSED_LAUNCH, K_ATT_MERGE, K_ATT_LDS_PAD, K_ATT_WAVES, K_ATT_WAVES_PL, K_ATT_REPAIR_WALK,
     K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_COUNT
 };
 struct Knob { const char* name; int value; const char* doc; };
@@ -111,6 +114,7 @@ static Knob g_knobs[K_COUNT] = {
     {"ATT_FWD_LDS", 1, "LDS-DMA staged fp32 forward: 0 never, 1 heads with >= 4 query tiles, 2 wherever it fits"},
     {"ATT_FWD_KSPLIT", 1, "staged forward: key-tile groups per query tile"},
     {"ATT_FWD_LDS_PAD", 0, "probe: extra LDS bytes per forward workgroup (fewer workgroups per CU)"},
+    {"ATT_STREAM", 0, "1: every fp32-view forward and every phase 0-3 backward through the streamed kernels (always taken above 192 padded keys)"},
     {"ATT_FUSED_LAUNCH", 2, "fused backward: 2 one launch per key block, 1 one launch for both"},
     {"ATT_MERGE", 1, "short heads: one workgroup per head for both key blocks in the fused backward"},
     {"ATT_LDS_PAD", 0, "probe: extra LDS bytes per backward workgroup"},
@@ -235,6 +239,15 @@ static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
     const int nqt = (a.Lq + 15) / 16;
     int wq, hpb;
     attn_shape(nqt, a.H, 5, 1, K_ATT_HPB_FWD, wq, hpb);          // measured: grouping heads does not pay in the forward
+    // more than 12 key tiles: the streamed forward (online softmax, attention_stream.h), before any held form is considered -- the
+    // staged form below would be picked by its LDS test alone.  SEGMM_ATT_STREAM=1: at every size (A/B, tests)
+    if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) {
+        a.hpb = hpb;
+        dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);       // one wave per 16-query tile of a head
+        hipLaunchKernelGGL((attn_fwd_stream_kernel<DH>), grid, block, (size_t)Tp, s, a);
+        LAUNCH_CHECK();
+        return 0;
+    }
     // round 4: the LDS-DMA staged form (one workgroup per head: K / V of both key blocks staged once, every load of the head in
     // flight at once -- the staging alone runs at 5.7 TB/s) for heads with MORE than three query tiles: there one workgroup brings
     // enough waves (>= 4 per head, two heads per CU) to cover the per-wave instruction chains -- Lq = 100 (user queries of the full
@@ -288,6 +301,12 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
     const int Tp = ((a.La + 15) & ~15) + ((a.Lb + 15) & ~15);
     if (phase == 1) {          // D only
         const long long n = (long long)a.B * a.Lq * a.H;
+        if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) {          // the streamed backward's D: the bits its dQ kernel stores in phase 0
+            const long long tiles = (long long)a.B * a.H * ((a.Lq + 15) / 16);
+            hipLaunchKernelGGL((attn_D_stream_kernel<DH>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
+            LAUNCH_CHECK();
+            return 0;
+        }
         hipLaunchKernelGGL((attn_D_kernel<DH>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
         LAUNCH_CHECK();
         return 0;
@@ -403,7 +422,8 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
         attn_shape(nqt, a.H, 12, 1, K_ATT_HPB_DQ, wq, hpb);
         a.hpb = hpb;
         dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);
-        if (Tp <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 4>), grid, block, Tp, s, a);
+        if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<DH>), grid, block, Tp, s, a);
+        else if (Tp <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 4>), grid, block, Tp, s, a);
         else if (Tp <= 160) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 10>), grid, block, Tp, s, a);
         else hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 12>), grid, block, Tp, s, a);
         LAUNCH_CHECK();
@@ -1166,6 +1186,8 @@ int segmm_attn_fwd(int B, int H, int dh, int Lq, int La, int Lb, const float* Qa
         SEGMM_REQUIRE(pl->hdr_o && pl->ldo2 % 64 == 0 && aligned16(pl->o) && (H * dh) % 32 == 0, "attn_fwd: plane output needs a header, ld2 %% 64, width %% 32");
         a.po_o = plane_out(pl->o, pl->ldo2, pl->hdr_o, pl->sin_o);
     }
+    SEGMM_REQUIRE(!(pl && pl->qa_in) || attn_keys_p(La, Lb) <= 192, "attn_fwd: input planes with %d padded keys > 192: the streamed forward reads the fp32 views only",
+                  attn_keys_p(La, Lb));
     rc = attn_fill_in(a, pl, B, H, dh, Lq, La, Lb, "attn_fwd");
     if (rc) return rc;
     ATTN_DISPATCH(attn_launch_fwd, dh, a, (hipStream_t)stream);
@@ -1184,6 +1206,8 @@ int segmm_attn_bwd(int B, int H, int dh, int Lq, int La, int Lb, const float* Qa
     SEGMM_REQUIRE(!planes_in || phase >= 4, "attn_bwd: input planes need the fused backward (phase 4 / 5 / 6)");
     int rc = attn_fill(a, B, H, dh, Lq, La, Lb, Qa, Qb, ldq, Ka, Va, ldka, Kb, Vb, ldkb, mq, mka, mkb, drop_p, seed, site, planes_in);
     if (rc) return rc;
+    SEGMM_REQUIRE(phase <= 3 || attn_keys_p(La, Lb) <= 192, "attn_bwd phase %d: the fused backward holds at most 12 key tiles; %d padded keys > 192 take the "
+                  "streamed backward (phase 0, or 1 + 2 + 3) on fp32 views, without input planes", phase, attn_keys_p(La, Lb));
     rc = attn_fill_in(a, pl, B, H, dh, Lq, La, Lb, "attn_bwd");
     if (rc) return rc;
     SEGMM_REQUIRE(!planes_in || (dh % 16 == 0 && dh <= 48), "attn_bwd: input planes are built for head dims 16, 32, 48 (got %d)", dh);

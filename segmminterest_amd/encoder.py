@@ -179,6 +179,8 @@ class SegFormerX(nn.Module):
         self.debug = getattr(model_cfg, "debug", 0)
         self.num_layers_enc = getattr(model_cfg, "num_layers_enc", len(d_model_lvls))
         self.use_pe = use_pe
+        # opt-in: attention calls with more than 192 padded keys run on the streamed kernels instead of being refused (engine.py)
+        self.attn_stream = int(getattr(model_cfg, "attn_stream", 0) or 0)
         self.vid_pe = nn.Embedding(max_vid_len, d)
         self.usr_pe = nn.Embedding(max_usr_len, d)
         self.vid_ln = nn.LayerNorm(d, eps=1e-12)

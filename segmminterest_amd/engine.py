@@ -887,6 +887,11 @@ def _ln_bwd(store, dy, x, mean, rstd, gname, bname, gbuf, dx, dx_drop, rows, d, 
     return pp
 
 
+def _attn_streamed(La, Lb):
+    """Does an attention call with key blocks of La and Lb tokens go to the streamed kernels (more than 12 padded key tiles)?"""
+    return ((La + 15) & ~15) + ((Lb + 15) & ~15) > 192
+
+
 def _mask_u8(m: torch.Tensor) -> torch.Tensor:
     if m.dtype != torch.bool or not m.is_contiguous():
         H.torch_fallback("the conversion of a %s mask to contiguous bool" % str(m.dtype).replace("torch.", ""))
@@ -915,6 +920,7 @@ class BackboneRun:
         self.abl = getattr(bb, "ablation_type", "ours")
         self.mode = attn_mode(bb)
         self.n_mlp = len(mlp_linears(bb)) if self.abl in MLP_VARIANTS else 0
+        self.attn_stream = int(getattr(bb, "attn_stream", 0) or 0)          # model_cfg.attn_stream (SegFormerX keeps it): the opt-in below
 
     def _input_act(self, x, rows, cols):
         """External fp32 input (feature tensor) as a GEMM operand.  Its partial maxima come with the tensor when its producer
@@ -941,11 +947,18 @@ class BackboneRun:
 
     # ---------------------------------------------------------------- forward
     def _require_attn_keys(self, S, Lt):
-        """The attention kernels keep the keys of both blocks, each padded to a multiple of 16, in at most 12 tiles (``attn_fill``,
-        capi.hip).  Checked here, before the pass enqueues anything, for every attention call it would make."""
+        """The held attention kernels keep the keys of both blocks, each padded to a multiple of 16, in at most 12 tiles.  Checked
+        here, before the pass enqueues anything, for every attention call it would make.  A model built with
+        ``model_cfg.attn_stream = 1`` opts in to the streamed kernels (csrc/attention_stream.h) for the calls beyond that: then the
+        limit is 256 per axis (``attn_fill``, capi.hip)."""
         if self.abl in MLP_VARIANTS or self.N < 2:
             return
         pad16 = lambda n: (n + 15) & ~15
+        if self.__dict__.get("attn_stream", 0):          # (read this way: the check also serves an object that was never initialised)
+            if pad16(S) > 256 or pad16(Lt) > 256:
+                raise RuntimeError("attn: S=%d video segments / Lt=%d user tokens not built: the streamed attention kernels take at "
+                                   "most 256 of each" % (S, Lt))
+            return
         calls = [(0 if self.mode == "cross" else S, 0 if self.mode == "self" else Lt)]
         if self.N >= 3 and self.mode != "self":
             calls.append((S, 0 if self.mode == "cross" else Lt))
@@ -1211,7 +1224,8 @@ class BackboneRun:
             return False
         if H.knob("ATT_FWD_PL") == 0:
             return False
-        return all(Lq <= 112 and La + Lb <= 192 and La % 4 == 0 and Lb % 4 == 0 for (Lq, La, Lb) in self._attn_calls())
+        return all(Lq <= 112 and La + Lb <= 192 and La % 4 == 0 and Lb % 4 == 0 and not _attn_streamed(La, Lb)
+                   for (Lq, La, Lb) in self._attn_calls())
 
     def _proj_act(self, i, which, rows, cols):
         """The fused projection output Yv / Yu of layer i as an Act.  With the planes-in attention and a calibrated site its producer
@@ -1382,10 +1396,17 @@ class BackboneRun:
         # repair pass cost as much as the stores they save; SEGMM_ATTN_PLANES_ONLY=2 forces the protocol for every shape)
         ponly = self.delayed and st.attn_planes_only and dYv.po is not None and (not nu or dYu.po is not None) and \
             (S > 32 or st.attn_planes_only > 1)
+        # a call with more than 192 padded keys (model_cfg.attn_stream) takes the streamed backward: phase 0 on the fp32 views, no
+        # plane outputs.  Both calls of a layer write into the same dY buffers, so a layer with such a call drops the plane outputs
+        # and the planes-only / repair protocol for both; the dY planes then come from the split pass of finish_act.
+        st_v = _attn_streamed(vq["La"], vq["Lb"])
+        st_u = full and _attn_streamed(uq["La"], uq["Lb"])
+        streamed = st_v or st_u
+        ponly = ponly and not streamed
 
         def planes_of(dq, dka_, dkb_, views, pflags=0):
             """segmm_attn_planes_t for one fused-backward call: query-side buffer dq, key-block buffers dka_ / dkb_ (Acts)."""
-            if not self.delayed or dq.po is None:
+            if not self.delayed or dq.po is None or streamed:
                 return None
             pl = H.AttnPlanes()
 
@@ -1417,7 +1438,7 @@ class BackboneRun:
                                uq["Vb"], uq["ldkb"], self.um, self.vm, self.um, rec["lse_u"], rec["u"]["A"].t, d, dAu, d, Dv_u,
                                duq["Qa"], duq["Qb"], duq["ldq"], duq["Ka"], duq["Va"], duq["ldka"], duq["Kb"], duq["Vb"], duq["ldkb"],
                                drop_p=self.p_drop, seed=self.seed, site=_site(self.bi, i, K_ATT_U),
-                               amax_q=sl_u, amax_ka=sl_v, amax_kb=sl_u, phase=4, planes=planes_of(dYu, dYv, dYu, duq, pflags), pin=rec.get("pin_u"))
+                               amax_q=sl_u, amax_ka=sl_v, amax_kb=sl_u, phase=0 if st_u else 4, planes=planes_of(dYu, dYv, dYu, duq, pflags), pin=rec.get("pin_u"))
                 attn_u_(H.ATTN_PLANES_ONLY if ponly else 0)
                 return dR1u_, attn_u_
             if usr_on_side:
@@ -1432,7 +1453,7 @@ class BackboneRun:
             H.attn_bwd(B, Hh, dh, S, vq["La"], vq["Lb"], vq["Qa"], vq["Qb"], vq["ldq"], vq["Ka"], vq["Va"], vq["ldka"], vq["Kb"], vq["Vb"],
                        vq["ldkb"], self.vm, self.vm, self.um, rec["lse_v"], rec["v"]["A"].t, d, dAv, d, Dv, dvq["Qa"], dvq["Qb"], dvq["ldq"],
                        dvq["Ka"], dvq["Va"], dvq["ldka"], dvq["Kb"], dvq["Vb"], dvq["ldkb"], drop_p=self.p_drop, seed=self.seed,
-                       site=_site(self.bi, i, K_ATT_V), amax_q=sl_v, amax_ka=sl_v, amax_kb=sl_u, phase=4,
+                       site=_site(self.bi, i, K_ATT_V), amax_q=sl_v, amax_ka=sl_v, amax_kb=sl_u, phase=0 if st_v else 4,
                        planes=planes_of(dYv, dYv, dYu, dvq, pflags), pin=rec.get("pin_v"))
         attn_v(H.ATTN_PLANES_ONLY if ponly else 0)
         if full:
@@ -1449,7 +1470,7 @@ class BackboneRun:
             dYv.no_f32 = dYv.po is not None
             if nu:
                 dYu.no_f32 = dYu.po is not None
-        if self.delayed:          # every column block of a dY buffer must have been written WITH planes, else fall back to the split pass
+        if self.delayed and not streamed:          # every column block of a dY buffer must have been written WITH planes, else fall back to the split pass
             produced(dYv)
             if nu:
                 produced(dYu)
