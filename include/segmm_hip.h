@@ -335,7 +335,11 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
                        const float* v2_all, int Bg, float* logits_out, float* dlogits, float* parts,
                        segmm_stream_t stream);
 
-/* K9 -- fused AdamW over one flat fp32 range (torch.optim.AdamW semantics; main_for_seq_leave_earlystop_SegMM.py:226,299) */
+/* K9 -- fused AdamW over one flat fp32 range (torch.optim.AdamW semantics; main_for_seq_leave_earlystop_SegMM.py:226,299).
+ * lr >= 0 travels by value.  lr < 0 (pass SEGMM_LIVE_LR) is a sentinel: the kernel takes the rate from the bound device step
+ * state (segmm_step_schedule below), the value segmm_step_advance evaluated for this step; it needs step == -1 and is refused
+ * otherwise.  The same holds for segmm_adamw_table (both phases), segmm_adamw_scaled and segmm_adamw_table_scaled. */
+#define SEGMM_LIVE_LR (-1)
 int segmm_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                 float eps, float weight_decay, int step, segmm_stream_t stream);
 /* AdamW over an id-embedding table [n_rows, width] (encoder.py:352-362: nn.Embedding inputs) whose gradient is zero outside the
@@ -347,7 +351,8 @@ int segmm_adamw(float* p, const float* g, float* m, float* v, int64_t n, float l
  *            the table): 28 B x 90 M parameters of HBM traffic leave the end of the step (config 3's 352 494 x 256 item table);
  *   phase 1: the listed rows, each once (a mark is claimed and cleared by whoever updates the row), with their gradient rows
  *            from g (the dense [n_rows, width] gradient).  Enqueue it after phase 0 AND the backward have completed.
- * flags: n_rows 32-bit words owned by the caller, zero before the first call; zero again after phase 1.  step as in segmm_adamw. */
+ * flags: n_rows 32-bit words owned by the caller, zero before the first call; zero again after phase 1.  step and lr (the
+ * SEGMM_LIVE_LR sentinel included: phase 0 at the head of a step reads the rate of that same step) as in segmm_adamw. */
 int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                       uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
                       segmm_stream_t stream);
@@ -359,7 +364,7 @@ int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_ro
  *   (reciprocal, then product; a NaN norm gives a NaN coef).  max_norm > 0; max_norm = inf reports the norm and gives coef = 1.
  * segmm_adamw_scaled / segmm_adamw_table_scaled: segmm_adamw / phase 1 of segmm_adamw_table with the gradient multiplied by *coef
  *   (device memory, e.g. out2 + 1) and rounded to fp32 first -- bit for bit segmm_adamw on fp32(g * coef).  The table's phase 0
- *   (g = 0) takes no scale. */
+ *   (g = 0) takes no scale.  lr < 0 (SEGMM_LIVE_LR) with step == -1: the device state's rate, as in segmm_adamw. */
 int segmm_grad_norm(const float* g, int64_t n, float max_norm, double* scratch, float* out2, segmm_stream_t stream);
 int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream);
@@ -381,6 +386,32 @@ int segmm_step_bind(void* state);
 int segmm_step_set(uint64_t seed, int step, float beta1, float beta2, segmm_stream_t stream);
 int segmm_step_advance(float beta1, float beta2, segmm_stream_t stream);
 int segmm_step_get(uint64_t* seed, int* step, float* bias_corrections, segmm_stream_t stream);
+/* The learning rate of the step, in the same state: a recorded step carries every AdamW argument by value, so a rate that moves
+ * from step to step lives on the device next to the bias corrections.  The state holds a schedule descriptor and `lr`, the rate
+ * of its current step; segmm_step_advance re-evaluates lr as it increments the count (no further launch), segmm_step_set for the
+ * count it is given, and the AdamW entry points read it when their lr argument is SEGMM_LIVE_LR.  With k = the number of
+ * COMPLETED optimizer steps (torch's opt.step(); sched.step() loop: step t runs at k = t - 1), W = warmup_steps, D = decay_steps,
+ * j = max(k - W, 0), r = eta_min / base_lr:
+ *     lr = base_lr * warm(k) * dec(j),   warm(k) = start_factor + (1 - start_factor) k / W for k < W, else 1 (W = 0: no warm-up)
+ *     SEGMM_LR_CONSTANT dec = 1                                    SEGMM_LR_STEP dec = gamma^floor(j / step_size)
+ *     SEGMM_LR_COSINE   dec = r + (1 - r)(1 + cos(pi min(j, D) / D)) / 2      SEGMM_LR_EXP  dec = gamma^j
+ *     SEGMM_LR_LINEAR   dec = 1 - (1 - r) min(j, D) / D            (cosine and linear hold eta_min after D steps)
+ * evaluated in double from the descriptor's floats and rounded once to fp32: torch.optim.lr_scheduler's LinearLR warm-up followed
+ * (SequentialLR) by ConstantLR / CosineAnnealingLR / LinearLR / StepLR / ExponentialLR.  A zeroed state has no schedule
+ * (SEGMM_LR_NONE) and lr = 0.
+ * segmm_step_schedule installs a descriptor in the bound state and sets lr for the state's current count (at count 0: the rate
+ *   of step 1).  base_lr > 0; warmup_steps >= 0 and, with a warm-up, 0 < start_factor <= 1; decay_steps >= 1 for cosine and
+ *   linear; 0 <= eta_min <= base_lr; 0 < gamma <= 1; step_size >= 1 (fields a kind does not use must still be in range: pass
+ *   start_factor = gamma = 1, step_size = 1, eta_min = 0).  SEGMM_LR_NONE is what a zeroed state holds, not a kind to install.
+ * segmm_step_set_base_lr changes base_lr alone and re-evaluates lr: with SEGMM_LR_CONSTANT the hook of any host-driven scheduler
+ *   (reduce-on-plateau), legal between any two steps, eager or replayed.
+ * segmm_step_get_lr reads {lr, base_lr} back (either pointer may be null); like segmm_step_get it takes HOST pointers and
+ *   synchronises the stream. */
+enum { SEGMM_LR_NONE = 0, SEGMM_LR_CONSTANT = 1, SEGMM_LR_COSINE = 2, SEGMM_LR_LINEAR = 3, SEGMM_LR_STEP = 4, SEGMM_LR_EXP = 5 };
+int segmm_step_schedule(int kind, float base_lr, int warmup_steps, float start_factor, int decay_steps, float eta_min, float gamma,
+                        int step_size, segmm_stream_t stream);
+int segmm_step_set_base_lr(float base_lr, segmm_stream_t stream);
+int segmm_step_get_lr(float* lr, float* base_lr, segmm_stream_t stream);
 
 
 /* ---- the callers either side of the training step -------------------------------------------

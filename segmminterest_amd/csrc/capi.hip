@@ -516,6 +516,7 @@ __global__ void step_set_kernel(StepState* st, uint32_t lo, uint32_t hi, int ste
     st->seed_lo = lo; st->seed_hi = hi; st->step = step;
     st->bc1 = step > 0 ? (float)(1.0 - pow((double)b1, (double)step)) : 1.f;
     st->bc2_sqrt = step > 0 ? (float)sqrt(1.0 - pow((double)b2, (double)step)) : 1.f;
+    st->lr = (float)segmm_lr_at(*st, step - 1);          // the descriptor stays; step 0 holds the rate of step 1 (k = 0)
 }
 __global__ void step_advance_kernel(StepState* st, float b1, float b2) {
     const int t = st->step + 1;
@@ -525,6 +526,17 @@ __global__ void step_advance_kernel(StepState* st, float b1, float b2) {
     st->seed_lo = lo;
     st->bc1 = (float)(1.0 - pow((double)b1, (double)t));
     st->bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)t));
+    st->lr = (float)segmm_lr_at(*st, t - 1);          // step t runs at the rate of t - 1 completed steps: double, rounded once
+}
+__global__ void step_schedule_kernel(StepState* st, int kind, float base_lr, int warmup_steps, float start_factor, int decay_steps,
+                                     float eta_min, float gamma, int step_size) {
+    st->kind = kind; st->base_lr = base_lr; st->warmup_steps = warmup_steps; st->start_factor = start_factor;
+    st->decay_steps = decay_steps; st->eta_min = eta_min; st->gamma = gamma; st->step_size = step_size;
+    st->lr = (float)segmm_lr_at(*st, st->step - 1);
+}
+__global__ void step_base_lr_kernel(StepState* st, float base_lr) {
+    st->base_lr = base_lr;
+    st->lr = (float)segmm_lr_at(*st, st->step - 1);
 }
 }  // namespace segmm
 
@@ -1467,6 +1479,7 @@ int segmm_adamw(float* p, const float* g, float* m, float* v, int64_t n, float l
                 float eps, float weight_decay, int step, segmm_stream_t stream) {
     SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw: pointer/alignment");
     SEGMM_REQUIRE(step >= 1 || step == -1, "adamw: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
     if (n <= 0) return 0;
     return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, (hipStream_t)stream);
 }
@@ -1476,6 +1489,7 @@ int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, 
     SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_scaled: pointer/alignment");
     SEGMM_REQUIRE(coef, "adamw_scaled: null coef (use segmm_adamw for an unscaled step)");
     SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_scaled: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_scaled: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
     if (n <= 0) return 0;
     return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream);
 }
@@ -1487,6 +1501,7 @@ int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_ro
     SEGMM_REQUIRE(phase == 0 || (phase == 1 && g && aligned16(g)), "adamw_table: phase %d (0: rows without a gradient, 1: the listed rows; needs g)", phase);
     SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "adamw_table: width %% 4, sizes");
     SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
     if (n_rows == 0) return 0;
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     hipStream_t s = (hipStream_t)stream;
@@ -1519,6 +1534,7 @@ int segmm_adamw_table_scaled(float* p, const float* g, float* m, float* v, int64
     SEGMM_REQUIRE(coef, "adamw_table_scaled: null coef (use segmm_adamw_table for an unscaled step)");
     SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "adamw_table_scaled: width %% 4, sizes");
     SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_scaled: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table_scaled: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
     if (n_rows == 0 || n_ids == 0) return 0;
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     hipLaunchKernelGGL(adamw_table_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, width / 4,
@@ -1583,6 +1599,46 @@ int segmm_step_get(uint64_t* seed, int* step, float* bias_corrections, segmm_str
     if (seed) *seed = ((uint64_t)h.seed_hi << 32) | h.seed_lo;
     if (step) *step = h.step;
     if (bias_corrections) { bias_corrections[0] = h.bc1; bias_corrections[1] = h.bc2_sqrt; }
+    return 0;
+}
+
+int segmm_step_schedule(int kind, float base_lr, int warmup_steps, float start_factor, int decay_steps, float eta_min, float gamma,
+                        int step_size, segmm_stream_t stream) {
+    SEGMM_REQUIRE(kind >= SEGMM_LR_CONSTANT && kind <= SEGMM_LR_EXP, "step_schedule: kind=%d (SEGMM_LR_CONSTANT .. SEGMM_LR_EXP)", kind);
+    SEGMM_REQUIRE(base_lr > 0.f && base_lr < INFINITY, "step_schedule: base_lr=%g (> 0, finite)", (double)base_lr);
+    SEGMM_REQUIRE(warmup_steps >= 0, "step_schedule: warmup_steps=%d (>= 0)", warmup_steps);
+    SEGMM_REQUIRE(warmup_steps == 0 || (start_factor > 0.f && start_factor <= 1.f), "step_schedule: start_factor=%g (in (0, 1] with a warm-up)",
+                  (double)start_factor);
+    SEGMM_REQUIRE((kind != SEGMM_LR_COSINE && kind != SEGMM_LR_LINEAR) || decay_steps >= 1, "step_schedule: decay_steps=%d (>= 1 for cosine / linear)",
+                  decay_steps);
+    SEGMM_REQUIRE(eta_min >= 0.f && eta_min <= base_lr, "step_schedule: eta_min=%g (in [0, base_lr])", (double)eta_min);
+    SEGMM_REQUIRE(gamma > 0.f && gamma <= 1.f, "step_schedule: gamma=%g (in (0, 1])", (double)gamma);
+    SEGMM_REQUIRE(step_size >= 1, "step_schedule: step_size=%d (>= 1)", step_size);
+    if (decay_steps < 1) decay_steps = 1;          // (unused by the other kinds; never a divisor of 0)
+    StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_schedule: no step state");
+    hipLaunchKernelGGL(step_schedule_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st, kind, base_lr, warmup_steps, start_factor, decay_steps,
+                       eta_min, gamma, step_size);
+    LAUNCH_CHECK();
+    return 0;
+}
+int segmm_step_set_base_lr(float base_lr, segmm_stream_t stream) {
+    SEGMM_REQUIRE(base_lr > 0.f && base_lr < INFINITY, "step_set_base_lr: base_lr=%g (> 0, finite)", (double)base_lr);
+    StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_set_base_lr: no step state");
+    hipLaunchKernelGGL(step_base_lr_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st, base_lr);
+    LAUNCH_CHECK();
+    return 0;
+}
+int segmm_step_get_lr(float* lr, float* base_lr, segmm_stream_t stream) {
+    const StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_get_lr: no step state");
+    StepState h;
+    hipError_t e = hipMemcpyAsync(&h, st, sizeof(StepState), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    SEGMM_CHECK_HIP(e);
+    if (lr) *lr = h.lr;
+    if (base_lr) *base_lr = h.base_lr;
     return 0;
 }
 

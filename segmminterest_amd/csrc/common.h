@@ -93,9 +93,40 @@ struct DropCfg {
 // The state is a small struct in CALLER-OWNED device memory (segmm_step_state_bytes; segmm_step_bind names the one the following
 // launches use -- two trainers in one process each bind their own before they step); with nothing bound the library falls back to
 // one default state of its own.  The pointer travels inside the launch's arguments: no __device__ global.
-struct StepState { uint32_t seed_lo, seed_hi; int step; float bc1, bc2_sqrt; uint32_t pad_[3]; };
+// The learning rate of the step lives here too (segmm_step_schedule): `lr` is the rate of the step whose count is `step`, evaluated
+// by the same one-thread kernels from the schedule descriptor behind it; the AdamW kernels read it when they are handed the
+// sentinel lr < 0.  An all-zero state has no schedule (kind 0) and lr = 0.
+struct StepState {
+    uint32_t seed_lo, seed_hi; int step; float bc1, bc2_sqrt;
+    float lr;                                  // rate of step `step` (of step 1 while step = 0), fp32(schedule in double)
+    int kind;                                  // SEGMM_LR_* (0: no schedule)
+    float base_lr; int warmup_steps; float start_factor; int decay_steps; float eta_min, gamma; int step_size;
+    uint32_t pad_[2];
+};
+static_assert(sizeof(StepState) % 16 == 0, "StepState: a multiple of 16 bytes");
 extern StepState* g_segmm_step;          // host: the bound state (capi.hip)
 StepState* segmm_step_current();         // host: the bound state, or the library's default one (allocated on first use)
+// lr after k completed optimizer steps (torch's opt.step(); sched.step() loop: step t runs at k = t - 1), in double from the fp32
+// descriptor: base_lr warm(k) dec(max(k - W, 0)); warm ramps linearly from start_factor to 1 over W steps, dec by kind
+// (1 constant, 2 cosine and 3 linear down to eta_min over decay_steps and held there, 4 gamma^floor(j / step_size), 5 gamma^j).
+// tests/lr_ref.py states the same expression operation for operation; nothing may be contracted into an fma.
+__host__ __device__ inline double segmm_lr_at(const StepState& s, int k) {
+#pragma clang fp contract(off)
+    if (s.kind == 0) return 0.0;
+    const double base = (double)s.base_lr, sf = (double)s.start_factor;
+    const int W = s.warmup_steps, D = s.decay_steps;
+    if (k < 0) k = 0;
+    const double warm = (W > 0 && k < W) ? sf + (1.0 - sf) * (double)k / (double)W : 1.0;
+    const int j = k > W ? k - W : 0;
+    const double r = (double)s.eta_min / base;
+    const double jd = (double)(j < D ? j : D);
+    double dec = 1.0;
+    if (s.kind == 2) dec = r + (1.0 - r) * (1.0 + cos(3.14159265358979323846 * jd / (double)D)) / 2.0;
+    else if (s.kind == 3) dec = 1.0 - (1.0 - r) * jd / (double)D;
+    else if (s.kind == 4) dec = pow((double)s.gamma, (double)(j / s.step_size));
+    else if (s.kind == 5) dec = pow((double)s.gamma, (double)j);
+    return base * warm * dec;
+}
 __device__ __forceinline__ DropCfg drop_live(DropCfg d) {
     if (d.live) { d.seed_lo ^= d.st->seed_lo; d.seed_hi ^= d.st->seed_hi; }
     return d;

@@ -630,7 +630,8 @@ template <bool SCALED>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
                              float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; }          // bias corrections of the device-side step count
+    // bias corrections of the device-side step count; lr < 0 (SEGMM_LIVE_LR): the scheduled rate of that step as well
+    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     const long long n4 = n >> 2;
     const float step = lr / bc1;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -661,7 +662,7 @@ __global__ __launch_bounds__(256) void table_mark_kernel(const long long* __rest
 __global__ __launch_bounds__(256) void adamw_table_rest_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long n_rows,
                                                                int w4, const unsigned int* __restrict__ flags, float lr, float b1, float b2,
                                                                float eps, float wd, float bc1, float bc2_sqrt, const StepState* live) {
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; }
+    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     const float step = lr / bc1;
     const long long n4 = n_rows * w4;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -679,7 +680,7 @@ __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict
                                                                int n_ids, unsigned int* __restrict__ flags, float lr, float b1, float b2, float eps,
                                                                float wd, float bc1, float bc2_sqrt, const StepState* live,
                                                                const float* __restrict__ coef) {
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; }
+    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     const float step = lr / bc1;
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);

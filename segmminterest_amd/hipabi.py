@@ -571,6 +571,28 @@ def step_get():
     return int(seed.value), int(step.value), (float(bc[0]), float(bc[1]))
 
 
+LIVE_LR = float(_K["SEGMM_LIVE_LR"])          # lr argument of the AdamW entry points: the device step state's rate (needs step = -1)
+LR_KINDS = {n: _K["SEGMM_LR_" + n.upper()] for n in ("constant", "cosine", "linear", "step", "exp")}
+
+
+def step_schedule(kind, base_lr, warmup_steps=0, start_factor=1.0, decay_steps=1, eta_min=0.0, gamma=1.0, step_size=1):
+    """``segmm_step_schedule``: installs a learning-rate schedule (``kind``: a key of LR_KINDS or its number) in the bound step
+    state and sets the state's rate for its current step count."""
+    _check(lib().segmm_step_schedule(int(LR_KINDS.get(kind, kind)), float(base_lr), int(warmup_steps), float(start_factor), int(decay_steps),
+                                     float(eta_min), float(gamma), int(step_size), _stream()), "segmm_step_schedule")
+
+
+def step_set_base_lr(base_lr):
+    _check(lib().segmm_step_set_base_lr(float(base_lr), _stream()), "segmm_step_set_base_lr")
+
+
+def step_get_lr():
+    """(lr of the state's current step, base_lr) of the device-side step state; synchronises the stream."""
+    out = (C.c_float * 2)()
+    _check(_lib_real().segmm_step_get_lr(C.addressof(out), C.addressof(out) + 4, _stream()), "segmm_step_get_lr")
+    return float(out[0]), float(out[1])
+
+
 def config_set(name, value):
     """``segmm_config_set``: set the tuning knob ``name`` (without the SEGMM_ prefix; see :func:`config_dump`); returns the previous value."""
     _KNOBS.clear()

@@ -18,7 +18,10 @@ data parallelism is what this build adds:
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import functools
+import math
+import struct
 from typing import Dict, List, Optional
 
 import os
@@ -87,6 +90,148 @@ def _check_max_grad_norm(max_grad_norm):
     return m
 
 
+def _f32(x):
+    """``x`` rounded to float32, as a Python float: what the C ABI's ``float`` parameters carry."""
+    try:
+        return struct.unpack("f", struct.pack("f", float(x)))[0]
+    except OverflowError:          # beyond the fp32 range
+        return math.copysign(math.inf, x)
+
+
+@dataclasses.dataclass(frozen=True)
+class LRSchedule:
+    """A learning-rate schedule the DEVICE evaluates every step (segmm_step_schedule): ``lr_schedule=`` of FusedAdamW / Trainer,
+    given as an instance, a dict of these fields or just the kind's name.  The optimizer's ``lr`` is the base rate; with k the
+    number of completed optimizer steps, W = warmup_steps and j = max(k - W, 0) the step runs at
+    base * warm(k) * dec(j):  warm(k) = start_factor + (1 - start_factor) k / W for k < W, else 1 (torch's LinearLR; its default
+    start_factor 1/3); dec by ``kind``: "constant" 1; "cosine" / "linear" down to ``eta_min`` over ``decay_steps`` steps and held
+    there; "step" gamma^floor(j / step_size); "exp" gamma^j -- torch's CosineAnnealingLR / LinearLR / StepLR / ExponentialLR behind
+    the warm-up in a SequentialLR, stepped once per optimizer step."""
+    kind: str = "constant"
+    warmup_steps: int = 0
+    start_factor: float = 1.0 / 3
+    decay_steps: int = 0
+    eta_min: float = 0.0
+    gamma: float = 1.0
+    step_size: int = 1
+
+    KINDS = ("constant", "cosine", "linear", "step", "exp")
+
+    @classmethod
+    def parse(cls, spec, base_lr):
+        """``spec`` (None, a kind name, a dict of fields or an LRSchedule) validated against the base rate -> LRSchedule or None."""
+        if spec is None:
+            return None
+        if isinstance(spec, str):
+            spec = {"kind": spec}
+        if isinstance(spec, cls):
+            spec = dataclasses.asdict(spec)
+        if not isinstance(spec, dict):
+            raise ValueError("lr_schedule must be None, a kind name, a dict or an LRSchedule, not %r" % (spec,))
+        unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+        if unknown:
+            raise ValueError("lr_schedule: unknown field(s) %s" % sorted(unknown))
+        kind = spec.get("kind", "constant")
+        if kind not in cls.KINDS:
+            raise ValueError("lr_schedule: kind %r is not one of %s" % (kind, cls.KINDS))
+        need = {"cosine": ("decay_steps",), "linear": ("decay_steps",), "step": ("gamma", "step_size"), "exp": ("gamma",)}.get(kind, ())
+        for f in need:
+            if f not in spec:
+                raise ValueError("lr_schedule: kind %r needs %s" % (kind, f))
+        try:
+            ints = {f: spec[f] for f in ("warmup_steps", "decay_steps", "step_size") if f in spec}
+            for f, v in ints.items():
+                if isinstance(v, bool) or int(v) != v:
+                    raise ValueError
+            s = cls(kind=kind, **{f: int(v) for f, v in ints.items()},
+                    **{f: float(spec[f]) for f in ("start_factor", "eta_min", "gamma") if f in spec})
+            base = float(base_lr)
+        except (TypeError, ValueError):
+            raise ValueError("lr_schedule: warmup_steps, decay_steps, step_size must be integers, the other fields and lr floats: %r" % (spec,))
+        s.check_base(base)
+        if s.warmup_steps < 0 or (s.warmup_steps > 0 and not 0.0 < s.start_factor <= 1.0):
+            raise ValueError("lr_schedule: warmup_steps >= 0 and, with a warm-up, 0 < start_factor <= 1")
+        if kind in ("cosine", "linear") and s.decay_steps < 1:
+            raise ValueError("lr_schedule: decay_steps >= 1 for kind %r" % kind)
+        if not 0.0 < s.gamma <= 1.0 or s.step_size < 1:
+            raise ValueError("lr_schedule: 0 < gamma <= 1 and step_size >= 1")
+        return s
+
+    def check_base(self, base):
+        """The base rate this schedule may run under: positive, finite and (as floats of the C ABI) not below eta_min."""
+        if not (0.0 < _f32(base) < math.inf) or not 0.0 <= _f32(self.eta_min) <= _f32(base):
+            raise ValueError("lr_schedule: the base rate must be positive and finite and 0 <= eta_min <= base rate (lr %r, eta_min %r)"
+                             % (base, self.eta_min))
+
+    def lr_at(self, base_lr, k):
+        """The rate after ``k`` completed optimizer steps as the device computes it: float64 arithmetic on the float32 descriptor
+        (csrc/common.h segmm_lr_at), rounded once to float32."""
+        base, sf, eta, gamma = (_f32(x) for x in (base_lr, self.start_factor, self.eta_min, self.gamma))
+        W, D, k = self.warmup_steps, max(self.decay_steps, 1), max(int(k), 0)
+        warm = sf + (1.0 - sf) * k / W if (W > 0 and k < W) else 1.0
+        j = max(k - W, 0)
+        r = eta / base
+        dec = 1.0
+        if self.kind == "cosine":
+            dec = r + (1.0 - r) * (1.0 + math.cos(math.pi * min(j, D) / D)) / 2.0
+        elif self.kind == "linear":
+            dec = 1.0 - (1.0 - r) * min(j, D) / D
+        elif self.kind == "step":
+            dec = gamma ** (j // self.step_size)
+        elif self.kind == "exp":
+            dec = gamma ** j
+        return _f32(base * warm * dec)
+
+
+class PlateauLR:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau in plain Python, driving ``opt.set_base_lr``: ``step(metric)`` after every
+    validation; once the metric has not improved (by torch's relative / absolute ``threshold``) for more than ``patience``
+    validations the base rate becomes max(rate * factor, min_lr), unless that moves it by no more than ``eps``.  ``opt`` needs an
+    ``lr`` attribute (the base rate) and ``set_base_lr``."""
+
+    def __init__(self, opt, factor=0.1, patience=10, min_lr=0.0, mode="min", threshold=1e-4, threshold_mode="rel", cooldown=0, eps=1e-8):
+        if mode not in ("min", "max") or threshold_mode not in ("rel", "abs"):
+            raise ValueError("lr_plateau: mode must be 'min' or 'max' and threshold_mode 'rel' or 'abs'")
+        try:
+            factor, min_lr, threshold, eps = float(factor), float(min_lr), float(threshold), float(eps)
+            if isinstance(patience, bool) or isinstance(cooldown, bool) or int(patience) != patience or int(cooldown) != cooldown:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError("lr_plateau: factor, min_lr, threshold, eps must be floats, patience and cooldown integers")
+        if not 0.0 < factor < 1.0:
+            raise ValueError("lr_plateau: factor must lie in (0, 1), not %r" % factor)
+        if not min_lr >= 0.0 or patience < 0 or cooldown < 0 or not threshold >= 0.0 or not eps >= 0.0:
+            raise ValueError("lr_plateau: min_lr, patience, cooldown, threshold and eps must be >= 0")
+        self.opt, self.factor, self.patience, self.min_lr, self.mode = opt, factor, int(patience), min_lr, mode
+        self.threshold, self.threshold_mode, self.cooldown, self.eps = threshold, threshold_mode, int(cooldown), eps
+        self.best = math.inf if mode == "min" else -math.inf
+        self.num_bad, self.cooldown_counter = 0, 0
+
+    def is_better(self, a, best):
+        if self.mode == "min":
+            return a < (best * (1.0 - self.threshold) if self.threshold_mode == "rel" else best - self.threshold)
+        return a > (best * (self.threshold + 1.0) if self.threshold_mode == "rel" else best + self.threshold)
+
+    def step(self, metric):
+        """Feed one validation result; returns the new base rate if this call lowered it, else None."""
+        current = float(metric)
+        if self.is_better(current, self.best):
+            self.best, self.num_bad = current, 0
+        else:
+            self.num_bad += 1
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.num_bad = 0
+        if self.num_bad > self.patience:
+            self.cooldown_counter, self.num_bad = self.cooldown, 0
+            old = float(self.opt.lr)
+            new = max(old * self.factor, self.min_lr)
+            if old - new > self.eps:
+                self.opt.set_base_lr(new)
+                return new
+        return None
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics (lr 1e-3, wd 1e-4, betas (.9,.999), eps 1e-8 at
     main_for_seq_leave_earlystop_SegMM.py:226) as ONE kernel over the contiguous live range of the
@@ -98,11 +243,18 @@ class FusedAdamW:
     min(1, m / (norm + 1e-6)) stay on the device, and AdamW multiplies the gradient by it as it reads it -- no host sync.
     ``grad_norm`` is the last step's norm as a 0-dim device tensor (valid until the next step; ``.item()`` syncs); m = inf
     reports the norm and never clips.  Unlike torch, ``.grad`` keeps the UNCLIPPED gradient after the step.  A non-finite norm
-    propagates as in torch, except to the id-table rows without a gradient of a two-pass table update (stepped with g = 0)."""
+    propagates as in torch, except to the id-table rows without a gradient of a two-pass table update (stepped with g = 0).
 
-    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
+    ``lr_schedule`` (:class:`LRSchedule`, a dict of its fields or a kind name; None = the rate travels by value, as ever): the
+    rate of every step is evaluated on the DEVICE from ``lr`` (the base rate) and the schedule, inside the launch that advances
+    the step state, and the AdamW kernels read it there -- so it may move under a recorded step.  Needs the device step state
+    (``Trainer(device_state=True)``).  ``set_base_lr`` moves the base rate between two steps, ``current_lr`` is the host's value
+    of the coming step's rate, ``device_lr`` reads the device's (a sync)."""
+
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.schedule = LRSchedule.parse(lr_schedule, lr)
         self.step_count = 0
         self.m = self.v = None
         self._flat_id = None
@@ -132,6 +284,46 @@ class FusedAdamW:
     def _coef(self):
         return None if self.max_grad_norm is None else self._clip_out[1:2]
 
+    # ---- the learning rate: by value, or (lr_schedule) the device step state's
+    def _bound_state(self, what):
+        """Binds this optimizer's device step state for a call that reads or writes the scheduled rate."""
+        if not self.__dict__.get("device_state", False) or self.__dict__.get("_step_state") is None:
+            raise RuntimeError("%s: lr_schedule needs the device step state -- build the optimizer through Trainer(device_state=True)" % what)
+        H.step_bind(self._step_state)
+
+    def _lr_arg(self):
+        """The lr argument of the AdamW launches: the rate itself, or the sentinel that makes the kernels read the device's."""
+        if self.schedule is None:
+            return self.lr
+        self._bound_state("step")
+        return H.LIVE_LR
+
+    def _install_schedule(self):
+        """Writes the schedule and the base rate into the bound step state (whose step count is already set)."""
+        s = self.schedule
+        self._bound_state("lr_schedule")
+        H.step_schedule(s.kind, self.lr, s.warmup_steps, s.start_factor, max(s.decay_steps, 1), s.eta_min, s.gamma, s.step_size)
+
+    def set_base_lr(self, lr):
+        """Moves the base rate (segmm_step_set_base_lr, stream-ordered, no sync): the schedule continues from the new base.  Legal
+        between any two steps, eager or replayed from a recording."""
+        if self.schedule is None:
+            raise RuntimeError("set_base_lr needs an lr_schedule (\"constant\" suffices); without one assign opt.lr and record() again")
+        self.schedule.check_base(float(lr))
+        self._bound_state("set_base_lr")
+        H.step_set_base_lr(float(lr))
+        self.lr = float(lr)
+
+    def current_lr(self):
+        """The rate the NEXT step runs at, from the host's copy of the schedule (no sync); the device computes the same closed form
+        with its own cos / pow, so ``device_lr`` after that step's launch may differ in the last fp32 bit."""
+        return self.lr if self.schedule is None else self.schedule.lr_at(self.lr, self.step_count)
+
+    def device_lr(self):
+        """The rate in the device step state: that of the last step enqueued (of the first one before any).  Synchronises."""
+        self._bound_state("device_lr")
+        return H.step_get_lr()[0]
+
     def step(self, gbuf=None):
         self.begin_step(gbuf)
         st = self._state()
@@ -140,7 +332,7 @@ class FusedAdamW:
         # now, with their gradients; everything else as contiguous ranges around them
         for o, n, rows, width, ids, flags in sorted(self.__dict__.pop("_early", []), key=lambda e: e[0]):
             self.step_range(pos, o, gbuf)
-            H.adamw_table(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self.lr, self.betas[0],
+            H.adamw_table(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0],
                           self.betas[1], self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, 1,
                           coef=self._coef())
             pos = o + n
@@ -160,7 +352,7 @@ class FusedAdamW:
         flags = fl.get(name)
         if flags is None or flags.numel() != rows or flags.device != st.flat.device:
             flags = fl[name] = torch.zeros((rows,), dtype=torch.int32, device=st.flat.device)
-        H.adamw_table(st.flat, None, self.m, self.v, o, rows, width, ids, flags, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+        H.adamw_table(st.flat, None, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0], self.betas[1], self.eps, self.wd,
                       -1 if self.__dict__.get("device_state", False) else self.step_count + 1, 0)
         self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, flags))
 
@@ -200,7 +392,7 @@ class FusedAdamW:
             H.step_bind(self._step_state)
         if end > start:
             # device_state: the bias corrections come from the device-side step count (segmm_step_advance), step = -1
-            H.adamw(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, end - start, self.lr, self.betas[0], self.betas[1],
+            H.adamw(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, end - start, self._lr_arg(), self.betas[0], self.betas[1],
                     self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, p_off=start, coef=self._coef())
 
     def end_step(self):
@@ -221,9 +413,15 @@ class FusedAdamW:
         group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "params": list(range(len(names)))}
+        if self.schedule is not None:
+            # torch's schedulers keep the base rate in "initial_lr" and the running one in "lr"; the descriptor is an extra key
+            # torch.optim.AdamW.load_state_dict carries along untouched
+            group.update(lr=self.current_lr(), initial_lr=self.lr, segmm_lr_schedule=dataclasses.asdict(self.schedule))
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
+        if "segmm_lr_schedule" in sd["param_groups"][0]:          # (refused before anything is overwritten)
+            self._bound_state("load_state_dict of a checkpoint written under an lr_schedule")
         st = self._state()
         names = [n for n, _ in self.model.named_parameters()]
         self.m.zero_()
@@ -239,10 +437,17 @@ class FusedAdamW:
         self.step_count = max(steps) if steps else 0
         g = sd["param_groups"][0]
         self.lr, self.wd, self.betas, self.eps = g["lr"], g["weight_decay"], tuple(g["betas"]), g["eps"]
+        if "segmm_lr_schedule" in g:          # written under a schedule: "lr" is the rate of the next step, "initial_lr" the base
+            self.lr = g["initial_lr"]
+            self.schedule = LRSchedule.parse(g["segmm_lr_schedule"], self.lr)
+        elif self.schedule is not None:
+            self.schedule.check_base(float(self.lr))
         if self.__dict__.get("device_state", False):          # the device-side step count (bias corrections) follows the checkpoint
             H.step_bind(self._step_state)
             seed, _, _ = H.step_get()
             H.step_set(seed, self.step_count, *self.betas)
+            if self.schedule is not None:
+                self._install_schedule()
 
 
 # ------------------------------------------------------------------------------------------------ communication
@@ -447,8 +652,10 @@ class Trainer:
 
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
-                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None):
+                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None):
         self.model = model
+        if lr_schedule is not None and not device_state:
+            raise ValueError("Trainer(lr_schedule=...) needs device_state=True: the rate of a step is evaluated in the device step state")
         # device_state: what changes from step to step (dropout seed words, AdamW's step count and bias corrections, the
         # site-header rows of a step) lives on the device / is laid out per step, so the kernel arguments of a step never
         # change and ``record()`` can note its launch sequence once for ``run_recorded()`` to replay from C.  The eager step in
@@ -459,7 +666,7 @@ class Trainer:
         # HBM-bound kernel (segmm_gather_l1) and the 573 KB/row host->device copy disappears
         self.feature_table = feature_table
         self.dropout = dropout      # False: run the step in eval mode (deterministic; used by the DP equivalence tests)
-        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
         self.comm = comm if comm is not None else DPComm()
         self.overlap = overlap
         st = model._store
@@ -499,6 +706,8 @@ class Trainer:
             if self.comm.rank:          # data-parallel ranks seed torch identically: every rank drops different elements of its rows
                 seed0 = (seed0 ^ (self.comm.rank * 0x9E3779B97F4A7C15)) & (2 ** 62 - 1)
             H.step_set(seed0, self.opt.step_count, *self.opt.betas)
+            if self.opt.schedule is not None:
+                self.opt._install_schedule()
             st.live_seed = H.LIVE_SEED | 0x5E6D0001          # the (constant) seed argument of every dropout launch
 
     def _on_bucket(self, name, after_side=False):
@@ -991,7 +1200,9 @@ class Trainer:
         return out
 
     def _hyper(self):
-        return (self.opt.lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm)
+        # under an lr_schedule the recorded commands carry the sentinel, not a rate: the rate may move, the schedule's presence not
+        lr = self.opt.lr if self.opt.schedule is None else H.LIVE_LR
+        return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm)
 
     def _timed_plan(self, r):
         """The recorded phases cut at every GEMM / attention command (bench.py's timed replay): [("host", fn) | ("run", Phase) |
@@ -1047,8 +1258,8 @@ class Trainer:
             raise RuntimeError("run_recorded() before record()")
         H.step_bind(self._step_state)
         if self._hyper() != r["hyper"]:
-            # the recorded segmm_adamw / segmm_adamw_table / segmm_grad_norm commands carry lr, weight decay, betas, eps and the
-            # clipping norm BY VALUE
+            # the recorded segmm_adamw / segmm_adamw_table / segmm_grad_norm commands carry lr (without an lr_schedule), weight
+            # decay, betas, eps and the clipping norm BY VALUE
             raise RuntimeError("run_recorded(): the optimizer's hyperparameters changed since record() (%r -> %r): record() again"
                                % (r["hyper"], self._hyper()))
         for k, (sh, dt) in r["spans"].items():
@@ -1339,7 +1550,8 @@ def compute_final_result(results_list):
 
 def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_step: int = 30, early_stop: int = 0,
         main_metric: str = "NDCG@5", ckpt: Optional["CheckPointer"] = None, logging_step: int = 0, log=None,
-        permutation: int = 1, top_k_mask: bool = False, metrics=None, recorded: bool = False, eager_steps: int = 3):
+        permutation: int = 1, top_k_mask: bool = False, metrics=None, recorded: bool = False, eager_steps: int = 3,
+        lr_plateau: Optional[dict] = None):
     """The train / validate / checkpoint / early-stop loop of the reference trainer around ``Trainer.train_step``
     (main_for_seq_leave_earlystop_SegMM.py:247-354): one validation over ``valid_batches`` BEFORE training, then per epoch every
     ``valid_step`` local steps a validation whose ``main_metric`` (mean over the validation batches, :179-181) drives
@@ -1351,6 +1563,10 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
     previous batch: no extra optimisation step), every later batch of the same shapes is enqueued from the recorded launch
     sequences (``run_recorded``: one C call per phase, bit-identical to the eager step); a batch of another shape (the short last
     batch of an epoch) takes the eager step.  Every batch is still stepped on exactly once, in order.
+    ``lr_plateau`` (a dict of :class:`PlateauLR` arguments, e.g. ``dict(factor=0.5, patience=2, min_lr=1e-6)``; ``mode`` defaults to
+    "max", the sense of the early-stop tests): reduce-on-plateau with torch.optim.lr_scheduler.ReduceLROnPlateau's rules, fed after
+    every validation of the loop the number early stopping reads -- every data-parallel rank decides alike -- and acting through
+    ``opt.set_base_lr``, so it needs ``Trainer(lr_schedule=...)`` ("constant" suffices) and works under ``recorded=True``.
     Returns the history dict the reference calls ``total_valid_loss_metrics`` (+ "stopped_epoch", "global_step")."""
     metrics = list(metrics) if metrics is not None else ["valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"]
     hist: Dict[str, list] = {"train_loss": [0.0]}
@@ -1365,6 +1581,16 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
 
     if recorded and not trainer.device_state:
         raise RuntimeError("fit(recorded=True) needs Trainer(device_state=True)")
+    plateau = None
+    if lr_plateau is not None:
+        if not isinstance(lr_plateau, dict):
+            raise ValueError("lr_plateau must be a dict of PlateauLR arguments, not %r" % (lr_plateau,))
+        if trainer.opt.schedule is None:
+            raise ValueError("fit(lr_plateau=...) needs Trainer(lr_schedule=...): \"constant\" suffices")
+        try:
+            plateau = PlateauLR(trainer.opt, **{"mode": "max", **lr_plateau})
+        except TypeError as e:
+            raise ValueError("lr_plateau: %s" % e)
 
     def shapes_of(b):
         return {k: (tuple(v.shape), v.dtype) for k, v in b.items() if torch.is_tensor(v) and v.numel()}
@@ -1402,6 +1628,8 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
                 hist["train_loss"].append(float(epoch_losses[-1]))
                 validate()
                 avg = hist[main_metric][-1]
+                if plateau is not None and plateau.step(avg) is not None and log is not None:
+                    log("Base learning rate: %g, Global_step: %d" % (trainer.opt.lr, global_step))
                 if log is not None:
                     log("Valid_loss: %s, %s: %s, Global_step: %d" % (hist["valid_loss"][-1] if "valid_loss" in hist else None, main_metric, avg, global_step))
                 if ckpt is not None and trainer.comm.rank == 0:
