@@ -155,8 +155,9 @@ __global__ __launch_bounds__(64 * ATT_PL_MAXW) void attn_fwd_pl_kernel(const Att
         // common.h site_planes_ok, on votes instead of wave reductions (the maximum itself is only needed on the fallback path)
         auto okf = [](float s, uint32_t flag, f32x4 m4) {
             const float m = fmaxf(fmaxf(m4.x, m4.y), fmaxf(m4.z, m4.w));          // this lane's four slots
-            const bool any_pos = __any(m > 0.f), any_big = __any(m * s >= 0.25f), any_over = __any(!(m * s < 65504.f));
-            return s > 0.f && flag == 0u && (!any_pos || ((any_big || s >= 0x1p60f) && !any_over));
+            const WindowCmp c = window_cmp(s, m);
+            const bool any_pos = __any(c.pos), any_big = __any(c.big), any_over = __any(c.over);          // (votes first: every lane takes part)
+            return site_live(s, flag) && window_holds(s, WindowCmp{any_pos, any_big, any_over});
         };
         auto mx4 = [](f32x4 m4) { return wave_max(fmaxf(fmaxf(m4.x, m4.y), fmaxf(m4.z, m4.w))); };
         ok_q = okf(s_q, hq1, mq4); ok_a = okf(s_a, ha1, ma4); ok_b = okf(s_b, hb1, mb4);
@@ -606,9 +607,8 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? SEGMM_ATT16_WPS : 4) void attn_b
             // GEMM's repair launch rewrote the planes with the exact scale of the recorded maxima): take that scale
             const float amax_q = wave_max(fmaxf(fmaxf(hq4.x, hq4.y), fmaxf(hq4.z, hq4.w)));
             const float amax_k = wave_max(fmaxf(fmaxf(hk4.x, hk4.y), fmaxf(hk4.z, hk4.w)));
-            auto okf = [](float s, uint32_t flag, float m) { return s > 0.f && flag == 0u && (!(m > 0.f) || ((m * s >= 0.25f || s >= 0x1p60f) && m * s < 65504.f)); };
-            sQs = okf(hq0, __float_as_uint(hq1), amax_q) ? hq0 : f16_scale_of(amax_q);
-            sK = okf(hk0, __float_as_uint(hk1), amax_k) ? hk0 : f16_scale_of(amax_k);
+            sQs = site_window_ok(hq0, __float_as_uint(hq1), amax_q) ? hq0 : f16_scale_of(amax_q);
+            sK = site_window_ok(hk0, __float_as_uint(hk1), amax_k) ? hk0 : f16_scale_of(amax_k);
             sV = sK;                                       // K and V of a block are columns of one buffer
             maxV = amax_k;                                 // bound of |V| (the site's maximum)
         }

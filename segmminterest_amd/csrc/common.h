@@ -251,12 +251,41 @@ __device__ __forceinline__ float site_amax(const float* hdr, int lane) {
 // SHRANK by more than ~2^9 since its scale was derived (the gradients of a batch whose loss has collapsed) would silently keep
 // 12 bits instead of 22.  max * s >= 2^-2 keeps every element's absolute error below 2^-22 max.  Checked by the CONSUMER, which
 // sees the complete maxima (one 1 KB read per wave); block-uniform.
-__device__ __forceinline__ bool site_planes_ok(const float* hdr, float s, int lane) {
-    if (!(s > 0.f) || __float_as_uint(hdr[1]) != 0u) return false;
-    const float m = site_amax(hdr, lane);
-    // (s at its upper clamp 2^60 -- f16_scale_of / scales_update keep 1/(sa sb) finite: the fallback would use the same scale)
-    return !(m > 0.f) || ((m * s >= 0.25f || s >= 0x1p60f) && m * s < 65504.f);
+//
+// THE RULE IS STATED HERE ONCE.  A producer's repair launch (gemm_planes_epi.h) and the consumers of the repaired planes
+// (attention_pl.h) must reach the same verdict from the same header words, or the consumer reads planes at the wrong scale:
+// every kernel judges a site through site_window_ok, or -- on votes -- through window_cmp + window_holds.
+struct WindowCmp { bool pos, big, over; };          // a maximum m against the window of scale s
+__device__ __forceinline__ WindowCmp window_cmp(float s, float m) { return {m > 0.f, m * s >= 0.25f, !(m * s < 65504.f)}; }
+// (s at its upper clamp 2^60 -- f16_scale_of / scales_update keep 1/(sa sb) finite: the fallback would use the same scale)
+__device__ __forceinline__ bool window_holds(float s, WindowCmp c) { return !c.pos || ((c.big || s >= 0x1p60f) && !c.over); }
+__device__ __forceinline__ bool site_live(float s, uint32_t flag) { return s > 0.f && flag == 0u; }          // planes written, no overflow recorded
+__device__ __forceinline__ bool site_window_ok(float s, uint32_t flag, float m) {
+    return site_live(s, flag) && window_holds(s, window_cmp(s, m));
 }
+__device__ __forceinline__ bool site_planes_ok(const float* hdr, float s, int lane) {
+    if (!site_live(s, __float_as_uint(hdr[1]))) return false;          // (no read of the maxima then)
+    return site_window_ok(s, 0u, site_amax(hdr, lane));
+}
+// The same verdict for kernels that cannot wait for three dependent reads: site_words REQUESTS every header word of a site
+// (scale, flag, this lane's four partial maxima) -- call it for all sites of a kernel before the first use, so that the loads
+// share one round trip.  site_scale is the wave-uniform scale; site_usable judges the words under it (needs the maxima: ask
+// only where there is an fp32 copy to fall back on); site_state is both plus the site's maximum, for the repair verdict.
+__device__ __forceinline__ float wave_uniform(float x) {          // same in every lane: keep it scalar
+    return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x)));
+}
+struct SiteWords { float scale, flag; f32x4 amax4; };
+struct SiteState { float scale, amax; bool ok; };
+__device__ __forceinline__ SiteWords site_words(const float* hdr, int lane) {
+    return {hdr[0], hdr[1], *(const f32x4*)(hdr + SITE_HDR + lane * 4)};
+}
+__device__ __forceinline__ float site_scale(const SiteWords& w) { return wave_uniform(w.scale); }
+__device__ __forceinline__ SiteState site_state(const SiteWords& w) {
+    const float s = site_scale(w);
+    const float m = wave_max(fmaxf(fmaxf(w.amax4.x, w.amax4.y), fmaxf(w.amax4.z, w.amax4.w)));
+    return {s, m, site_window_ok(s, __float_as_uint(wave_uniform(w.flag)), m)};
+}
+__device__ __forceinline__ bool site_usable(const SiteWords& w) { return site_state(w).ok; }
 // (x0, x1) * s -> packed fp16 (hi0, hi1), (lo0, lo1); hi + lo = x s up to 2^-22 |x s|.
 // Four VALU instructions per pair: v_fma_mix{lo,hi}_f16 multiply in fp32, round ONCE to fp16 and write one half
 // of the destination, and take the fp16 hi term straight back as the addend of the lo term

@@ -15,7 +15,9 @@
 // were written with, hdr[1] != 0 = some element left the fp16 range under that scale (delayed scaling: s comes from an
 // earlier step) -- or hdr[0] == 0: no planes were written at all (first use of a tensor site).  In both cases the
 // kernel takes the operand from its fp32 copy instead and splits it on the fly with the exact scale of the partial
-// maxima (slow path, staged through registers; results identical in accuracy, never silently wrong).
+// maxima (slow path, staged through registers; results identical in accuracy, never silently wrong).  The verdict is ONE rule,
+// common.h's site_window_ok: every generation of these kernels (this file; gemm_planes8.h and gemm_planes4.h, which share
+// their epilogue and rare-path staging through gemm_planes_epi.h) and the attention kernels judge a header through it.
 //
 // NT kernel: 256 x 256 x 32 tile, 512 threads = 8 waves as 2 (m) x 4 (n), 128 x 64 per wave = 4 x 2 MFMA tiles x 3
 // products, 128 accumulator registers; two 64 KB LDS stages (A 256 rows x 128 B, B 256 rows x 128 B); one barrier per

@@ -11,8 +11,9 @@
 // the quantisation loss of launches with few tiles (config 4's 256-row shard: 120 tiles of 256 x 256 on 256 CUs).
 //
 // Same arithmetic, operand format (P32 planes), MFMA shape and order (v_mfma_f32_16x16x32_f16, hl + lh + hh per k32 block,
-// swapped operands: the accumulator tile is C^T), fallback / repair protocol and epilogue as gemm_pl_nt8: the results are
-// BITWISE those of gemm_pl_nt8 (same accumulation chain per element).
+// swapped operands: the accumulator tile is C^T) as gemm_pl_nt8; the fallback / repair verdicts (site_usable / site_state, common.h), the rare
+// path's staging and the epilogue (nt_epilogue, gemm_planes_epi.h) ARE gemm_pl_nt8's, instantiated for this tile: the results
+// are BITWISE those of gemm_pl_nt8 (same accumulation chain per element).
 //
 // NT kernel gemm_pl_nt4: waves as 1 (m) x 4 (n), 128 x 64 per wave (128 accumulator registers).  LDS:
 //     [0, 32 K)            A: two stages of 128 rows x 128 B (a k-tile of 32: [32 hi | 32 lo] per row), shared by the four waves
@@ -49,8 +50,7 @@ constexpr int P4_BRING = 3 * P4_BHALF;                 // 12 KB per wave
 #define P4_STAGGER 0          // units of 512 cycles per k-tile that the late half of the first round sleeps (0: no stagger)
 #endif
 constexpr int P4_LDS = P4_BOFF + 4 * P4_BRING + P4_LDS_PAD;         // 80 KB
-constexpr int P4_EHALF = 32768;                        // epilogue: a quarter of the tile's extra operand (32 rows x 1 KB)
-constexpr int P4_PATCH = 2 * P4_EHALF;                 // epilogue: 4 KB transpose patch per wave behind the two E halves
+constexpr int P4_PATCH = NtEpiGeom<4, 1, true>::PATCH;              // output code: 4 KB transpose patch per wave, where the NT epilogue has its own
 
 template <int N>
 __device__ __forceinline__ void wait_vm_barrier() {          // close a k-tile: all but the N youngest pieces landed, then the workgroup's barrier
@@ -100,12 +100,9 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_nt4(const GemmArgs p, const PG
     // ---- REPAIR launch of a planes-only output (see gemm_pl_nt8): usable site -> leave at once, else recompute with the exact scale
     float c_repair = 0.f;
     if (q.repair) {
-        const float hc0 = q.c_hdr[0];
-        const uint32_t hc1 = __float_as_uint(q.c_hdr[1]);
-        const f32x4 amc = *(const f32x4*)(q.c_hdr + SITE_HDR + lane * 4);
-        const float m = wave_max(fmaxf(fmaxf(amc.x, amc.y), fmaxf(amc.z, amc.w)));
-        if (hc0 > 0.f && hc1 == 0u && (!(m > 0.f) || ((m * hc0 >= 0.25f || hc0 >= 0x1p60f) && m * hc0 < 65504.f))) return;
-        c_repair = f16_scale_of(m);
+        const SiteState sc = site_state(site_words(q.c_hdr, lane));
+        if (sc.ok) return;
+        c_repair = f16_scale_of(sc.amax);
     }
 
     // ---- stagger: the workgroups of a launch start within a microsecond of each other, so the two that share a CU would run
@@ -164,20 +161,13 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_nt4(const GemmArgs p, const PG
         for (int pc = 0; pc < 4; ++pc) dmaB1(1, pc, 2);
     }
 
-    // ---- operand state (block-uniform): planes usable?  (all header words requested at once, judged like site_planes_ok)
-    auto uni = [](float x) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
-    const float ha0 = q.A.hdr[0], ha1 = q.A.hdr[1], hb0 = q.B.hdr[0], hb1 = q.B.hdr[1];
-    const f32x4 ama = *(const f32x4*)(q.A.hdr + SITE_HDR + lane * 4), amb = *(const f32x4*)(q.B.hdr + SITE_HDR + lane * 4);
+    // ---- operand state (block-uniform): planes usable?  (all header words requested at once, judged by the rule of common.h)
+    const SiteWords wa = site_words(q.A.hdr, lane), wb = site_words(q.B.hdr, lane);
     const float cs_in = (q.Cp && q.c_scale_in) ? *q.c_scale_in : 0.f;
-    const float sa_hdr = uni(ha0), sb_hdr = uni(hb0);
-    auto planes_ok = [&](float s, float flag, f32x4 v) {
-        const float m = wave_max(fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-        if (!(s > 0.f) || __float_as_uint(flag) != 0u) return false;
-        return !(m > 0.f) || ((m * s >= 0.25f || s >= 0x1p60f) && m * s < 65504.f);
-    };
-    const bool slowA = q.A.f32 != nullptr && !planes_ok(sa_hdr, uni(ha1), ama);
-    const bool slowB = q.B.f32 != nullptr && !planes_ok(sb_hdr, uni(hb1), amb);
-    const float c_scale = q.repair ? uni(c_repair) : uni(cs_in);
+    const float sa_hdr = site_scale(wa), sb_hdr = site_scale(wb);
+    const bool slowA = q.A.f32 != nullptr && !site_usable(wa);          // (no fp32 copy: nothing to fall back on, not judged)
+    const bool slowB = q.B.f32 != nullptr && !site_usable(wb);
+    const float c_scale = q.repair ? wave_uniform(c_repair) : wave_uniform(cs_in);
 
     // ---- fragment read addressing (lane: row l15 of a 16-row block, logical chunk 4 plane + lq; physical = logical ^ swz)
     const int swz = (l15 >> 1) & 7;
@@ -285,34 +275,13 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_nt4(const GemmArgs p, const PG
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the early pieces have landed before anything is restaged
         if (slowA) sa = site_exact_scale(q.A.hdr, (float*)(smem + P4_LDS - 64), tid, 256);
         if (slowB) sb = site_exact_scale(q.B.hdr, (float*)(smem + P4_LDS - 64), tid, 256);
-        auto slow_stage = [&](const PlaneOperand& op, float sc, int row0, int nrows, int ntrows, int kt, char* dst) {
-#pragma unroll 1
-            for (int j = tid; j < ntrows * 4; j += 256) {
-                const int row = j >> 2, kc = j & 3;
-                const float* src = op.f32 + (size_t)min(row0 + row, nrows - 1) * op.ldf + kt * 32 + kc * 8;
-                const f32x4 x0 = *(const f32x4*)src, x1 = *(const f32x4*)(src + 4);
-                uint32_t h0, l0, h1, l1, h2, l2, h3, l3;
-                splith_pair(x0.x, x0.y, sc, h0, l0); splith_pair(x0.z, x0.w, sc, h1, l1);
-                splith_pair(x1.x, x1.y, sc, h2, l2); splith_pair(x1.z, x1.w, sc, h3, l3);
-                const int sw = (row >> 1) & 7;
-                *(uint4*)(dst + row * 128 + ((kc ^ sw) << 4)) = make_uint4(h0, h1, h2, h3);
-                *(uint4*)(dst + row * 128 + (((4 + kc) ^ sw) << 4)) = make_uint4(l0, l1, l2, l3);
-            }
-        };
-        auto dma_rows = [&](__amdgpu_buffer_rsrc_t rs, const PlaneOperand& op, int row0, int nrows, int ntrows, int kt, char* dst) {
-#pragma unroll 1
-            for (int pc = wave; pc < ntrows / 8; pc += 4) {
-                const int row = pc * 8 + r8;
-                lds_dma16(rs, dst + pc * 1024, (uint32_t)min(row0 + row, nrows - 1) * (uint32_t)op.ld2 * 2u +
-                          (uint32_t)(((lane & 7) ^ ((row >> 1) & 7)) * 16), (uint32_t)kt * 128u);
-            }
-        };
         const char* bsh = smem + P4_ASTAGE + wn * 64 * 128;
 #pragma unroll 1
         for (int t = 0; t < nkt; ++t) {
             __syncthreads();
-            if (slowA) slow_stage(q.A, sa, m0, p.M, P4_BM, t, smem); else dma_rows(rsA, q.A, m0, p.M, P4_BM, t, smem);
-            if (slowB) slow_stage(q.B, sb, n0, p.N, P4_BN, t, smem + P4_ASTAGE); else dma_rows(rsB, q.B, n0, p.N, P4_BN, t, smem + P4_ASTAGE);
+            if (slowA) nt_slow_stage<256>(q.A, sa, m0, p.M, P4_BM, t, smem, tid); else nt_dma_rows<256>(rsA, q.A, m0, p.M, P4_BM, t, smem, wave, lane);
+            if (slowB) nt_slow_stage<256>(q.B, sb, n0, p.N, P4_BN, t, smem + P4_ASTAGE, tid);
+            else nt_dma_rows<256>(rsB, q.B, n0, p.N, P4_BN, t, smem + P4_ASTAGE, wave, lane);
             dma_wait_barrier();
 #pragma unroll
             for (int j = 0; j < NJ; ++j) rdB(j, bsh, bsh + P4_BHALF);
@@ -327,246 +296,11 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_nt4(const GemmArgs p, const PG
     }
     STAMP(2);
 
-    // ================================================================ epilogue (gemm_pl_nt8's, for one wave group)
-    // lane holds C[gm = m0 + 16 i + l15][gn = n0 + 64 wn + 16 j + 4 lq .. + 3] of tile (i, j).  The extra operand E (residual, or
-    // the aux tensor of an activation gradient) is staged by LDS-DMA, a quarter of the tile (32 rows x 1 KB) at a time, into
-    // the two 32 KB halves at the bottom of the LDS; the per-wave transpose patches sit behind them.  Every wave has passed
-    // the loop's last barrier with its LDS reads retired, so the k-loop's regions are free.
-    float am = 0.f;
-    if (SEGMM_GEMM_DBG(q) & 2) {
-        float t = 0.f;          // timing ablation: keep every accumulator alive, skip the epilogue
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) t += acc[i][j].x + acc[i][j].y + acc[i][j].z + acc[i][j].w;
-        if (t == 1.2345f) p.C[0] = 1.f;
-    } else {
-        const float inv_ab = (1.f / sa) * (1.f / sb);          // exact powers of two
-        const int epi = p.epi;
-        const bool has_res = p.residual != nullptr, has_drop = p.drop.p > 0.f;
-        const DropCfg drop_e = drop_live(p.drop);
-        const bool aux_r = epi == EPI_DGELU || epi == EPI_DRELU, aux_w = epi == EPI_GELU;
-        const bool planes = c_scale > 0.f && q.Cp != nullptr;
-        const bool store_c = q.write_c && !(SEGMM_GEMM_DBG(q) & 1);
-        const bool periodic = has_res && p.res_period < p.M;
-        const int res_rows = has_res ? min(p.res_period, p.M) : 0;
-        const bool has_e = has_res || aux_r;
-        auto ext = [&](bool on, long long rows, long long ld, long long elt) -> uint32_t {      // view extent in bytes (0: absent)
-            if (!on || rows <= 0) return 0u;
-            return (uint32_t)(((rows - 1) * ld + p.N) * elt);          // < 2^31 (checked by the host)
-        };
-        const __amdgpu_buffer_rsrc_t rsC = make_rsrc(p.C, ext(store_c, p.M, p.ldc, 4));
-        const __amdgpu_buffer_rsrc_t rsAuxW = make_rsrc(p.aux, ext(aux_w, p.M, p.ldaux, 4));
-        const __amdgpu_buffer_rsrc_t rsE = aux_r ? make_rsrc(p.aux, ext(true, p.M, p.ldaux, 4)) : make_rsrc(p.residual, ext(has_res, res_rows, p.ldr, 4));
-        const int ldE = aux_r ? p.ldaux : p.ldr;
-        const __amdgpu_buffer_rsrc_t rsPl = make_rsrc(q.Cp, planes ? (uint32_t)((((long long)p.M - 1) * q.ldc2 + 2ll * p.N) * 2) : 0u);
-        const int ns = (store_c ? 1 : 0) + (planes ? 1 : 0) + (aux_w ? 1 : 0);          // store instructions per float4
-
-        const int gm0 = m0 + l15;
-        const int gn0 = n0 + wn * 16 * NJ + 4 * lq;
-        uint32_t colmask[NJ];          // 0 or BUF_OOB: columns beyond N are pushed out of every descriptor's range
-        f32x4 bias4[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int gn = gn0 + 16 * j;
-            colmask[j] = gn < p.N ? 0u : BUF_OOB;
-            bias4[j] = (p.bias && gn < p.N) ? *(const f32x4*)(p.bias + gn) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        const bool full_tile = m0 + P4_BM <= p.M && n0 + P4_BN <= p.N;
-        // E quarter qq -> half (qq & 1): slot s = tile row - 32 qq at byte s * 1024; 16-byte chunk c of the row at physical chunk
-        // c ^ (row & 15) (conflict-free ds_read_b128 of the accumulator layout); the permutation is applied to the DMA source
-        auto dmaE = [&](int qq) {
-            char* dst = smem + (qq & 1) * P4_EHALF;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int slot = wave * 8 + k;
-                const int R = qq * 32 + slot;          // tile row (wave-uniform)
-                const int gmR = m0 + R;
-                const int er = aux_r ? gmR : (periodic ? gmR % p.res_period : gmR);
-                const int ch = lane ^ (R & 15);
-                const uint32_t vo = (ch < 16 * NJ && n0 + 4 * ch < p.N) ? (uint32_t)ch * 16u : BUF_OOB;
-                lds_dma16e(rsE, dst + slot * 1024, vo, ((uint32_t)er * (uint32_t)ldE + (uint32_t)n0) * 4u);
-            }
-        };
-        auto vmwait = [&](int kind) {          // kind 0: 8 newer ops; 1: S + 8; 2: S newer ops, S = 8 ns store instructions of the last quarter
-            __builtin_amdgcn_sched_barrier(0);
-            if (kind == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (ns == 1) { if (kind == 1) asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-            else if (ns == 2) { if (kind == 1) asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); }
-            else if (ns == 3) { if (kind == 1) asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); }
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        // ---- stores: every 16-row x 64-column strip passes through the wave's 4 KB patch (chunk c of row r at physical chunk
-        // c ^ r) and leaves as whole 256-byte row segments: lane (lq, l15) of pass t stores row 4 t + lq, columns 4 l15 .. + 3
-        char* trp = smem + P4_PATCH + wave * 4096;
-        const uint32_t tr_w = (uint32_t)(l15 * 256);
-        const int gnT = n0 + wn * 16 * NJ + 4 * l15;
-        const uint32_t tmask = (l15 < 4 * NJ && gnT < p.N) ? 0u : BUF_OOB;
-        const uint32_t oCT = (((uint32_t)(m0 + lq) * (uint32_t)p.ldc + (uint32_t)gnT) * 4u) | tmask;
-        const uint32_t oAuxT = (((uint32_t)(m0 + lq) * (uint32_t)p.ldaux + (uint32_t)gnT) * 4u) | tmask;
-        auto tr_put = [&](int j, f32x4 v) { *(f32x4*)(trp + tr_w + (((lq + 4 * j) ^ l15) << 4)) = v; };
-        auto tr_get = [&](int t) { const int r = 4 * t + lq; return *(const f32x4*)(trp + r * 256 + (((l15 ^ r) & 15) << 4)); };
-        const uint32_t oPlT = (((uint32_t)(m0 + lq) * (uint32_t)q.ldc2 + (uint32_t)((((gnT & ~7) >> 5) << 6) + ((gnT & ~7) & 31) + ((l15 & 1) ? 32 : 0))) * 2u) | tmask;
-
-        if (has_e) { dmaE(0); dmaE(1); }
-        const uint32_t e_lane = (uint32_t)(l15 * 1024);          // + 16384 for odd row blocks; chunk ((16 wn + 4 j + lq) ^ l15) * 16
-        auto row_loop = [&](auto act_tag, auto drop_tag, auto pl_tag) {
-            constexpr int ACT = decltype(act_tag)::value;          // 0 none, 1 ReLU / ReLU', 2 GELU / GELU'
-            constexpr bool DROP = decltype(drop_tag)::value, PLANES = decltype(pl_tag)::value;
-#pragma unroll 1
-            for (int i = 0; i < 8; ++i) {
-                if (has_e && (i & 1) == 0) vmwait(i == 0 ? 0 : (i == 6 ? 2 : 1));          // quarter i / 2 has landed (all waves: barrier)
-                f32x4 c[NJ];
-                switch (i) {
-                    case 0: for (int j = 0; j < NJ; ++j) c[j] = acc[0][j]; break;
-                    case 1: for (int j = 0; j < NJ; ++j) c[j] = acc[1][j]; break;
-                    case 2: for (int j = 0; j < NJ; ++j) c[j] = acc[2][j]; break;
-                    case 3: for (int j = 0; j < NJ; ++j) c[j] = acc[3][j]; break;
-                    case 4: for (int j = 0; j < NJ; ++j) c[j] = acc[4][j]; break;
-                    case 5: for (int j = 0; j < NJ; ++j) c[j] = acc[5][j]; break;
-                    case 6: for (int j = 0; j < NJ; ++j) c[j] = acc[6][j]; break;
-                    default: for (int j = 0; j < NJ; ++j) c[j] = acc[7][j]; break;
-                }
-                const int gm = gm0 + 16 * i;
-                const uint32_t rowmask = gm < p.M ? 0xffffffffu : 0u;
-                const uint32_t soC = (uint32_t)i * 16u * (uint32_t)p.ldc * 4u, soAux = (uint32_t)i * 16u * (uint32_t)p.ldaux * 4u;
-                const char* ebuf = smem + ((i >> 1) & 1) * P4_EHALF + e_lane + (i & 1) * 16384;
-                f32x4 e[NJ];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) e[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (has_e) {
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) e[j] = *(const f32x4*)(ebuf + (((4 * NJ * wn + 4 * j + lq) ^ l15) << 4));
-                }
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    f32x4 v = c[j] * inv_ab + bias4[j];
-                    if (ACT == 2) {
-                        if (epi == EPI_GELU) {
-                            tr_put(j, v);          // the pre-activation leaves through the transpose patch below
-                            v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
-                        } else {
-                            v.x *= gelu_erf_grad(e[j].x); v.y *= gelu_erf_grad(e[j].y); v.z *= gelu_erf_grad(e[j].z); v.w *= gelu_erf_grad(e[j].w);
-                        }
-                    } else if (ACT == 1) {
-                        if (epi == EPI_RELU) {
-                            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-                        } else {
-                            v.x = e[j].x > 0.f ? v.x : 0.f; v.y = e[j].y > 0.f ? v.y : 0.f; v.z = e[j].z > 0.f ? v.z : 0.f; v.w = e[j].w > 0.f ? v.w : 0.f;
-                        }
-                    }
-                    if (DROP) v = drop_apply4(drop_e, ((uint64_t)gm * (uint64_t)p.N + (uint64_t)(gn0 + 16 * j)) >> 2, v);
-                    if (ACT == 0) v += e[j];                    // e = 0 without a residual
-                    else if (has_res) v += e[j];                // (e is the aux tensor of an activation gradient otherwise)
-                    c[j] = v;
-                    {          // running max |v| over the elements that exist (branch-free)
-                        const uint32_t mk = rowmask & ~((int32_t)colmask[j] >> 31);
-                        const float mx = __uint_as_float(__float_as_uint(v.x) & mk), my = __uint_as_float(__float_as_uint(v.y) & mk);
-                        const float mz = __uint_as_float(__float_as_uint(v.z) & mk), mw = __uint_as_float(__float_as_uint(v.w) & mk);
-                        asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(am) : "v"(mx), "v"(my));
-                        asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(am) : "v"(mz), "v"(mw));
-                    }
-                }
-                if (ACT == 2 && epi == EPI_GELU) {          // the pre-activations (put above), as whole row segments
-                    f32x4 ga[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) ga[t] = tr_get(t);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) buf_store4(rsAuxW, oAuxT, soAux + (uint32_t)(4 * t) * (uint32_t)p.ldaux * 4u, ga[t]);
-                }
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) tr_put(j, c[j]);
-                // all four reads of the patch are requested before the first store: a read issued right in front of the store that
-                // needs it exposes one LDS round trip per store -- 32 per tile, ~130 cycles each on an idle LDS and three times that
-                // beside the partner workgroup's k-loop (measured: 13.7 k cycles per epilogue)
-                f32x4 g4[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) g4[t] = tr_get(t);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 v = g4[t];
-                    buf_store4(rsC, oCT, soC + (uint32_t)(4 * t) * (uint32_t)p.ldc * 4u, v);
-                    if (PLANES) {
-                        uint32_t h0, l0, h1, l1;
-                        splith_pair(v.x, v.y, c_scale, h0, l0);
-                        splith_pair(v.z, v.w, c_scale, h1, l1);
-                        const bool oddl = (l15 & 1) != 0;
-                        const uint32_t r0 = dpp_swap1(oddl ? h0 : l0), r1 = dpp_swap1(oddl ? h1 : l1);
-                        const u32x4_t w = oddl ? u32x4_t{r0, r1, l0, l1} : u32x4_t{h0, h1, r0, r1};
-                        buf_store4u_aux<SEGMM_PLANE_AUX>(rsPl, oPlT, (uint32_t)(16 * i + 4 * t) * (uint32_t)q.ldc2 * 2u, w);
-                    }
-                }
-                if (has_e && (i & 1) == 1 && i < 5) {          // both row blocks of the quarter are read: refill its half with quarter + 2
-                    end_load_segment();
-                    dmaE((i >> 1) + 2);
-                }
-            }
-        };
-        // whole tile, no activation, no dropout, no plane output (the fused projections, the input-gradient GEMMs): unrolled
-        auto fast_loop = [&](auto e_tag) {
-            constexpr bool HAS_E = decltype(e_tag)::value;
-            auto put_block = [&](int i) {
-                const char* ebuf = smem + ((i >> 1) & 1) * P4_EHALF + e_lane + (i & 1) * 16384;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    f32x4 v = acc[i][j] * inv_ab + bias4[j];
-                    if (HAS_E) v += *(const f32x4*)(ebuf + (((4 * NJ * wn + 4 * j + lq) ^ l15) << 4));
-                    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(am) : "v"(v.x), "v"(v.y));
-                    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(am) : "v"(v.z), "v"(v.w));
-                    tr_put(j, v);
-                }
-            };
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                if (HAS_E && (i & 1) == 0) vmwait(i == 0 ? 0 : (i == 6 ? 2 : 1));
-                const uint32_t soC = (uint32_t)i * 16u * (uint32_t)p.ldc * 4u;
-                f32x4 g4[4];          // (the four reads before the first store: see row_loop)
-                if (SEGMM_GEMM_DBG(q) & 8) {          // timing ablation: no LDS transposition (wrong layout)
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { g4[t] = acc[i][t] * inv_ab + bias4[t]; am = fmaxf(am, g4[t].x); }
-                } else {
-                    put_block(i);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) g4[t] = tr_get(t);
-                }
-                if (SEGMM_GEMM_DBG(q) & 4) {          // timing ablation: no store instructions
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) am = fmaxf(am, g4[t].x + g4[t].y + g4[t].z + g4[t].w);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) buf_store4(rsC, oCT, soC + (uint32_t)(4 * t) * (uint32_t)p.ldc * 4u, g4[t]);
-                }
-                STAMPX(i);
-                if (HAS_E && (i & 1) == 1 && i < 5) {
-                    end_load_segment();
-                    dmaE((i >> 1) + 2);
-                }
-            }
-        };
-        const bool fast = full_tile && epi == EPI_NONE && !has_drop && !planes;
-        if (fast) {
-            if (has_e) fast_loop(std::true_type{}); else fast_loop(std::false_type{});
-        } else {
-            using A0 = std::integral_constant<int, 0>; using A1 = std::integral_constant<int, 1>; using A2 = std::integral_constant<int, 2>;
-            using T = std::true_type; using F = std::false_type;
-            auto pick = [&](auto act_tag) {
-                if (has_drop) { if (planes) row_loop(act_tag, T{}, T{}); else row_loop(act_tag, T{}, F{}); }
-                else { if (planes) row_loop(act_tag, F{}, T{}); else row_loop(act_tag, F{}, F{}); }
-            };
-            if (epi == EPI_GELU || epi == EPI_DGELU) pick(A2{});
-            else if (epi == EPI_RELU || epi == EPI_DRELU) pick(A1{});
-            else pick(A0{});
-        }
-    }
-    STAMP(3);
-    if (q.repair) return;          // (the header keeps the first launch's verdict)
-    if (q.c_hdr) {
-        site_commit(q.c_hdr, am, blockIdx.x * 4 + wave, c_scale);
-        if (c_scale > 0.f && scale_writer(blockIdx.x * 4 + wave)) q.c_hdr[0] = c_scale;
-    } else if (p.amax_out) amax_commit(p.amax_out, am, blockIdx.x * 4 + wave);
+    // ---- epilogue (gemm_planes_epi.h): gemm_pl_nt8's for one wave group, with the four reads of the transpose patch requested
+    // before the first store of a row block.  E halves of 32 KB at the bottom of the LDS, the patches behind them.
+    using G = NtEpiGeom<NJ, 1, true>;
+    static_assert(G::BM == P4_BM && G::BN == P4_BN && G::LDS <= P4_LDS, "the epilogue's LDS image fits the k-loop's");
+    nt_epilogue<G>(p, q, acc, smem, sa, sb, c_scale, m0, n0, wave, lane);
 }
 
 }  // namespace segmm
@@ -589,7 +323,8 @@ namespace segmm {
 // LDS-DMA builtin it has seen (it cannot tell which LDS bytes the DMA writes; plain ds_read_b128 loads are not treated that way) --
 // inside a loop that keeps 12 pieces in flight that drains the whole prefetch at every fragment read (first build of this kernel:
 // 0.55x of gemm_pl_tn8).  The asm form is invisible to the pass; every RAW / WAR between a piece and the reads of its bytes is
-// ordered by the explicit s_waitcnt vmcnt(N) + s_barrier of the stream, as in the NT kernel.  (No other code of the kernel uses M0.)
+// ordered by the explicit s_waitcnt vmcnt(N) + s_barrier of the stream, as in the NT kernel.  (No other code of the kernel uses M0.
+// "m0" cannot go on the clobber list: hipcc treats it as a reserved register it does not preserve around the statement, and warns.)
 __device__ __forceinline__ u32x4_t rsrc_words(const void* p, uint32_t bytes) {
     const uint64_t a = (uint64_t)p;
     return u32x4_t{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, bytes, 0x00020000u};
@@ -658,18 +393,11 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
         for (int i = 0; i < 4; ++i) lds_dma16_asm(rsA1, smem + P4_ASTAGE + wave * 4096 + i * 1024, voa[i], ka0 + ka);
     }
 
-    // ---- operand state (all header words requested at once)
-    auto uni = [](float x) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x))); };
-    const float ha0 = q.A.hdr[0], ha1 = q.A.hdr[1], hb0 = q.B.hdr[0], hb1 = q.B.hdr[1];
-    const f32x4 ama = *(const f32x4*)(q.A.hdr + SITE_HDR + lane * 4), amb = *(const f32x4*)(q.B.hdr + SITE_HDR + lane * 4);
-    const float sa0 = uni(ha0), sb0 = uni(hb0);
-    auto planes_ok = [&](float s, float flag, f32x4 v) {
-        const float m = wave_max(fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-        if (!(s > 0.f) || __float_as_uint(flag) != 0u) return false;
-        return !(m > 0.f) || ((m * s >= 0.25f || s >= 0x1p60f) && m * s < 65504.f);
-    };
-    const bool slowA = q.A.f32 != nullptr && !planes_ok(sa0, uni(ha1), ama);          // delayed scale outside its window: fp32 fallback
-    const bool slowB = q.B.f32 != nullptr && !planes_ok(sb0, uni(hb1), amb);
+    // ---- operand state (all header words requested at once, judged by the rule of common.h)
+    const SiteWords wa = site_words(q.A.hdr, lane), wb = site_words(q.B.hdr, lane);
+    const float sa0 = site_scale(wa), sb0 = site_scale(wb);
+    const bool slowA = q.A.f32 != nullptr && !site_usable(wa);          // delayed scale outside its window: fp32 fallback
+    const bool slowB = q.B.f32 != nullptr && !site_usable(wb);
     float sa = sa0, sb = sb0;
 
     // ---- transposed fragment reads: lane = (lq: token octet, qq = (lane >> 2) & 3: token inside a 4-block, pp = lane & 3)

@@ -242,6 +242,40 @@ def test_gemm_p_nt_epilogue_variants(M, N, K, case):
             assert float(hdr[H.SITE_HDR:].max()) == float(Cp.abs().max())
 
 
+def test_gemm_p_nt_repair_launch():
+    """The REPAIR launch of a planes-only NT output (write_c bit 1), as engine._lin_fwd issues it: a site that is usable under the
+    scale it was written with (the exact one, or one a factor 4 below it) is left alone bit for bit; one whose delayed scale was
+    too large (planes overflowed, flag up) or too small (maximum below the fp16 window) has its planes rewritten with the exact scale of the recorded maxima -- the planes the
+    stand-alone split pass makes of the fp32 result -- while the header keeps the first launch's verdict.  130 x 96 x 64: ragged
+    in M for the 128- and the 256-row tiles, narrower than any tile, two k-tiles."""
+    H = _abi()
+    M, N, K = 130, 96, 64
+    A, W = _rand(M, K, seed=21), _rand(N, K, seed=22, scale=0.1)
+    pa, pw = H.to_planes(A, M, K), H.to_planes(W, N, K, keep_f32=False)
+    C = torch.empty(M, N, device=DEV)
+    H.gemm_p(H.LAYOUT_NT, M, N, K, pa, pw, C, N)
+    amax = float(C.abs().max())
+    s = 2.0 ** (15 - math.frexp(amax)[1])          # the power of two with amax * s in [2^14, 2^15): f16_scale_of
+    assert 2.0 ** 14 <= amax * s < 2.0 ** 15
+    # ("in window": usable but not the exact scale -- a repair that wrongly recomputed would rewrite the planes at s, not s / 4)
+    for case, first in (("exact", s), ("in window", s / 4), ("too large", s * 2.0 ** 30), ("too small", s * 2.0 ** -30)):
+        pl, hdr, sc, po = _po(H, M, N, first)
+        kw = dict(c_pt=H.PT(pl, hdr, M, N), c_scale_ptr=sc.data_ptr(), write_c=False)
+        H.gemm_p(H.LAYOUT_NT, M, N, K, pa, pw, None, N, **kw)
+        pl0, hdr0 = pl.clone(), hdr.clone()
+        assert float(hdr0[0]) == first and float(hdr0[H.SITE_HDR:].max()) == amax, case
+        assert (float(hdr0[1]) != 0.0) is (case == "too large"), case
+        H.gemm_p(H.LAYOUT_NT, M, N, K, pa, pw, None, N, repair=True, **kw)
+        if case in ("exact", "in window"):
+            assert torch.equal(pl.view(torch.int16), pl0.view(torch.int16)), case
+        else:
+            assert not torch.equal(pl.view(torch.int16), pl0.view(torch.int16)), case
+            ref_pl, _ = _ref_planes(H, C, M, N, s)
+            assert torch.equal(pl, ref_pl), case
+        # the header keeps the first launch's verdict: scale word, flag (and the maxima) as the first launch left them
+        assert torch.equal(hdr.view(torch.int32), hdr0.view(torch.int32)), case
+
+
 def test_gemm_p_overflow_flag_takes_fp32_path():
     """A delayed scale that has become too large: the producer raises the flag, the consumer reads the fp32 copy instead of
     the (infinite) planes -- same result as with exact planes."""
