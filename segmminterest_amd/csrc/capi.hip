@@ -1393,8 +1393,9 @@ int segmm_label_stats_unpack(const float* gathered, int G, int B, float* v_all, 
 }
 
 int segmm_zero_rows(float* table, int width, const int64_t* ids, int n, int64_t n_rows, segmm_stream_t stream) {
-    SEGMM_REQUIRE(table && ids && width > 0 && width % 4 == 0 && aligned16(table) && n_rows > 0, "zero_rows: arguments");
-    if (n <= 0) return 0;
+    SEGMM_REQUIRE(table && width > 0 && width % 4 == 0 && aligned16(table) && n_rows > 0, "zero_rows: arguments");
+    if (n <= 0) return 0;          // an empty list (torch hands out a null pointer for it) clears nothing
+    SEGMM_REQUIRE(ids, "zero_rows: null id list");
     hipLaunchKernelGGL(zero_rows_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, table, width, (const long long*)ids, (long long)n_rows);
     LAUNCH_CHECK();
     return 0;
