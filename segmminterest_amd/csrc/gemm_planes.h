@@ -17,7 +17,8 @@
 // kernel takes the operand from its fp32 copy instead and splits it on the fly with the exact scale of the partial
 // maxima (slow path, staged through registers; results identical in accuracy, never silently wrong).  The verdict is ONE rule,
 // common.h's site_window_ok: every generation of these kernels (this file; gemm_planes8.h and gemm_planes4.h, which share
-// their epilogue and rare-path staging through gemm_planes_epi.h) and the attention kernels judge a header through it.
+// their NT epilogue and rare-path staging through gemm_planes_epi.h, their TN token-row image and output code through
+// gemm_planes_tn.h) and the attention kernels judge a header through it.
 //
 // NT kernel: 256 x 256 x 32 tile, 512 threads = 8 waves as 2 (m) x 4 (n), 128 x 64 per wave = 4 x 2 MFMA tiles x 3
 // products, 128 accumulator registers; two 64 KB LDS stages (A 256 rows x 128 B, B 256 rows x 128 B); one barrier per
@@ -371,33 +372,44 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_nt(const GemmArgs p, const PGe
 // 64-byte bank windows (conflict-free per 32-lane half); the permutation is applied to the DMA source address.
 // Split-K over blockIdx.z (partial slabs + splitk_reduce), 256 x 256 tile, 8 waves as 2 (m) x 4 (n).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 lds_tr8(const char* a) {          // 8 tokens (two 4-token blocks, 4 KB apart) of this lane's feature
+template <int STRIDE>          // the one transposed fragment read: 8 tokens (two 4-token blocks, STRIDE bytes apart) of this lane's feature
+__device__ __forceinline__ f32x4 lds_tr8(const char* a) {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 4096));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + STRIDE));
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(f32x4, v);
 }
+// Tile and token slab of a TN workgroup (tile BM x 256; all three generations).  Workgroups are dealt to the 8 XCDs round-robin
+// in dispatch order (x fastest, then z): each XCD gets a run of consecutive (k-slab, tile) pairs, so the tiles sharing a token
+// slab of A or B meet in one L2 (hit rate 44 % -> see DESIGN.md).  do_colsum: the bias gradient rides in the first column tile.
+template <int BM>
+struct TnTile {
+    int kz, lb, m0, n0, kbeg, kend, nkt;
+    bool do_colsum;
+    __device__ __forceinline__ TnTile(const GemmArgs& p, const PGemmX& q) {
+        const int ntile = p.nbm * p.nbn;
+        const int lg = xcd_remap(blockIdx.x + ntile * blockIdx.z, ntile * gridDim.z);
+        kz = lg / ntile, lb = lg - kz * ntile;
+        m0 = (lb / p.nbn) * BM, n0 = (lb % p.nbn) * PBN;
+        kbeg = kz * p.k_per_split;
+        kend = min(p.K, kbeg + p.k_per_split);
+        nkt = (kend - kbeg + 31) >> 5;
+        do_colsum = q.colsum_out != nullptr && (lb % p.nbn) == 0;
+    }
+};
 
 __global__ __launch_bounds__(512, 2) void gemm_pl_tn(const GemmArgs p, const PGemmX q) {
     __shared__ __attribute__((aligned(16))) char smem[2 * PSTAGE];      // two stages x (A: 32 tokens x 1 KB | B: 32 tokens x 1 KB)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    // workgroups are dealt to the 8 XCDs round-robin in dispatch order (x fastest, then z): give each XCD a run of
-    // consecutive (k-slab, tile) pairs, so the tiles sharing a token slab of A or B meet in one L2 (hit rate 44 % -> see DESIGN.md)
-    const int ntile = p.nbm * p.nbn;
-    const int lg = xcd_remap(blockIdx.x + ntile * blockIdx.z, ntile * gridDim.z);
-    const int kz = lg / ntile, lb = lg - kz * ntile;
-    const int m0 = (lb / p.nbn) * PBM, n0 = (lb % p.nbn) * PBN;
-    const int kbeg = kz * p.k_per_split;
-    const int kend = min(p.K, kbeg + p.k_per_split);
-    const int nkt = (kend - kbeg + 31) >> 5;
-
+    const TnTile<PBM> T(p, q);
+    const int kz = T.kz, m0 = T.m0, n0 = T.n0, kbeg = T.kbeg, kend = T.kend, nkt = T.nkt;
     // bias gradient folded in: the workgroups of the first column tile also form sum_k A[k, m] -- one more MFMA pair per
     // k16 step and wave against an all-ones B fragment (wave (wm, wn) takes A block i = wn of its 128 rows), instead of a
     // separate column-sum pass over the whole fp32 dY tensor
-    const bool do_colsum = q.colsum_out != nullptr && (lb % p.nbn) == 0;
+    const bool do_colsum = T.do_colsum;
     const float sa_hdr = q.A.hdr[0], sb_hdr = q.B.hdr[0];
     const bool slowA = q.A.f32 != nullptr && !site_planes_ok(q.A.hdr, sa_hdr, lane);
     const bool slowB = q.B.f32 != nullptr && !site_planes_ok(q.B.hdr, sb_hdr, lane);
@@ -428,7 +440,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn(const GemmArgs p, const PGe
         voa[i] = (uint32_t)t * (uint32_t)q.A.ld2 * 2u + (uint32_t)m0 * 4u + inrow;
         vob[i] = (uint32_t)t * (uint32_t)q.B.ld2 * 2u + (uint32_t)n0 * 4u + inrow;
     }
-    // slow path: fp32 [token][feature] -> exact split -> the same LDS image; a thread converts 8 consecutive features of one token
+    // slow path: fp32 [token][feature] -> exact split -> the same LDS image; a thread converts 8 consecutive features of one token.
+    // NOT gemm_planes_tn.h's tn_image_put: this kernel's image has no half swap (its 32 x 32 x 16 fragments put one token octet in a
+    // 32-lane half, so no two lane groups read the same features of tokens 8 apart) and is written 16 bytes per plane and thread.
     auto slow_stage = [&](const PlaneOperand& op, float sc, int k0, char* dst, int f0, int nfeat) {
 #pragma unroll 1
         for (int jj = 0; jj < 2; ++jj) {
@@ -483,19 +497,19 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn(const GemmArgs p, const PGe
             f32x4 bh[2], bl[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                bh[j] = lds_tr8(st + fb[2 * j] + s * 16384);
-                bl[j] = lds_tr8(st + fb[2 * j + 1] + s * 16384);
+                bh[j] = lds_tr8<4096>(st + fb[2 * j] + s * 16384);
+                bl[j] = lds_tr8<4096>(st + fb[2 * j + 1] + s * 16384);
             }
             if constexpr (CS) {
-                const f32x4 ch = lds_tr8(st + fcs_h + s * 16384);
-                const f32x4 cl = lds_tr8(st + fcs_l + s * 16384);
+                const f32x4 ch = lds_tr8<4096>(st + fcs_h + s * 16384);
+                const f32x4 cl = lds_tr8<4096>(st + fcs_l + s * 16384);
                 accb = mfma_x<true>(cl, ones, accb);
                 accb = mfma_x<true>(ch, ones, accb);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const f32x4 ah = lds_tr8(st + fa[2 * (i & 1)] + (i >> 1) * 256 + s * 16384);
-                const f32x4 al = lds_tr8(st + fa[2 * (i & 1) + 1] + (i >> 1) * 256 + s * 16384);
+                const f32x4 ah = lds_tr8<4096>(st + fa[2 * (i & 1)] + (i >> 1) * 256 + s * 16384);
+                const f32x4 al = lds_tr8<4096>(st + fa[2 * (i & 1) + 1] + (i >> 1) * 256 + s * 16384);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     f32x16 c = acc[i][j];

@@ -315,9 +315,7 @@ namespace segmm {
 //     A (shared):  32 tokens x 512 B (128 features x [hi | lo]) per stage; one LDS-DMA instruction moves TWO token rows
 //     B (private): wave wn stages only ITS 64 features: 256 B per token; the ring's three half-slots hold 16 tokens each (4 KB; a
 //                  k-tile is the halves 2t = tokens 0-15 and 2t+1 = tokens 16-31); one LDS-DMA instruction moves FOUR token rows
-// LDS image of a token row (512 / 256 B): pieces of 64 B (piece = 2 * feature block + plane); piece c of token t sits at physical
-// piece c ^ (t & 3), and inside a piece the two 32-byte halves are swapped for tokens with bit 3 set -- gemm_pl_tn8's permutation
-// (row pitches of 512 and 256 B are multiples of the 256-byte bank period, like its 1 KB): conflict-free transposed reads.
+// LDS image of a token row (512 / 256 B): gemm_pl_tn8's, the token-row image of gemm_planes_tn.h at these two row pitches.
 // Same MFMA order per element and the same split ranges as gemm_pl_tn8: the results are BITWISE its results.
 // LDS-DMA written as inline asm.  hipcc's waitcnt pass puts an s_waitcnt vmcnt(0) in front of every ds_read_b64_tr_b16 that follows an
 // LDS-DMA builtin it has seen (it cannot tell which LDS bytes the DMA writes; plain ds_read_b128 loads are not treated that way) --
@@ -337,13 +335,6 @@ __device__ __forceinline__ void lds_dma16_asm(u32x4_t r, const void* lds_wave_ba
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" :: "v"(voff), "s"(r), "s"(la), "s"(soff) : "memory");
 #endif
 }
-__device__ __forceinline__ f32x4 lds_tr8s(const char* a, int stride4) {          // 8 tokens (two 4-token blocks, stride4 bytes apart) of this lane's feature
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + stride4));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f32x4, v);
-}
 
 __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PGemmX q) {
     constexpr int NJ = 4;
@@ -351,31 +342,26 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wn = wave;
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int ntile = p.nbm * p.nbn;
-    const int lg = xcd_remap(blockIdx.x + ntile * blockIdx.z, ntile * gridDim.z);          // tiles of one token slab meet in one L2
-    const int kz = lg / ntile, lb = lg - kz * ntile;
-    const int m0 = (lb / p.nbn) * P4_BM, n0 = (lb % p.nbn) * P4_BN;
-    const int kbeg = kz * p.k_per_split;
-    const int kend = min(p.K, kbeg + p.k_per_split);
-    const int nkt = (kend - kbeg + 31) >> 5;
-    const bool do_colsum = q.colsum_out != nullptr && (lb % p.nbn) == 0;
+    const int lq = lane >> 4;
+    const TnTile<P4_BM> T(p, q);          // tiles of one token slab meet in one L2
+    const int m0 = T.m0, n0 = T.n0, kbeg = T.kbeg, kend = T.kend, nkt = T.nkt;
+    const bool do_colsum = T.do_colsum;
     if (P4_EPI_PRIO) __builtin_amdgcn_s_setprio(P4_EPI_PRIO);
 
     // ---- LDS-DMA.  A: piece 4 wave + i of 16 = tokens 2 piece, 2 piece + 1 (lanes 0-31 / 32-63), 32 chunks of 16 B per token;
     // B: piece pc of 8 = tokens 4 pc .. 4 pc + 3 (16 lanes each), 16 chunks per token, half = pc >> 2.
-    // physical chunk l of token t holds logical piece (l >> 2) ^ (t & 3), chunk (l & 3) ^ (2 * bit 3 of t)
+    // Physical chunk l of token t fetches tn_image_src(l, t).
     const u32x4_t rsA = rsrc_words(q.A.p, q.A.bytes), rsB = rsrc_words(q.B.p, q.B.bytes);
     uint32_t voa[4], vob[8];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int tok = 2 * (4 * wave + i) + (lane >> 5), l = lane & 31;
-        voa[i] = (uint32_t)tok * (uint32_t)q.A.ld2 * 2u + (uint32_t)m0 * 4u + (uint32_t)((((l >> 2) ^ (tok & 3)) << 6) + (((l & 3) ^ (((tok >> 3) & 1) << 1)) << 4));
+        voa[i] = (uint32_t)tok * (uint32_t)q.A.ld2 * 2u + (uint32_t)m0 * 4u + tn_image_src(l, tok);
     }
 #pragma unroll
     for (int pc = 0; pc < 8; ++pc) {
         const int tok = 4 * pc + (lane >> 4), l = lane & 15;
-        vob[pc] = (uint32_t)tok * (uint32_t)q.B.ld2 * 2u + (uint32_t)(n0 + 64 * wn) * 4u + (uint32_t)((((l >> 2) ^ (tok & 3)) << 6) + (((l & 3) ^ (((tok >> 3) & 1) << 1)) << 4));
+        vob[pc] = (uint32_t)tok * (uint32_t)q.B.ld2 * 2u + (uint32_t)(n0 + 64 * wn) * 4u + tn_image_src(l, tok);
     }
     char* const bring = smem + P4_BOFF + wave * P4_BRING;
     const uint32_t ka = (uint32_t)q.A.ld2 * 64u, kb = (uint32_t)q.B.ld2 * 64u;          // bytes per k-tile of 32 token rows
@@ -401,21 +387,9 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
     float sa = sa0, sb = sb0;
 
     // ---- transposed fragment reads: lane = (lq: token octet, qq = (lane >> 2) & 3: token inside a 4-block, pp = lane & 3)
-    const int qq = (lane >> 2) & 3, pp = lane & 3;
-    const uint32_t hsw = (uint32_t)((lq & 1) << 5);          // tokens with bit 3 set: the 32-byte halves of a piece are swapped
-    const uint32_t base_a = (uint32_t)((8 * lq + qq) * 512 + 8 * pp);
-    const uint32_t base_b = (uint32_t)((8 * (lq & 1) + qq) * 256 + 8 * pp);          // inside the half-slot of token octets (lq >> 1)
-    // A tile i (16 features), plane pl: base_a + (((2 (i >> 1) + pl) ^ qq) << 6) + ((32 (i & 1)) ^ hsw); B tile j likewise on base_b.
-    // The XOR with qq touches the two low bits of the piece index only: four per-lane offsets xa[v], v = 2 (feature block & 1) + plane,
-    // a constant 256 B per feature-block pair, and the per-lane half offset
-    uint32_t xa[4], xb[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) { xa[v] = base_a + (uint32_t)((v ^ qq) << 6); xb[v] = base_b + (uint32_t)((v ^ qq) << 6); }
-    const uint32_t hh[2] = {hsw, 32u ^ hsw};
-    auto frag_off = [&](int i, int pl, const uint32_t* x) -> uint32_t {
-        const int fbk = i >> 1;
-        return x[2 * (fbk & 1) + pl] + (uint32_t)((fbk >> 1) * 256) + hh[i & 1];
-    };
+    // A tile i (16 features), plane pl: xa(i, pl) in rows of 512 B; B tile j: xb(j, pl) in rows of 256 B inside the half-slot of
+    // token octets (lq >> 1)
+    const TnFrag xa = tn_frag_off(lane, lq, 512), xb = tn_frag_off(lane, lq & 1, 256);
 
     f32x4 acc[8][NJ];
 #pragma unroll
@@ -425,13 +399,13 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
     f32x4 accb[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     f32x4 bh[NJ], bl[NJ], ah[2], al[2];
     auto rdA = [&](const char* st, int i, int buf) {
-        ah[buf] = lds_tr8s(st + frag_off(i, 0, xa), 2048);
-        al[buf] = lds_tr8s(st + frag_off(i, 1, xa), 2048);
+        ah[buf] = lds_tr8<2048>(st + xa(i, 0));
+        al[buf] = lds_tr8<2048>(st + xa(i, 1));
     };
     // B: token octets 0, 1 (lanes lq < 2) in half `h0`, octets 2, 3 in half `h1`: a per-lane base
     auto rdB = [&](int j, const char* lane_half) {
-        bh[j] = lds_tr8s(lane_half + frag_off(j, 0, xb), 1024);
-        bl[j] = lds_tr8s(lane_half + frag_off(j, 1, xb), 1024);
+        bh[j] = lds_tr8<1024>(lane_half + xb(j, 0));
+        bl[j] = lds_tr8<1024>(lane_half + xb(j, 1));
     };
     auto mma1 = [&](int r, int j, int buf) {
         f32x4 c = acc[r][j];
@@ -522,13 +496,6 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the early pieces have landed before anything is restaged
         if (slowA) sa = site_exact_scale(q.A.hdr, (float*)(smem + P4_LDS - 64), tid, 256);
         if (slowB) sb = site_exact_scale(q.B.hdr, (float*)(smem + P4_LDS - 64), tid, 256);
-        auto put = [&](char* row, int f, f32x4 x, float sc, int t) {          // 4 features f .. f+3 (f % 4 == 0, relative to the staged row) of token t
-            uint32_t hh0, l0, hh1, l1;
-            splith_pair(x.x, x.y, sc, hh0, l0); splith_pair(x.z, x.w, sc, hh1, l1);
-            const int b = f >> 5, g8 = (f & 31) >> 2, cp = (g8 >> 1) ^ (((t >> 3) & 1) << 1), sw = t & 3;
-            *(uint2*)(row + (((2 * b) ^ sw) << 6) + (cp << 4) + ((g8 & 1) << 3)) = make_uint2(hh0, hh1);
-            *(uint2*)(row + (((2 * b + 1) ^ sw) << 6) + (cp << 4) + ((g8 & 1) << 3)) = make_uint2(l0, l1);
-        };
 #pragma unroll 1
         for (int t = 0; t < nkt; ++t) {
             __syncthreads();
@@ -539,7 +506,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
                     const int tk = e >> 5, f = (e & 31) * 4;
                     f32x4 x = {0.f, 0.f, 0.f, 0.f};
                     if (k0 + tk < kend && m0 + f < p.M) x = *(const f32x4*)(q.A.f32 + (size_t)(k0 + tk) * q.A.ldf + m0 + f);
-                    put(smem + tk * 512, f, x, sa, tk);
+                    tn_image_put(smem + tk * 512, f, x, sa, tk);
                 }
             } else {
 #pragma unroll
@@ -551,7 +518,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
                     const int tk = e >> 4, f = (e & 15) * 4;
                     f32x4 x = {0.f, 0.f, 0.f, 0.f};
                     if (k0 + tk < kend && n0 + 64 * wn + f < p.N) x = *(const f32x4*)(q.B.f32 + (size_t)(k0 + tk) * q.B.ldf + n0 + 64 * wn + f);
-                    put(bring + (tk >> 4) * P4_BHALF + (tk & 15) * 256, f, x, sb, tk);
+                    tn_image_put(bring + (tk >> 4) * P4_BHALF + (tk & 15) * 256, f, x, sb, tk);
                 }
             } else {
 #pragma unroll
@@ -572,37 +539,10 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
         __syncthreads();
     }
 
-    // ---- outputs
-    const bool split = gridDim.z > 1;
-    const float inv_a = 1.f / sa;
-    if (do_colsum && lq == 0) {          // every row of accb holds the column sums: lanes of column group 0 own 16 features each
-        float* dst = split ? q.colsum_ws + (size_t)kz * p.M : q.colsum_out;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int m = m0 + 16 * (2 * wn + e) + l15;
-            if (m < p.M) dst[m] = accb[e].x * inv_a;
-        }
-    }
-    const float inv_ab = inv_a * (1.f / sb);
-    float* Cout = split ? p.C + (size_t)kz * (size_t)p.slab_stride : p.C;
-    const __amdgpu_buffer_rsrc_t rsC = make_rsrc(Cout, (uint32_t)((((long long)p.M - 1) * p.ldc + p.N) * 4));
-    // whole 256-byte row segments through the wave's transpose patch (see gemm_pl_nt8)
-    char* trp = smem + P4_PATCH + wave * 4096;
-    const int gnT = n0 + wn * 64 + 4 * l15;
-    const uint32_t oCT = (((uint32_t)(m0 + lq) * (uint32_t)p.ldc + (uint32_t)gnT) * 4u) | (gnT < p.N ? 0u : BUF_OOB);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *(f32x4*)(trp + l15 * 256 + (((lq + 4 * j) ^ l15) << 4)) = acc[i][j] * inv_ab;
-        f32x4 g4[4];          // (the four reads before the first store: see gemm_pl_nt4's row_loop)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int r = 4 * t + lq;
-            g4[t] = *(const f32x4*)(trp + r * 256 + (((l15 ^ r) & 15) << 4));
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) buf_store4k(rsC, oCT, (uint32_t)(16 * i + 4 * t) * (uint32_t)p.ldc * 4u, g4[t]);
-    }
+    // ---- outputs (gemm_planes_tn.h): gemm_pl_tn8's for one wave group, the four patch reads of a row block before its first store
+    using G = TnOutGeom<1, true>;
+    static_assert(G::BM == P4_BM && G::PATCH == P4_PATCH && G::LDS <= P4_LDS, "the patches where the NT epilogue has its own");
+    tn_outputs<G>(p, q, acc, accb, smem, sa, sb, T, wave, lane);
 }
 
 }  // namespace segmm

@@ -39,7 +39,7 @@
 //  * The first DMA pieces leave before the site headers are read (their addresses depend on blockIdx only); the headers
 //    (two dependent global reads under load) are fetched while the first k-tiles fly.
 #pragma once
-#include "gemm_planes_epi.h"
+#include "gemm_planes_tn.h"
 
 namespace segmm {
 
@@ -231,11 +231,8 @@ namespace segmm {
 // wave-instruction per row, fragments by ds_read_b64_tr_b16 (hardware transpose: per 16-lane group 4 tokens x 16 features,
 // a lane ends up with 8 consecutive tokens of ITS feature -- the 16 x 16 x 32 operand form directly).
 //
-// LDS image of a token row (1 KB): 16 pieces of 64 B (piece = 2 * feature block + plane); piece c of token t sits at
-// physical piece c ^ (t & 3) -- the four token rows of a transposed read fall into four different 64-byte bank windows -- and
-// inside a piece the two 32-byte halves (16 features each) are swapped for tokens with bit 3 set: the two 16-lane groups of a
-// 32-lane half read the SAME 16 features of tokens 8 apart (16 x 16 x 32: lane group = token octet), which would otherwise hit
-// the same banks twice.  Both permutations are applied to the DMA source address.
+// LDS image of a token row (1 KB = 16 pieces of 64 B): the token-row image of gemm_planes_tn.h, which also holds its DMA source
+// rule, the fallback's writer, the fragment-read offsets and the output code (shared with gemm_pl_tn4).
 //
 // Schedule per k-tile t (stage t & 1; g0 = waves 0-3 = features 0-127 of A, g1 one segment behind):
 //     L(t,P0): tr-reads of B (all 64 columns of the wave) and A sub-tile 0; DMA of the group's 16 token rows of A(t+1)
@@ -249,37 +246,24 @@ namespace segmm {
 // The bias gradient (column sums of A over k) rides along in the workgroups of the first column tile: wave (wm, wn) adds
 // one MFMA pair per phase against an all-ones fragment for its m-tile wn.  Output: split-K slabs (plain float4 stores from the
 // accumulators, C^T trick as in gemm_pl_nt8) combined by splitk_reduce, or C itself for a single split.
-__device__ __forceinline__ f32x4 lds_tr8b(const char* a) {          // 8 tokens (two 4-token blocks, 4 KB apart) of this lane's feature
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 4096));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f32x4, v);
-}
-
 __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PGemmX q) {
     // two stages x (A: 32 tokens x 1 KB | B: 32 tokens x 1 KB) + a 4 KB transpose patch per wave for the output stores
     __shared__ __attribute__((aligned(16))) char smem[2 * PSTAGE + 8 * 4096];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wn = wave & 3;
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int ntile = p.nbm * p.nbn;
-    const int lg = xcd_remap(blockIdx.x + ntile * blockIdx.z, ntile * gridDim.z);          // tiles of one token slab meet in one L2
-    const int kz = lg / ntile, lb = lg - kz * ntile;
-    const int m0 = (lb / p.nbn) * PBM, n0 = (lb % p.nbn) * PBN;
-    const int kbeg = kz * p.k_per_split;
-    const int kend = min(p.K, kbeg + p.k_per_split);
-    const int nkt = (kend - kbeg + 31) >> 5;
-    const bool do_colsum = q.colsum_out != nullptr && (lb % p.nbn) == 0;
+    const int lq = lane >> 4;
+    const TnTile<PBM> T(p, q);          // tiles of one token slab meet in one L2
+    const int m0 = T.m0, n0 = T.n0, kbeg = T.kbeg, kend = T.kend, nkt = T.nkt;
+    const bool do_colsum = T.do_colsum;
 
     // ---- LDS-DMA: piece = one token row (1 KB); group g fetches rows t = 16 g + 4 wn + i (i < 4) of both operands.  The row
-    // and the tile's feature offset are wave-uniform (scalar offset of the instruction); per lane only the position inside the row:
-    // physical 16-byte chunk `lane` of row t holds logical piece (lane >> 2) ^ (t & 3), chunk (lane & 3) ^ (2 * bit 3 of t) --
-    // t & 3 = i and bit 3 of t = wn >> 1 here, so the offset of piece i is inrow0 ^ (i << 6)
+    // and the tile's feature offset are wave-uniform (scalar offset of the instruction); per lane only the position inside the row,
+    // tn_image_src(lane, t).  Here t & 3 = i and bit 3 of t = wn >> 1, and i enters the formula only as an XOR on the piece index
+    // (bits 6, 7 of the offset): tn_image_src(lane, t0 + i) = tn_image_src(lane, t0) ^ (i << 6)
     const __amdgpu_buffer_rsrc_t rsA = make_rsrc(q.A.p, q.A.bytes), rsB = make_rsrc(q.B.p, q.B.bytes);
     const int t0 = 16 * grp + 4 * wn;
-    const uint32_t inrow0 = (uint32_t)(((lane >> 2) << 6) + (((lane & 3) ^ ((wn >> 1) << 1)) << 4));
+    const uint32_t inrow0 = tn_image_src(lane, t0);
     auto dmaA_pl = [&](int kt) {
         char* st = smem + (kt & 1) * PSTAGE + t0 * 1024;
         const uint32_t so = (uint32_t)(kbeg + kt * 32 + t0) * (uint32_t)q.A.ld2 * 2u + (uint32_t)m0 * 4u;
@@ -317,12 +301,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
             const int t = t0 + i, gk = kbeg + kt * 32 + t, gf = f0 + lane * 4;
             f32x4 x = {0.f, 0.f, 0.f, 0.f};
             if (gk < kend && gf < nfeat) x = *(const f32x4*)(op.f32 + (size_t)gk * op.ldf + gf);
-            uint32_t hh0, l0, hh1, l1;
-            splith_pair(x.x, x.y, sc, hh0, l0); splith_pair(x.z, x.w, sc, hh1, l1);
-            // 8-byte group g8 = lane & 7 of feature block b = lane >> 3: 16-byte chunk g8 >> 1 (halves swapped for tokens with bit 3 set)
-            const int b = lane >> 3, g8 = lane & 7, cp = (g8 >> 1) ^ (((t >> 3) & 1) << 1), sw = t & 3;
-            *(uint2*)(dst + t * 1024 + (((2 * b) ^ sw) << 6) + (cp << 4) + ((g8 & 1) << 3)) = make_uint2(hh0, hh1);
-            *(uint2*)(dst + t * 1024 + (((2 * b + 1) ^ sw) << 6) + (cp << 4) + ((g8 & 1) << 3)) = make_uint2(l0, l1);
+            tn_image_put(dst + t * 1024, lane * 4, x, sc, t);
         }
     };
     auto dmaA = [&](int kt) { if (slowA) stage_f32(q.A, sa, kt, m0, p.M, smem + (kt & 1) * PSTAGE); else dmaA_pl(kt); };
@@ -336,17 +315,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
     }
 
     // ---- transposed fragment reads: lane = (g = lq: token octet, qq = (lane >> 2) & 3: token inside a 4-block, pp = lane & 3)
-    const int qq = (lane >> 2) & 3, pp = lane & 3;
-    const uint32_t lane_base = (uint32_t)((8 * lq + qq) * 1024 + 4 * pp * 2);
-    const uint32_t hsw = (uint32_t)((lq & 1) << 5);          // tokens 8 .. 15 and 24 .. 31 (bit 3 set): the 32-byte halves of a piece are swapped
-    // A tile i (16 features) of phase mh, plane pl: lane part fr[i >> 1][pl] + (32 (i & 1)) ^ hsw, uniform part (2 wm + mh) * 256;
-    // B tile j: the same lane part, uniform part 32768 + 256 wn
-    uint32_t fr[2][2];
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) fr[hb][pl] = lane_base + (uint32_t)(((2 * hb + pl) ^ qq) << 6);
-    const uint32_t h0 = hsw, h1 = 32u ^ hsw;          // byte offset of the even / odd 16-feature half inside the piece
+    // A tile i (16 features) of phase mh, plane pl: lane part fr(i, pl), uniform part (2 wm + mh) * 256; B tile j: the same lane
+    // part, uniform part 32768 + 256 wn
+    const TnFrag fr = tn_frag_off(lane, lq, 1024);
     const int ua = grp * 2 * 256, ub = 32768 + wn * 256;          // wave-uniform parts
 
     f32x4 acc[8][4];
@@ -360,16 +331,16 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
         const char* sa_ = st + ua + mh * 256;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ah[i] = lds_tr8b(sa_ + fr[i >> 1][0] + ((i & 1) ? h1 : h0));
-            al[i] = lds_tr8b(sa_ + fr[i >> 1][1] + ((i & 1) ? h1 : h0));
+            ah[i] = lds_tr8<4096>(sa_ + fr.x[2 * (i >> 1)] + fr.h[i & 1]);
+            al[i] = lds_tr8<4096>(sa_ + fr.x[2 * (i >> 1) + 1] + fr.h[i & 1]);
         }
     };
     auto readB = [&](const char* st) {
         const char* sb_ = st + ub;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            bh[j] = lds_tr8b(sb_ + fr[j >> 1][0] + ((j & 1) ? h1 : h0));
-            bl[j] = lds_tr8b(sb_ + fr[j >> 1][1] + ((j & 1) ? h1 : h0));
+            bh[j] = lds_tr8<4096>(sb_ + fr.x[2 * (j >> 1)] + fr.h[j & 1]);
+            bl[j] = lds_tr8<4096>(sb_ + fr.x[2 * (j >> 1) + 1] + fr.h[j & 1]);
         }
     };
     auto mma = [&](auto mh_tag, auto cs_tag) {
@@ -434,35 +405,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
     };
     if (do_colsum) k_loop(std::true_type{}); else k_loop(std::false_type{});
 
-    // ---- outputs
-    const bool split = gridDim.z > 1;
-    const float inv_a = 1.f / sa;
-    const float nanv = 0.f;
-    if (do_colsum && lq == 0) {          // every row of accb holds the column sums: lanes of column group 0 own 16 features each
-        float* dst = split ? q.colsum_ws + (size_t)kz * p.M : q.colsum_out;
-#pragma unroll
-        for (int mh = 0; mh < 2; ++mh) {
-            const int m = m0 + grp * 128 + mh * 64 + 16 * wn + l15;
-            if (m < p.M) dst[m] = accb[mh].x * inv_a + nanv;
-        }
-    }
-    const float inv_ab = inv_a * (1.f / sb);
-    float* Cout = split ? p.C + (size_t)kz * (size_t)p.slab_stride : p.C;
-    const __amdgpu_buffer_rsrc_t rsC = make_rsrc(Cout, (uint32_t)((((long long)p.M - 1) * p.ldc + p.N) * 4));
-    // whole 256-byte row segments through the wave's transpose patch (see gemm_pl_nt8: 16-byte-per-row stores drain 3.5x slower)
-    char* trp = smem + 2 * PSTAGE + wave * 4096;
-    const int gnT = n0 + wn * 64 + 4 * l15;
-    const uint32_t oCT = (((uint32_t)(m0 + grp * 128 + lq) * (uint32_t)p.ldc + (uint32_t)gnT) * 4u) | (gnT < p.N ? 0u : BUF_OOB);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *(f32x4*)(trp + l15 * 256 + (((lq + 4 * j) ^ l15) << 4)) = acc[i][j] * inv_ab + nanv;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int r = 4 * t + lq;
-            buf_store4k(rsC, oCT, (uint32_t)(16 * i + 4 * t) * (uint32_t)p.ldc * 4u, *(const f32x4*)(trp + r * 256 + (((l15 ^ r) & 15) << 4)));
-        }
-    }
+    // ---- outputs (gemm_planes_tn.h): two wave groups, each read of the transpose patch in front of its store
+    using G = TnOutGeom<2, false>;
+    static_assert(G::BM == PBM && G::LDS == sizeof(smem), "the patches behind the two stages");
+    tn_outputs<G>(p, q, acc, accb, smem, sa, sb, T, wave, lane);
 }
 
 }  // namespace segmm

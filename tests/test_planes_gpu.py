@@ -309,6 +309,58 @@ def test_gemm_p_overflow_flag_takes_fp32_path():
     assert float((C1 - C0).abs().max()) <= 2e-6 * float(C0.abs().max())
 
 
+# 256 x 256 x 200: one tile of gemm_pl_tn8 / two row tiles of gemm_pl_tn4, seven k-tiles (both LDS stages, the three-slot B ring goes
+# round twice), a token tail of 8; with 2 splits: slabs of 128 and 72 tokens, column sums through the workspace.  K = 8: one k-tile
+# (every nkt > 1 / t + 1 < nkt edge, gemm_pl_tn4's zero-length descriptors).  N = 512: two column tiles, column sums in the first only.
+# M = 128: gemm_pl_tn4 alone (the round-2 kernel under "round3").
+@pytest.mark.parametrize("case", ["flag_A", "flag_B", "flag_both", "never_written"])
+@pytest.mark.parametrize("M,N,K,splits", [(256, 256, 200, 1), (256, 256, 200, 2), (256, 256, 8, 1), (256, 512, 40, 1), (128, 256, 72, 1)])
+def test_gemm_p_tn_fp32_fallback(M, N, K, splits, case):
+    """The fp32 fallback of the TN kernels the step uses (gemm_pl_tn8 / gemm_pl_tn4 write the token-row LDS image by hand from the
+    fp32 copy): C and the folded column sums are bit for bit those of the same launch on exact planes -- the fallback splits with
+    site_exact_scale of the same maxima as the mode-0 split pass, splith_pair gives the plane bits, and both paths run the same
+    MFMAs per element and k-tile in the same order -- and both stay inside the fp64 bounds of the split-K / column-sum tests."""
+    H = _abi()
+    dY, X = _rand(K, M, seed=50), _rand(K, N, seed=51)
+    dY[3, 3] = 500.0          # 500 * 2^9 and 6 * 2^14 leave the fp16 range
+    X[1, 5] = 6.0
+    refC, refcs, cs_mag = dY.double().t() @ X.double(), dY.double().sum(0), float(dY.double().abs().sum(0).max())
+    ws = torch.empty(splits * (M * N + M), device=DEV)
+
+    def launch(pa, pb):
+        C, cs = torch.full((M + 1, N), 7.0, device=DEV), torch.full((M + 1,), 7.0, device=DEV)
+        H.gemm_p(H.LAYOUT_TN, M, N, K, pa, pb, C, N, splits=splits, workspace=ws, colsum_out=cs)
+        assert float(C[M].min()) == 7.0 and float(C[M].max()) == 7.0 and float(cs[M]) == 7.0, "margin written"
+        return C[:M], cs[:M]
+
+    def flagged(x, cols, scale):          # delayed scale too large for the outlier: flag up, maxima recorded by the mode-1 split
+        pl, hdr = _ref_planes(H, x, K, cols, scale)
+        assert float(hdr[1]) != 0.0 and not torch.isfinite(pl.float()).all()
+        return H.PT(pl, hdr, K, cols, f32=x)
+
+    def never_written(x, cols):          # first use of a site: no planes, scale 0, maxima from the absmax pass
+        hz = H.new_site(DEV)[0]
+        H.absmax(x, K, cols, cols, out=hz[H.SITE_HDR:])
+        return H.PT(torch.zeros((K, 2 * cols), dtype=torch.float16, device=DEV), hz, K, cols, f32=x)
+
+    exact_a, exact_b = H.to_planes(dY, K, M), H.to_planes(X, K, N)
+    C0, cs0 = launch(exact_a, exact_b)
+    if case == "never_written":
+        pa, pb = never_written(dY, M), never_written(X, N)
+    else:
+        pa = flagged(dY, M, 2.0 ** 9) if case in ("flag_A", "flag_both") else exact_a
+        pb = flagged(X, N, 2.0 ** 14) if case in ("flag_B", "flag_both") else exact_b
+    C1, cs1 = launch(pa, pb)
+    e_c = float((C1.double() - refC).abs().max() / refC.abs().max())
+    e_cs = float((cs1.double() - refcs).abs().max())
+    n_c, n_cs = int((C1.view(torch.int32) != C0.view(torch.int32)).sum()), int((cs1.view(torch.int32) != cs0.view(torch.int32)).sum())
+    print("tn fallback %s %dx%dx%d/%d: C err %.3g (< 3e-6), colsum err %.3g (<= %.3g), words off C %d colsum %d"
+          % (case, M, N, K, splits, e_c, e_cs, 3e-6 * cs_mag, n_c, n_cs))
+    assert e_c < 3e-6 and e_cs <= 3e-6 * cs_mag
+    assert float((C0.double() - refC).abs().max() / refC.abs().max()) < 3e-6 and float((cs0.double() - refcs).abs().max()) <= 3e-6 * cs_mag
+    assert torch.equal(C1, C0) and torch.equal(cs1, cs0), (n_c, n_cs)
+
+
 def test_low_scale_keeps_fp32_level_accuracy():
     """Delayed scales sit 2^3 below the exact ones (head-room for growth): the GEMM error vs fp64 must stay at fp32 level."""
     H = _abi()
