@@ -202,6 +202,9 @@ int segmm_colsum(const float* X, int ld, const float* w, int64_t M, int N, float
  * columns [h*dh, (h+1)*dh).  Masks are uint8 (torch.bool).  lse: [2, B, H, Lq] floats
  * (plane 0 = softmax row max, plane 1 = 1/row sum, written by the forward); Dvec: [B, H, Lq] floats.
  * One key block may be empty (La == 0 or Lb == 0, its pointers null): the CrossAtt / SelfAtt ablations.
+ * Head dims: dh in {4, 8, 16, 32, 48, 64, 96, 128}.  The wide heads (96, 128) run the fp32-view forms only -- direct and
+ * streamed forward, the D kernels, the dQ / dK-dV pair and a fused backward of their own (at most 8 waves per workgroup, a key
+ * block of more tiles in passes) -- with every plane OUTPUT; input planes (*_in) are refused there.
  * Sizes: Lq <= 256, La <= 256, Lb <= 256.  Up to 192 padded keys (each key block rounded up to a multiple of 16) every form
  * below is available.  Beyond that the forward and phases 0-3 of the backward run on the streamed kernels (key tiles in a
  * run-time loop, online softmax; fp32 views, plane OUTPUT of the forward still written); the fused phases 4-6 and input
@@ -211,7 +214,8 @@ int segmm_colsum(const float* X, int ld, const float* w, int64_t M, int N, float
  * 1 = Dvec = rowsum(dO * O) only; 2 = dQa/dQb only (Dvec not written); 3 = dKa/dVa/dKb/dVb only (reads Dvec) -- phases 2
  * and 3 are independent once phase 1 is complete and may run concurrently on two streams; 4 = dQ, dK and dV in ONE kernel
  * (one workgroup per (b, h, key block), query side staged in LDS in chunks of 48 rows, D formed inside -- Dvec is not
- * used; <= 12 key tiles per block); 5 / 6 = the same kernel for key block a / b only (the two launches of phase 4 are
+ * used; <= 12 key tiles per block; wide heads: a launch that takes a block in several passes carries the dQ partial sums in
+ * the fp32 dQ buffer, which it therefore writes under any flags); 5 / 6 = the same kernel for key block a / b only (the two launches of phase 4 are
  * independent: disjoint outputs, shared maxima slots are integer atomic maxima -- they may run on two streams). */
 /* optional plane outputs of the attention kernels (see "PLANE OUTPUTS of producers"): the forward's O; in the fused backward
  * (phase 4) the query-side gradients dQa / dQb (one site: they are columns of the same buffer) and the key-side gradients

@@ -101,6 +101,12 @@ constexpr int ATT_PLANES_ONLY = 1, ATT_REPAIR = 2;
 #endif
 constexpr int ATT_MAX_THREADS = 320;    // forward: up to 5 waves = 5 row tiles of one (b, h) per workgroup
 constexpr int ATT_BWD_THREADS = 768;    // backward kernels need ~160 registers: at most 12 waves per workgroup
+// Wide heads (DH = 96, 128): the row fragments alone are DH / 4 registers each, so the one-wave-per-tile kernels are bounded
+// for FOUR waves per workgroup -- one per SIMD, the whole 512-entry register file (VGPRs + AGPRs) for a wave, no scratch.
+constexpr int ATT_WIDE_THREADS = 256;
+constexpr bool att_wide(int dh) { return dh > 64; }
+constexpr int att_bwd_threads(int dh) { return att_wide(dh) ? ATT_WIDE_THREADS : ATT_BWD_THREADS; }
+constexpr int att_stream_fwd_threads(int dh) { return att_wide(dh) ? ATT_WIDE_THREADS : 320; }
 
 __device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
 
@@ -156,7 +162,20 @@ __device__ __forceinline__ void col_load(float (&f)[(DH + 15) / 16], __amdgpu_bu
     typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
     typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
     if (CT * c < DH) {
-        if (CT == 4) {
+        if (CT > 4) {          // wide heads (CT = 6, 8): a 16-byte load and the rest of the lane's CT floats (8-byte aligned at CT = 6)
+            const f32x4 v = buf_load4(r, voff, soff);
+            f[0] = v.x; f[1 % CT] = v.y; f[2 % CT] = v.z; f[3 % CT] = v.w;
+            if (CT == 8) {
+                const f32x4 w = buf_load4(r, voff + 16, soff);
+                f[4 % CT] = w.x; f[5 % CT] = w.y; f[6 % CT] = w.z; f[7 % CT] = w.w;
+            } else {
+#pragma unroll
+                for (int i = 4; i < CT; i += 2) {
+                    const u32x2_t w = __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff + 4 * i, (int)soff, 0);
+                    f[i % CT] = __uint_as_float(w.x); f[(i + 1) % CT] = __uint_as_float(w.y);
+                }
+            }
+        } else if (CT == 4) {
             const f32x4 v = buf_load4(r, voff, soff);
             f[0] = v.x; f[1 % CT] = v.y; f[2 % CT] = v.z; f[3 % CT] = v.w;
         } else if (CT == 3) {
@@ -688,7 +707,7 @@ __global__ __launch_bounds__(768) void attn_fwd_lds_kernel(const AttnArgs p) {
 // output the kernel is ONE pass over the key tiles with nothing but the dQ accumulators carried along:
 //   S^T_t = K_t.Q^T -> P^T_t ;  dP^T_t = V_t.dO^T ;  dS^T_t = P^T_t (dP^T_t - D) fac ;  dQ^T += K_t^T . dS^T_t
 template <int DH, int NT>
-__global__ __launch_bounds__(ATT_BWD_THREADS) void attn_bwd_dq_kernel(const AttnArgs p) {
+__global__ __launch_bounds__(att_bwd_threads(DH)) void attn_bwd_dq_kernel(const AttnArgs p) {
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
     extern __shared__ uint8_t km[];
@@ -836,7 +855,7 @@ __global__ __launch_bounds__(256) void attn_D_kernel(const AttnArgs p) {
 // was measured 12 % slower).
 // NQT > 0: number of query tiles known at compile time (fully unrolled); NQT = 0: runtime loop.
 template <int DH, int NQT>
-__global__ __launch_bounds__(ATT_BWD_THREADS) void attn_bwd_dkv_kernel(const AttnArgs p) {
+__global__ __launch_bounds__(att_bwd_threads(DH)) void attn_bwd_dkv_kernel(const AttnArgs p) {
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
     extern __shared__ __attribute__((aligned(16))) float smem_f[];

@@ -25,7 +25,7 @@
 namespace segmm {
 
 template <int DH>
-__global__ __launch_bounds__(ATT_MAX_THREADS) void attn_fwd_stream_kernel(const AttnArgs p) {
+__global__ __launch_bounds__(att_stream_fwd_threads(DH)) void attn_fwd_stream_kernel(const AttnArgs p) {
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
     extern __shared__ uint8_t km[];
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void attn_D_stream_kernel(const AttnArgs p) {
 // kernel of its own rather than an NT = 0 instance so that the unrolled instances compile from untouched source.  The K / V row-fragment double buffer is two named
 // halves, the loop is unrolled by two.
 template <int DH>
-__global__ __launch_bounds__(ATT_BWD_THREADS) void attn_bwd_dq_stream_kernel(const AttnArgs p) {
+__global__ __launch_bounds__(att_bwd_threads(DH)) void attn_bwd_dq_stream_kernel(const AttnArgs p) {
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
     extern __shared__ uint8_t km[];

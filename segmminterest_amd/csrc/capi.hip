@@ -9,6 +9,7 @@
 #include "attention16.h"
 #include "attention_pl.h"
 #include "attention_stream.h"
+#include "attention_wide.h"
 #include "common.h"
 #include "evalops.h"
 #include "gemm.h"
@@ -77,7 +78,10 @@ static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, 
     if (Lb == 0) { Qb = Qa; Kb = Ka; Vb = Va; ldkb = ldka; mkb = mka; }
     // (with input planes the fp32 views of Q / K / V are optional: a caller whose projection GEMMs write planes only has none)
     SEGMM_REQUIRE(((Qa && Qb && Ka && Va && Kb && Vb) || (planes_in && !Qa && !Qb && !Ka && !Va && !Kb && !Vb)) && mq && mka && mkb, "attn: null pointer");
-    SEGMM_REQUIRE(dh == 4 || dh == 8 || dh == 16 || dh == 32 || dh == 48 || dh == 64, "attn: head dim %d not built (4,8,16,32,48,64)", dh);
+    SEGMM_REQUIRE(dh == 4 || dh == 8 || dh == 16 || dh == 32 || dh == 48 || dh == 64 || dh == 96 || dh == 128,
+                  "attn: head dim %d not built (4,8,16,32,48,64,96,128)", dh);
+    // wide heads are built in the fp32-view forms only (direct and streamed forward, D, dQ / dK-dV pair, fused backward)
+    SEGMM_REQUIRE(!(planes_in && att_wide(dh)), "attn: input planes are not built for wide heads (head dim %d > 64): hand the fp32 views of Q / K / V", dh);
     SEGMM_REQUIRE(ldq % 4 == 0 && ldka % 4 == 0 && ldkb % 4 == 0, "attn: leading dims %% 4");
     SEGMM_REQUIRE(aligned16(Qa) && aligned16(Qb) && aligned16(Ka) && aligned16(Va) && aligned16(Kb) && aligned16(Vb), "attn: alignment");
     // More than 192 padded keys (12 tiles) go to the streamed kernels (attention_stream.h), which take any tile count; the limit
@@ -178,12 +182,13 @@ static void attn_shape(int n, int H, int max_waves, int want_default, int kn, in
         for (int w = 5; w >= 3; --w)
             if (n % w == 0) { wq = w; break; }
     }
+    if (wq > max_waves) wq = max_waves;          // (wide heads: four waves per workgroup, att_bwd_threads)
     hpb = 1;
     const int e = knob(kn);          // A/B knob (SEGMM_ATT_HPB_FWD / _DQ / _DKV = "heads[,tiles]")
     int want = want_default;
     if (e & 0xff) {
         want = e & 0xff;
-        if ((e >> 8) > 0 && (e >> 8) <= n) wq = e >> 8;
+        if ((e >> 8) > 0 && (e >> 8) <= n && (e >> 8) <= max_waves) wq = e >> 8;
     }
     for (int c = want; c >= 1; --c)
         if (H % c == 0 && c * wq <= max_waves) { hpb = c; break; }
@@ -193,7 +198,7 @@ static void attn_shape(int n, int H, int max_waves, int want_default, int kn, in
 // shape qualifies.  SEGMM_ATT_FWD_PL=0 keeps the fp32-operand kernels (A/B, tests).
 template <int DH>
 static bool attn_fwd_pl_takes(const AttnArgs& a) {
-    if constexpr (DH % 16 != 0) return false;
+    if constexpr (DH % 16 != 0 || att_wide(DH)) return false;          // (wide heads: fp32 views only, attn_fill refuses input planes)
     else {
         if (knob(K_ATT_FWD_PL) == 0) return false;
         const int nqt = (a.Lq + 15) / 16, T = a.La + a.Lb;
@@ -203,7 +208,7 @@ static bool attn_fwd_pl_takes(const AttnArgs& a) {
 }
 template <int DH>
 static int attn_launch_fwd_pl(AttnArgs& a, hipStream_t s) {
-    if constexpr (DH % 16 == 0) {
+    if constexpr (DH % 16 == 0 && !att_wide(DH)) {
         const int nqt = (a.Lq + 15) / 16, T = a.La + a.Lb;
         const size_t lds = attn_fwd_pl_lds_bytes<DH>(a.La, a.Lb);
         // instances: key-block-a length 40 with all 9 tiles present (configs 2 / 4 / 5: tile classes resolved at compile time, a
@@ -232,7 +237,7 @@ static int attn_launch_fwd_pl(AttnArgs& a, hipStream_t s) {
 
 template <int DH>
 static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
-    if (attn_fwd_pl_takes<DH>(a)) return attn_launch_fwd_pl<DH>(a, s);
+    if constexpr (!att_wide(DH)) { if (attn_fwd_pl_takes<DH>(a)) return attn_launch_fwd_pl<DH>(a, s); }
     SEGMM_REQUIRE(a.Qa, "attn_fwd: no fp32 views were given and the planes-in forward does not take this call (it needs dh %% 16 == 0, "
                         "La %% 4 == 0, Lb %% 4 == 0, Lq <= 112, 4-byte aligned masks; knob ATT_FWD_PL)");
     const int Tp = ((a.La + 15) & ~15) + ((a.Lb + 15) & ~15);
@@ -242,6 +247,7 @@ static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
     // more than 12 key tiles: the streamed forward (online softmax, attention_stream.h), before any held form is considered -- the
     // staged form below would be picked by its LDS test alone.  SEGMM_ATT_STREAM=1: at every size (A/B, tests)
     if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) {
+        if constexpr (att_wide(DH)) attn_shape(nqt, a.H, ATT_WIDE_THREADS / 64, 1, K_ATT_HPB_FWD, wq, hpb);
         a.hpb = hpb;
         dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);       // one wave per 16-query tile of a head
         hipLaunchKernelGGL((attn_fwd_stream_kernel<DH>), grid, block, (size_t)Tp, s, a);
@@ -257,7 +263,7 @@ static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
     // the key tiles over two or three wave groups per query tile (SEGMM_ATT_FWD_KSPLIT) does not change that: the direct form stays.
     // SEGMM_ATT_FWD_LDS=0 / 2: never / wherever it fits (A/B, tests).
     const int fwd_lds = knob(K_ATT_FWD_LDS);
-    if constexpr (DH >= 16) {
+    if constexpr (DH >= 16 && !att_wide(DH)) {          // (the staged form is not built for wide heads)
         const size_t lds2 = attn_fwd_lds_bytes<DH>(a.La, a.Lb);
         if ((fwd_lds == 2 || (fwd_lds == 1 && nqt >= 4)) && nqt <= 8 && lds2 <= 80 * 1024) {
             // key-tile groups per query tile (waves per head = nqt * ksp <= 12): more waves on the same staged K / V
@@ -322,6 +328,53 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
         // the repair pass is (almost always) a launch of workgroups that leave at once: one launch for both key blocks
         const int fmode = (a.pflags & ATT_REPAIR) ? 1 : fmode_env;
         const int nmax = nta > ntb ? nta : ntb;
+        if constexpr (att_wide(DH)) {
+            // wide heads: attn_bwd_fused_wide_kernel (attention_wide.h) -- at most ATT_WIDE_MAXW waves per workgroup, a block of more
+            // key tiles in passes; the launch forms of the narrow kernel (merged short heads, one launch per block, one for both) and
+            // its LDS layout plus a [16][DH + 4] K image per wave: 84 - 157 KB, every launch below 160 KB
+            SEGMM_REQUIRE(a.Qa, "attn_bwd: wide heads take the fp32 views");
+            static bool optin = false;          // dynamic LDS above 64 KB needs the opt-in, once per kernel
+            if (!optin) {
+#define WIDE_OPTIN(...) (void)hipFuncSetAttribute((const void*)attn_bwd_fused_wide_kernel<DH, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
+                WIDE_OPTIN(4, true, 16); WIDE_OPTIN(4, true, 32); WIDE_OPTIN(4, true); WIDE_OPTIN(4, false);
+                WIDE_OPTIN(8, true, 16); WIDE_OPTIN(8, true, 32); WIDE_OPTIN(8, true); WIDE_OPTIN(8, false);
+#undef WIDE_OPTIN
+                optin = true;
+            }
+            if (knob(K_ATT_MERGE) != 0 && phase == 4 && a.Lq <= 32 && nta > 0 && ntb > 0 && nta + ntb <= 4) {
+                const int nw = nta + ntb;
+                a.hpb = 3;
+                const dim3 grid(a.B * a.H), block(64 * nw);
+                Lq_p = Lq_small;
+                const size_t lds = ((size_t)5 * Lq_p * (DH + 4) + (size_t)nw * 16 * (DH + 4) + 3 * Lq_p + (size_t)nw * 16 * 20 + 8 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp;
+                if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, 4, true, 16>), grid, block, lds, s, a);
+                else hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, 4, true, 32>), grid, block, lds, s, a);
+                LAUNCH_CHECK();
+                return 0;
+            }
+            for (int blk = 0; blk < 2; ++blk) {
+                if (fmode == 1 && blk == 1) break;
+                if (fmode != 1 && phase >= 5 && blk != phase - 5) continue;
+                const int nt_ = fmode == 1 ? nmax : (blk == 0 ? nta : ntb);
+                if (nt_ == 0) continue;
+                const int nw = nt_ < ATT_WIDE_MAXW ? nt_ : ATT_WIDE_MAXW;
+                a.hpb = fmode == 1 ? 2 : blk;
+                const dim3 grid((fmode == 1 ? 2 : 1) * a.B * a.H), block(64 * nw);
+                const bool one = a.Lq <= ATT_FUSED_QCHUNK;
+                Lq_p = Lq_small;
+                const size_t lds = ((size_t)3 * Lq_p * (DH + 4) + (size_t)nw * 16 * (DH + 4) + 3 * Lq_p + (size_t)nw * 16 * 20 + 4 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp +
+                                   (size_t)knob(K_ATT_LDS_PAD);
+#define FUSEDW(NWV) do { if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, true, 16>), grid, block, lds, s, a); \
+                         else if (Lq_p == 32) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, true, 32>), grid, block, lds, s, a); \
+                         else if (one) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, true>), grid, block, lds, s, a); \
+                         else hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, false>), grid, block, lds, s, a); } while (0)
+                if (nw <= 4) FUSEDW(4);
+                else FUSEDW(8);
+#undef FUSEDW
+            }
+            LAUNCH_CHECK();
+            return 0;
+        } else {
         // short heads (config 3: 20 x (20 + 1) and 1 x (1 + 20), three key tiles): ONE workgroup per head for both key blocks
         // (p.hpb == 3, attention.h) -- the query side is staged once, one launch instead of two; bit-identical to the per-block
         // launches.  SEGMM_ATT_MERGE=0 restores them (A/B, tests)
@@ -414,12 +467,13 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
         }
         LAUNCH_CHECK();
         return 0;
+        }          // (narrow heads)
     }
     a.write_D = phase == 0;
     if (phase == 0 || phase == 2) {
         const int nqt = (a.Lq + 15) / 16;
         int wq, hpb;
-        attn_shape(nqt, a.H, 12, 1, K_ATT_HPB_DQ, wq, hpb);
+        attn_shape(nqt, a.H, att_bwd_threads(DH) / 64, 1, K_ATT_HPB_DQ, wq, hpb);
         a.hpb = hpb;
         dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);
         if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<DH>), grid, block, Tp, s, a);
@@ -431,7 +485,7 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
     if (phase == 0 || phase == 3) {
         const int nt = Tp / 16;
         int wq, hpb;
-        attn_shape(nt, a.H, 12, 1, K_ATT_HPB_DKV, wq, hpb);
+        attn_shape(nt, a.H, att_bwd_threads(DH) / 64, 1, K_ATT_HPB_DKV, wq, hpb);
         // small workgroups: at 3 waves/SIMD a CU holds 12 waves = six 2-wave groups, but only two 5-wave ones
         // (measured for 10 key tiles: 2 waves 533 us, 1 wave 544, 4 waves 611, 5 waves 722)
         if (!knob(K_ATT_HPB_DKV)) wq = nt >= 2 ? 2 : 1;
@@ -455,6 +509,8 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
         case 32: return FN<32>(__VA_ARGS__);        \
         case 48: return FN<48>(__VA_ARGS__);        \
         case 64: return FN<64>(__VA_ARGS__);        \
+        case 96: return FN<96>(__VA_ARGS__);        \
+        case 128: return FN<128>(__VA_ARGS__);      \
         default: return segmm_fail(-1, "attn: head dim %d", dh); \
     }
 
