@@ -189,6 +189,18 @@ int segmm_layernorm_bwd_pos(const float* dy, const float* x, const float* mean, 
                             int d, float drop_y_p, uint32_t drop_y_site, float drop_b_p, uint32_t drop_b_site, uint64_t seed,
                             float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in, float* part_pos, int period,
                             segmm_stream_t stream);
+/* PLANES ONLY: the three entry points above take dx == NULL when planes, hdr and scale_in are given and dx_drop == NULL (anything
+ * else fails): no fp32 dx is stored; planes, header, maxima and partials are bit for bit those of the launch with dx.  The
+ * consumer of such planes has no fp32 copy to fall back on, so the protocol of the attention gradients applies: after the
+ * producers, segmm_site_fixup judges the site (hdr[2] != 0: unusable, hdr[0] = the exact scale), then this REPAIR launch -- same
+ * arguments as the segmm_layernorm_bwd_pos launch it follows -- leaves at once when hdr[2] == 0 and otherwise recomputes the rows
+ * and rewrites ONLY the planes with hdr[0].  It writes no dx, no partial buffer, no maxima and no flag (those pointers may be
+ * NULL); dx_drop must be NULL.  Knob DPRE_PLANES_ONLY (segmm_config_set) tells the engine where to use it. */
+int segmm_layernorm_bwd_pos_repair(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                   float* dx, float* dx_drop, float* part_dgamma, float* part_dbeta, float* part_dsum, int64_t rows,
+                                   int d, float drop_y_p, uint32_t drop_y_site, float drop_b_p, uint32_t drop_b_site, uint64_t seed,
+                                   float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in, float* part_pos, int period,
+                                   segmm_stream_t stream);
 int segmm_colsum_pos(const float* part, int n_rows, int period, int d, float* out, segmm_stream_t stream);
 
 /* out[n] (+)= sum_m w[m] * X[m,n]  (bias gradients, LayerNorm partial combine, head weight gradient).

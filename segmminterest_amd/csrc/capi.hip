@@ -109,7 +109,7 @@ static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, 
 // in by -DSEGMM_ATT_PROBE / -DSEGMM_GEMM_PROBE only.
 enum {
     K_ATTN, K_ATT_FWD_PL, K_ATT_FWD_LDS, K_ATT_FWD_KSPLIT, K_ATT_FWD_LDS_PAD, K_ATT_STREAM, K_ATT_FUSED_LAUNCH, K_ATT_MERGE, K_ATT_LDS_PAD, K_ATT_WAVES, K_ATT_WAVES_PL, K_ATT_REPAIR_WALK,
-    K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_COUNT
+    K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_DPRE_PLANES_ONLY, K_COUNT
 };
 struct Knob { const char* name; int value; const char* doc; };
 static Knob g_knobs[K_COUNT] = {
@@ -134,6 +134,7 @@ static Knob g_knobs[K_COUNT] = {
     {"PL_NJ", 0, "plane NT GEMM: tile width in 64-column units (0: modelled choice)"},
     {"TN_VAR", 8, "plane TN GEMM: 8 gemm_pl_tn4 (round 6: 128 x 256 tiles, two workgroups per CU) for few-tile and 128-row matrices, gemm_pl_tn8 (round 3) otherwise; 4 gemm_pl_tn4 wherever it fits; 88 gemm_pl_tn8 wherever it fits; 0: the round-2 fallback kernel for every launch"},
     {"LN_BWD_PARTS", 0, "LayerNorm backward: most workgroups (= partial rows of its column sums) per launch; 0: as many four-wave workgroups as are resident at the row width (768 at d = 768: one full round, no under-occupied tail)"},
+    {"DPRE_PLANES_ONLY", 1, "embedding LayerNorm gradients as planes only + repair launch (no fp32 copy): 0 never, 1 for sites on the per-position grid today (rows * d >= 2^23), 2 wherever segmm_layernorm_bwd_pos_parts gives a grid (tests at small shapes), 3 as 1 for the user side only (A/B per site)"},
 };
 static bool g_knobs_ready = false;
 static void knobs_init() {
@@ -1106,15 +1107,21 @@ static int ln_bwd_launch(const float* dy, const float* x, const float* mean, con
                          float* dx, float* dx_drop, float* part_dgamma, float* part_dbeta, float* part_dsum, int64_t rows,
                          int d, float drop_y_p, uint32_t drop_y_site, float drop_b_p, uint32_t drop_b_site, uint64_t seed,
                          float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in, float* part_pos, int parts, segmm_stream_t stream,
-                         const float* dy_col = nullptr) {
-    SEGMM_REQUIRE(dy && x && mean && rstd && gamma && dx && part_dgamma && part_dbeta, "layernorm_bwd: null pointer");
+                         const float* dy_col = nullptr, bool repair = false) {
+    SEGMM_REQUIRE(dy && x && mean && rstd && gamma && (repair || (part_dgamma && part_dbeta)), "layernorm_bwd: null pointer");
+    // planes only: the gradient leaves as planes written with a delayed scale -- there must be one, and no second fp32 output
+    SEGMM_REQUIRE(dx || repair || (planes && hdr && scale_in), "layernorm_bwd: dx == NULL (planes only) needs a plane output: planes, hdr and scale_in");
+    SEGMM_REQUIRE(dx || !dx_drop, "layernorm_bwd: dx == NULL (planes only) with dx_drop given: the planes would hold dx_drop, keep both fp32 outputs");
+    SEGMM_REQUIRE(!repair || (planes && hdr && !dx_drop), "layernorm_bwd_pos_repair: rewrites the planes of a planes-only launch: planes + hdr, no dx_drop");
     PLANE_OUT_CHECK("layernorm_bwd", d);
     SEGMM_REQUIRE(d > 0 && d % 4 == 0 && d <= 256 * ROW_MAXV, "layernorm_bwd: d=%d unsupported", d);
-    SEGMM_REQUIRE((dy_col ? aligned16(dy_col) : aligned16(dy)) && aligned16(x) && aligned16(dx) && aligned16(gamma) && (!dx_drop || aligned16(dx_drop)), "layernorm_bwd: alignment");
+    SEGMM_REQUIRE((dy_col ? aligned16(dy_col) : aligned16(dy)) && aligned16(x) && (!dx || aligned16(dx)) && aligned16(gamma) && (!dx_drop || aligned16(dx_drop)), "layernorm_bwd: alignment");
     const DropCfg dy_ = make_drop(drop_y_p, seed, drop_y_site), db_ = make_drop(drop_b_p, seed, drop_b_site);
-#define LNB(V) hipLaunchKernelGGL((layernorm_bwd_kernel<V>), dim3(parts), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, dx, dx_drop, part_dgamma, part_dbeta, part_dsum, (long long)rows, d, dy_, db_, amax, plane_out(planes, ld2, hdr, scale_in), part_pos, dy_col)
+#define LNB_(V, R) hipLaunchKernelGGL((layernorm_bwd_kernel<V, R>), dim3(parts), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma, dx, dx_drop, part_dgamma, part_dbeta, part_dsum, (long long)rows, d, dy_, db_, amax, plane_out(planes, ld2, hdr, scale_in), part_pos, dy_col)
+#define LNB(V) do { if (repair) LNB_(V, true); else LNB_(V, false); } while (0)
     if (d <= 256) LNB(1); else if (d <= 512) LNB(2); else if (d <= 768) LNB(3); else if (d <= 1024) LNB(4); else LNB(8);
 #undef LNB
+#undef LNB_
     LAUNCH_CHECK();
     return 0;
 }
@@ -1157,6 +1164,19 @@ int segmm_layernorm_bwd_pos(const float* dy, const float* x, const float* mean, 
     SEGMM_REQUIRE(part_pos && parts > 0 && (4 * parts) % period == 0, "layernorm_bwd_pos: %lld rows with period %d have no per-position grid", (long long)rows, period);
     return ln_bwd_launch(dy, x, mean, rstd, gamma, dx, dx_drop, part_dgamma, part_dbeta, part_dsum, rows, d, drop_y_p, drop_y_site, drop_b_p,
                          drop_b_site, seed, amax, planes, ld2, hdr, scale_in, part_pos, parts, stream);
+}
+
+// The REPAIR launch of a planes-only segmm_layernorm_bwd_pos (dx == NULL), after segmm_site_fixup has judged the site: same
+// arguments, same grid.  Writes the planes alone (dx, the partial buffers, amax and part_pos are not touched and may be NULL).
+int segmm_layernorm_bwd_pos_repair(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                   float* dx, float* dx_drop, float* part_dgamma, float* part_dbeta, float* part_dsum, int64_t rows,
+                                   int d, float drop_y_p, uint32_t drop_y_site, float drop_b_p, uint32_t drop_b_site, uint64_t seed,
+                                   float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in, float* part_pos, int period,
+                                   segmm_stream_t stream) {
+    const int parts = segmm_layernorm_bwd_pos_parts(rows, period, d);
+    SEGMM_REQUIRE(parts > 0, "layernorm_bwd_pos_repair: %lld rows with period %d have no per-position grid", (long long)rows, period);
+    return ln_bwd_launch(dy, x, mean, rstd, gamma, dx, dx_drop, part_dgamma, part_dbeta, part_dsum, rows, d, drop_y_p, drop_y_site, drop_b_p,
+                         drop_b_site, seed, amax, planes, ld2, hdr, scale_in, part_pos, parts, stream, nullptr, true);
 }
 
 int segmm_colsum_pos(const float* part, int n_rows, int period, int d, float* out, segmm_stream_t stream) {

@@ -159,7 +159,14 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 // residual branch "x = res + dropout(z)": dz = dx_drop); per-workgroup partial dgamma / dbeta and, optionally,
 // the partial COLUMN SUMS of the forwarded gradient (dx_drop, or dx without it) -- the bias gradient of the
 // Linear that produced z, which would otherwise cost a second pass over that tensor.
-template <int V>
+// dx == null (with a plane output, no dx_drop): PLANES ONLY -- the gradient leaves as planes, maxima and partials, exactly the ones
+// of the launch with dx, and no fp32 copy is stored (the embedding LayerNorms: their dx is read by a plane TN GEMM alone, the
+// positional sums come from part_pos; 157 MB of stores at 51 200 x 768).  The consumer then has no fp32 copy to fall back on, so
+// the REPAIR form of the same launch follows segmm_site_fixup (the protocol of the attention backward, attention.h ATT_REPAIR):
+// hdr[2] == 0 = the planes are usable, every workgroup leaves after one scalar load; otherwise the rows are recomputed and ONLY
+// the planes rewritten, with the exact scale fixup left in hdr[0] -- no dx, no partials, no maxima, no flag (the column sums of the
+// first launch's partials may be running on the side stream, and every workgroup must read the same header).
+template <int V, bool REPAIR = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                      const float* __restrict__ gamma, float* __restrict__ dx,
@@ -172,7 +179,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     // decoder_leave_focal.py:451,596): formed here instead of being written out by one kernel and read back by this one.
     drop_y = drop_live(drop_y); drop_branch = drop_live(drop_branch);
     __shared__ f32x4 red[4][64];
-    const float ps = plane_scale(po);
+    float ps = plane_scale(po);
+    if (REPAIR) {
+        if (po.hdr[2] == 0.f) return;          // (block-uniform: one header word)
+        ps = po.hdr[0];
+    }
     float am = 0.f;          // max |dx_drop| (or |dx| when there is no dropped copy): the tensor the GEMMs consume
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     // part_pos (embedding LayerNorms): this WAVE's sum of dx over the rows it walks, one partial row per wave.  The host picks the
@@ -198,8 +209,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                 f32x4 t = dy_col ? *(const f32x4*)(dy_col + c) * dy[row] : ld_row4(dy + row * d + c);
                 if (drop_y.p > 0.f) t = drop_apply4(drop_y, ((uint64_t)row * d + c) >> 2, t);
                 xh[i] = (ld_row4(x + row * d + c) - mu) * rs;
-                ab[i] += t;
-                ag[i] += t * xh[i];
+                if (!REPAIR) { ab[i] += t; ag[i] += t * xh[i]; }
                 g[i] = t * gm[i];
                 s1 += g[i].x + g[i].y + g[i].z + g[i].w;
                 const f32x4 u = g[i] * xh[i];
@@ -213,19 +223,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
             const int c = lane * 4 + i * 256;
             if (c < d) {
                 const f32x4 o = (g[i] - s1 - xh[i] * s2) * rs;
-                st_row4(dx + row * d + c, o);
+                if (!REPAIR && dx) st_row4(dx + row * d + c, o);
                 f32x4 od = o;
-                if (dx_drop) {
+                if (!REPAIR && dx_drop) {
                     if (drop_branch.p > 0.f) od = drop_apply4(drop_branch, ((uint64_t)row * d + c) >> 2, o);
                     st_row4(dx_drop + row * d + c, od);
                 }
                 if (ps > 0.f) plane_store4_pair(po.p, po.ld2, row, c, od, ps);
-                as[i] += od;
-                ap[i] += o;
-                am = absmax4(am, od);
+                if (!REPAIR) { as[i] += od; ap[i] += o; am = absmax4(am, od); }
             }
         }
     }
+    if (REPAIR) return;
     plane_finish(po, amax, am, blockIdx.x * nw + wave, ps, blockIdx.x == 0 && threadIdx.x == 0);
     if (part_pos) {
 #pragma unroll

@@ -734,14 +734,19 @@ class AmaxArena:
             store.update_scales(self.t, self.sites, self.i, backward=backward)
 
 
-def new_act(store, arena, rows, cols, t=None, key=None, planes=True, site=None, delayed=False):
+def new_act(store, arena, rows, cols, t=None, key=None, planes=True, site=None, delayed=False, planes_only=False):
     """An Act with a fresh site header; ``t`` given or allocated (``key``: persistent scratch name instead of a new tensor).
     ``planes=False``: no GEMM reads it on the plane engine (only its fp32 values / maxima are wanted).
     ``site`` names the tensor for delayed scaling; with ``delayed`` and a calibrated site the Act carries a plane output
-    (``po``) for its producer kernel, otherwise ``finish_act`` makes the planes with an exact split pass."""
+    (``po``) for its producer kernel, otherwise ``finish_act`` makes the planes with an exact split pass.
+    ``planes_only``: if the Act gets a plane output, it gets NO fp32 tensor (``t`` None, ``no_f32``): the producer writes planes only
+    and runs the repair protocol (BackboneRun.backward, embedding part)."""
     dev = store.flat.device
-    if t is None:
-        t = store.buf(key, (rows, cols)) if key is not None else torch.empty((rows, cols), dtype=torch.float32, device=dev)
+
+    def alloc_t():
+        return store.buf(key, (rows, cols)) if key is not None else torch.empty((rows, cols), dtype=torch.float32, device=dev)
+    if t is None and not planes_only:
+        t = alloc_t()
     want = planes
     planes = None
     if want and store.engine_p and cols % 32 == 0:
@@ -752,6 +757,11 @@ def new_act(store, arena, rows, cols, t=None, key=None, planes=True, site=None, 
         a.scale_ptr = store.scale_ptr(site, delayed)
         if a.scale_ptr is not None:
             a.po = H.PO(planes, 2 * cols, a.hdr, a.scale_ptr)
+    if planes_only:
+        if a.po is not None:
+            a.no_f32 = True
+        elif a.t is None:
+            a.t = alloc_t()
     return a
 
 
@@ -774,8 +784,8 @@ def _needs_f32(act, what):
     """A launch is about to read ``act.t``: refuse if its producers wrote planes only (engine._layer_bwd, planes-only protocol)."""
     if getattr(act, "no_f32", False):
         raise RuntimeError("%s reads the fp32 copy of an operand whose producers wrote planes only (attention gradients: set "
-                           "SEGMM_ATTN_PLANES_ONLY=0; L1-normalised input features: SEGMM_INPUT_PLANES_ONLY=0 -- needed for operands "
-                           "a plane GEMM cannot take)" % what)
+                           "SEGMM_ATTN_PLANES_ONLY=0; L1-normalised input features: SEGMM_INPUT_PLANES_ONLY=0; embedding LayerNorm gradients: "
+                           "library knob DPRE_PLANES_ONLY=0 -- needed for operands a plane GEMM cannot take)" % what)
 
 
 def _wgrad(store, dY, y_off, X, x_off, Mrows, n_out, n_in, gW, accumulate=False, gb=None):
@@ -852,16 +862,24 @@ def _colsum(store, X, ld, M, N, out, x_off=0, w=None, accumulate=False):
     H.colsum(X, ld, M, N, out, ws, w=w, accumulate=accumulate, x_off=x_off)
 
 
+def _ln_pos_parts(rows, period, d, force=False):
+    """Workgroups of the per-position grid a LayerNorm backward over ``rows`` tokens of sequences of ``period`` takes (0: the plain grid)."""
+    return H.layernorm_bwd_pos_parts(rows, period, d) if (period >= 8 and (force or rows * d >= (1 << 23))) else 0
+
+
 def _ln_bwd(store, dy, x, mean, rstd, gname, bname, gbuf, dx, dx_drop, rows, d, drop_y=(0.0, 0), drop_b=(0.0, 0), seed=0,
-            amax=None, dsum_to=None, po=None, pos_period=0, dy_outer=None):
+            amax=None, dsum_to=None, po=None, pos_period=0, dy_outer=None, force_pos=False):
     """LayerNorm backward + its affine gradients.  ``dsum_to``: gradient tensor that receives the column sums of the
     forwarded gradient (dx_drop, or dx): the bias gradient of the Linear feeding this LayerNorm's residual branch,
     accumulated inside the same kernel instead of by a second pass over [rows, d].
     ``pos_period`` = L (embedding LayerNorms, rows = B * L): the launch takes the per-position grid and the per-wave sums of dx
     it leaves are returned ([4 * parts, d], partial row p = position p mod L; None when no such grid exists) -- the
-    positional-embedding gradient then is a sum over ~40 partial rows per position instead of a pass over dx."""
+    positional-embedding gradient then is a sum over ~40 partial rows per position instead of a pass over dx.
+    ``dx`` None: planes only (needs ``po`` and the per-position grid; ``force_pos`` takes that grid at any size)."""
     # (worth it when the second pass it saves is long: short sequences / small tensors keep the plain column sum)
-    pparts = H.layernorm_bwd_pos_parts(rows, pos_period, d) if (pos_period >= 8 and rows * d >= (1 << 23)) else 0
+    pparts = _ln_pos_parts(rows, pos_period, d, force_pos)
+    if dx is None and (pparts <= 0 or po is None):
+        raise RuntimeError("a planes-only LayerNorm backward needs a plane output and the per-position grid (%s)" % gname)
     parts = pparts if pparts > 0 else H.layernorm_bwd_parts(rows, d)
     # partial buffers named after the parameter: their reductions may run on the side stream (store.ln_side)
     pg = store.buf("ln_pg:" + gname, (parts, d))
@@ -1538,29 +1556,64 @@ class BackboneRun:
                     on_bucket("%slayer%d" % (P, i), after_side=True)
         # ---- embedding backward.  User side first: its weight gradient (the larger one) queues on the side stream
         # behind the projection weight gradients still running there, the video side's runs on the main stream.
+        # PLANES ONLY (library knob DPRE_PLANES_ONLY): in image mode the fp32 gradient of an embedding LayerNorm's input is read by
+        # nobody -- the weight gradient reads the planes, the positional sums come from part_pos; it only ever was the overflow
+        # fallback of the TN GEMM (157 + 63 MB of stores per step at config 2).  Such a side gets no fp32 buffer and dx = None;
+        # after BOTH LayerNorm backwards one site_fixup judges the sites, and the repair launch of each site (leaves at once
+        # unless the delayed scale turned out wrong) runs on the stream of its consumer, directly before that weight gradient.
         H.mark(H.PHASE_EMBED_BWD, self.bi)
-        if dXu is not None:
-            dpre_u = new_act(st, self.amb, Mu, d, key="dpre_u", planes=not bb.id_usr, site=P + "dpre_u", delayed=self.delayed)
-            pp_u = _ln_bwd(st, dXu, sv["pre_u"], sv["meu"], sv["reu"], P + "usr_ln.weight", P + "usr_ln.bias", gbuf, dpre_u.t, None, Mu, d,
-                           drop_y=(self.p_drop, _site(self.bi, 0, K_EMB_U)), seed=self.seed, amax=dpre_u.slots, po=dpre_u.po, pos_period=Lt)
-            finish_act(st, produced(dpre_u))
-            self._embed_bwd("usr", dpre_u, B, Lt, gbuf, pp_u)
+        ko = H.knob("DPRE_PLANES_ONLY") if (st.engine_p and self.delayed) else 0
+
+        def planes_only(side, rows, L):
+            if not ko or (bb.id_vid if side == "vid" else bb.id_usr) or sv.get("frame_pos") is not None:
+                return False
+            x = sv["%s_x" % side]
+            if x.planes is None or d % 32 or x.cols % 32:          # (_wgrad's condition for the plane TN GEMM)
+                return False
+            if ko == 3 and side == "vid":          # (A/B per site: the user side alone)
+                return False
+            return _ln_pos_parts(rows, L, d, ko == 2) > 0
+
+        def repair_of(dy, side, act, key, L):
+            pre, me, re_ = ("pre_u", "meu", "reu") if side == "usr" else ("pre_v", "mev", "rev")
+            return lambda: H.layernorm_bwd_pos_repair(dy, sv[pre], sv[me], sv[re_], st.p(P + "%s_ln.weight" % side), L, act.po,
+                                                      drop_y_p=self.p_drop, drop_y_site=_site(self.bi, 0, key), seed=self.seed)
+
+        def embed_u():
+            self._embed_bwd("usr", dpre_u, B, Lt, gbuf, pp_u, repair=repair_of(dXu, "usr", dpre_u, K_EMB_U, Lt) if dpre_u.no_f32 else None)
             if on_bucket is not None:
                 # the user-side embedding gradients: LayerNorm / positional parts were written on the main stream, the weight
                 # gradient is still in flight on the side stream -- the hook orders the all-reduce behind BOTH without making the
                 # main stream (which goes on with the video side) wait for the side stream
                 on_bucket(P + "embed_u", after_side=True)
-        dpre_v = new_act(st, self.amb, Mv, d, key="dpre_v", planes=not bb.id_vid, site=P + "dpre_v", delayed=self.delayed)
+        dpre_u = None
+        if dXu is not None:
+            dpre_u = new_act(st, self.amb, Mu, d, key="dpre_u", planes=not bb.id_usr, site=P + "dpre_u", delayed=self.delayed,
+                             planes_only=planes_only("usr", Mu, Lt))
+            pp_u = _ln_bwd(st, dXu, sv["pre_u"], sv["meu"], sv["reu"], P + "usr_ln.weight", P + "usr_ln.bias", gbuf, dpre_u.t, None, Mu, d,
+                           drop_y=(self.p_drop, _site(self.bi, 0, K_EMB_U)), seed=self.seed, amax=dpre_u.slots, po=dpre_u.po, pos_period=Lt,
+                           force_pos=dpre_u.no_f32)
+            finish_act(st, produced(dpre_u))
+            if not dpre_u.no_f32:
+                embed_u()
+        dpre_v = new_act(st, self.amb, Mv, d, key="dpre_v", planes=not bb.id_vid, site=P + "dpre_v", delayed=self.delayed,
+                         planes_only=planes_only("vid", Mv, S))
         pp_v = _ln_bwd(st, dXv, sv["pre_v"], sv["mev"], sv["rev"], P + "vid_ln.weight", P + "vid_ln.bias", gbuf, dpre_v.t, None, Mv, d,
-                       drop_y=(self.p_drop, _site(self.bi, 0, K_EMB_V)), seed=self.seed, amax=dpre_v.slots, po=dpre_v.po, pos_period=S)
+                       drop_y=(self.p_drop, _site(self.bi, 0, K_EMB_V)), seed=self.seed, amax=dpre_v.slots, po=dpre_v.po, pos_period=S,
+                       force_pos=dpre_v.no_f32)
         finish_act(st, produced(dpre_v))
-        self._embed_bwd("vid", dpre_v, B, S, gbuf, pp_v)
+        u_only = dpre_u is not None and dpre_u.no_f32
+        if u_only or dpre_v.no_f32:          # every producer of the two sites is enqueued: judge them in one tiny launch
+            H.site_fixup(dpre_u.hdr if u_only else None, dpre_v.hdr if dpre_v.no_f32 else None, stats=st.scales()[st.MAX_SITES:])
+        if u_only:
+            embed_u()
+        self._embed_bwd("vid", dpre_v, B, S, gbuf, pp_v, repair=repair_of(dXv, "vid", dpre_v, K_EMB_V, S) if dpre_v.no_f32 else None)
         join_side(st)
         self.amb.close(st, backward=True)
         if on_bucket is not None:
             on_bucket(P + "embed")
 
-    def _embed_bwd(self, side, dpre_act, B, L, gbuf, part_pos=None):
+    def _embed_bwd(self, side, dpre_act, B, L, gbuf, part_pos=None, repair=None):
         st, bb, P, d, sv = self.store, self.bb, self.pre, self.d, self.sv
         dpre = dpre_act.t
         M = B * L
@@ -1632,6 +1685,8 @@ class BackboneRun:
             # before the user side) therefore runs on the MAIN stream, the user-side one on the side stream.
             ctx = contextlib.nullcontext() if side == "vid" else side_work(st)
             with ctx:
+                if repair is not None:          # planes-only dpre: its repair launch, on the consumer's stream
+                    repair()
                 _wgrad(st, dpre_act, 0, x, 0, M, d, Din, gtab)
                 # bias gradient = sum over all tokens of dpre = sum over positions of the positional-embedding
                 # gradient just computed ([L, d] instead of a second pass over [B*L, d])

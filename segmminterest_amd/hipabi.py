@@ -735,7 +735,8 @@ def layernorm_bwd_pos_parts(rows, period, d):
 
 def layernorm_bwd_pos(dy, x, mean, rstd, gamma, dx, dx_drop, part_dgamma, part_dbeta, part_pos, period, drop_y_p=0.0, drop_y_site=0,
                       drop_b_p=0.0, drop_b_site=0, seed=0, amax=None, part_dsum=None, po=None):
-    """LayerNorm backward on the per-position grid: also leaves the per-wave sums of dx in ``part_pos`` [4 * parts, d]."""
+    """LayerNorm backward on the per-position grid: also leaves the per-wave sums of dx in ``part_pos`` [4 * parts, d].
+    ``dx=None`` (with ``po``, no ``dx_drop``): planes only -- no fp32 dx is stored; see :func:`layernorm_bwd_pos_repair`."""
     _dev(dy, x, dx)
     d = x.shape[-1]
     _check(lib().segmm_layernorm_bwd_pos(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx), _ptr(dx_drop),
@@ -743,6 +744,17 @@ def layernorm_bwd_pos(dy, x, mean, rstd, gamma, dx, dx_drop, part_dgamma, part_d
                                          int(drop_y_site), float(drop_b_p), int(drop_b_site), int(seed), _ptr(amax), *_po(po),
                                          _ptr(part_pos), int(period), _stream()),
            "segmm_layernorm_bwd_pos")
+
+
+def layernorm_bwd_pos_repair(dy, x, mean, rstd, gamma, period, po, drop_y_p=0.0, drop_y_site=0, seed=0):
+    """The REPAIR launch of a planes-only ``layernorm_bwd_pos`` (``dx=None``), after :func:`site_fixup`: leaves at once when the
+    site's planes are usable (hdr[2] == 0), else rewrites the planes -- and nothing else -- with the exact scale in hdr[0]."""
+    _dev(dy, x)
+    d = x.shape[-1]
+    _check(lib().segmm_layernorm_bwd_pos_repair(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), None, None, None, None, None,
+                                                x.numel() // d, d, float(drop_y_p), int(drop_y_site), 0.0, 0, int(seed), None, *_po(po),
+                                                None, int(period), _stream()),
+           "segmm_layernorm_bwd_pos_repair")
 
 
 def colsum_pos(part, period, out):
