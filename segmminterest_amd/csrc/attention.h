@@ -36,6 +36,7 @@
 // stream is indexed by (b, h, query, padded key) so 4 consecutive keys share one hash call.
 #pragma once
 #include "common.h"
+#include "attention_lds.h"
 
 namespace segmm {
 
@@ -290,9 +291,10 @@ __device__ __forceinline__ float col_store_p(float* rowp, _Float16* planes, int 
 }
 
 // kmask[jp] : 1 valid, 0 masked token (-10000 fill), 2 alignment pad (probability 0)
+// (nthr: the threads that take part -- blockDim.x, or the surviving threads of a fused backward workgroup)
 __device__ __forceinline__ void stage_kmask(uint8_t* km, const uint8_t* mka, const uint8_t* mkb, int b, int La, int Lb,
-                                            int La_p, int Lb_p) {
-    for (int j = threadIdx.x; j < La_p + Lb_p; j += blockDim.x) {
+                                            int La_p, int Lb_p, int nthr) {
+    for (int j = threadIdx.x; j < La_p + Lb_p; j += nthr) {
         uint8_t v;
         if (j < La_p) v = (j < La) ? (mka[(size_t)b * La + j] ? 1 : 0) : 2;
         else { const int jb = j - La_p; v = (jb < Lb) ? (mkb[(size_t)b * Lb + jb] ? 1 : 0) : 2; }
@@ -359,7 +361,7 @@ __global__ __launch_bounds__(ATT_MAX_THREADS) void attn_fwd_kernel(const AttnArg
     const int bh = xcd_remap(blockIdx.x, gridDim.x) * p.hpb + wave / wq, b = bh / p.H, h = bh % p.H;
     const int La_p = round16(p.La), Lb_p = round16(p.Lb), Tp = La_p + Lb_p, nta = La_p >> 4, nt = Tp >> 4;
     const int col0 = h * DH;
-    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p);
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, blockDim.x);
     __syncthreads();
     const int qt = blockIdx.y * wq + wave % wq;      // this wave's query tile
     if (16 * qt >= p.Lq) return;
@@ -557,7 +559,7 @@ __global__ __launch_bounds__(768) void attn_fwd_lds_kernel(const AttnArgs p) {
         stage(p.Va, p.ka_bytes, p.La, La_p, p.ldka, sVa, cha);
         stage(p.Vb, p.kb_bytes, p.Lb, Lb_p, p.ldkb, sVb, chb);
     }
-    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p);
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, blockDim.x);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #ifdef SEGMM_ATT_PROBE
@@ -716,7 +718,7 @@ __global__ __launch_bounds__(att_bwd_threads(DH)) void attn_bwd_dq_kernel(const 
     const int bh = xcd_remap(blockIdx.x, gridDim.x) * p.hpb + wave / wq, b = bh / p.H, h = bh % p.H;
     const int La_p = round16(p.La), Lb_p = round16(p.Lb), Tp = La_p + Lb_p, nta = La_p >> 4, nt = Tp >> 4;
     const int col0 = h * DH;
-    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p);
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, blockDim.x);
     __syncthreads();
     const int qt = blockIdx.y * wq + wave % wq;
     if (16 * qt >= p.Lq) return;
@@ -883,7 +885,7 @@ __global__ __launch_bounds__(att_bwd_threads(DH)) void attn_bwd_dkv_kernel(const
         }
         for (int q = threadIdx.x; q < Lq_p; q += blockDim.x) qm[q] = q < p.Lq ? (p.mq[(size_t)b * p.Lq + q] ? 1 : 0) : 2;
     }
-    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p);
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, blockDim.x);
     __syncthreads();
     const int jt = blockIdx.y * wq + wave % wq;     // this wave's key tile
     if (jt >= nt) return;
@@ -1024,8 +1026,8 @@ template <int DH, int NW, bool ONE, int QCH = ATT_FUSED_QCHUNK>
 __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_fused_kernel(const AttnArgs p) {
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
-    constexpr int RS = DH + 4;                 // LDS row stride (floats): 16-byte aligned rows, conflict-free fragment reads
-    constexpr int TS = 20;                     // row stride of the 16 x 16 transpose scratch
+    constexpr int RS = att_lds_rs(DH);         // LDS row stride (floats)
+    constexpr int TS = ATT_LDS_TS;             // row stride of the 16 x 16 transpose scratch
     constexpr int QC = QCH;                    // queries staged at a time (1 - 3 query tiles)
     constexpr int MAXQT = QC / 16;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -1080,20 +1082,22 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_fused_kernel(const AttnAr
 #endif
     ATT_MARK(0);
     const int nQ = merged ? 2 : 1;                         // staged Q projections / dQ accumulators
-    float* sQ0 = smem_f;                                   // [nQ][QC][RS] query rows of the current chunk
-    float* sdO = sQ0 + nQ * QC * RS;
-    float* sdQ0 = sdO + QC * RS;
+    const AttLdsFused L = att_lds_fused(DH, QC, nw, Tp, merged);
+    char* const sm = (char*)smem_f;
+    float* sQ0 = (float*)(sm + L.q);                       // [nQ][QC][RS] query rows of the current chunk
+    float* sdO = (float*)(sm + L.dO);
+    float* sdQ0 = (float*)(sm + L.dq);
     float* sQ = sQ0 + ((merged && !isa) ? QC * RS : 0);   // this wave's block: its Q rows, its dQ accumulator
     float* sdQ = sdQ0 + ((merged && !isa) ? QC * RS : 0);
-    float* s_mx = sdQ0 + nQ * QC * RS;
-    float* s_inv = s_mx + QC;
-    float* s_D = s_inv + QC;
-    float* s_tr = s_D + QC + wave * (16 * TS);                              // this wave's transpose scratch
-    int* s_turn0 = (int*)(s_D + QC + nw * (16 * TS));                       // [nQ][4] whose turn it is to add dQ of query tile qt
+    float* s_mx = (float*)(sm + L.mx);
+    float* s_inv = (float*)(sm + L.inv);
+    float* s_D = (float*)(sm + L.D);
+    float* s_tr = (float*)(sm + L.tr) + wave * (16 * TS);                   // this wave's transpose scratch
+    int* s_turn0 = (int*)(sm + L.turn);                                     // [nQ][4] whose turn it is to add dQ of query tile qt
     int* s_turn = s_turn0 + ((merged && !isa) ? 4 : 0);
-    float* s_Dp = (float*)(s_turn0 + 4 * nQ);                               // [QC][DH/4] partial products dO . O
-    uint8_t* qm = (uint8_t*)(s_Dp + QC * (DH / 4));                         // [QC] 1 valid query, 0 masked, 2 pad
-    uint8_t* km = qm + QC;                                                  // [Tp]
+    float* s_Dp = (float*)(sm + L.dp);                                      // [QC][DH/4] partial products dO . O
+    uint8_t* qm = (uint8_t*)(sm + L.qm);                                    // [QC] 1 valid query, 0 masked, 2 pad
+    uint8_t* km = (uint8_t*)(sm + L.km);                                    // [Tp]
     // ---- this wave's key tile
     const int jt = (isa ? 0 : nta) + wib;                                   // padded key tile of this wave
     KeyBlocks<DH> kbk;
@@ -1119,12 +1123,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_fused_kernel(const AttnAr
     // (the other order costs 18 % at Lq = 100).  (Round 4: two staging items per thread in flight + the fragments right behind
     // them, for the short chunks of config 3: no gain at Lq = 20, 86 -> 97 us at Lq = 1 -- removed.)
     if (!ONE) load_frags();
-    for (int j = threadIdx.x; j < Tp; j += nthr) {         // key flags (stage_kmask with the surviving thread count)
-        uint8_t v;
-        if (j < La_p) v = (j < p.La) ? (p.mka[(size_t)b * p.La + j] ? 1 : 0) : 2;
-        else { const int jb = j - La_p; v = (jb < p.Lb) ? (p.mkb[(size_t)b * p.Lb + jb] ? 1 : 0) : 2; }
-        km[j] = v;
-    }
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, nthr);
     const float fscale = p.scale;
     const int jp = 16 * jt + l15;                          // this lane's key (padded index)
     f32x4 dk[C::CT], dv[C::CT];

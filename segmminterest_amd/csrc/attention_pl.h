@@ -347,12 +347,6 @@ __global__ __launch_bounds__(64 * ATT_PL_MAXW) void attn_fwd_pl_kernel(const Att
 }
 
 
-// LDS bytes of attn_bwd_pl_kernel for a query chunk of QC rows, nw waves and Tp padded keys (keep in step with the kernel's layout)
-template <int DH>
-inline size_t attn_bwd_pl_lds_bytes(int QC, int nw, int /*Tp*/) {
-    return ((size_t)3 * QC * (DH + 4) + 3 * QC + 4 + 36) * 4 + (size_t)nw * 2 * 16 * (DH * 2 + 8) + QC;
-}
-
 // ------------------------------------------------------------------------------------------ backward: fused dQ + dK + dV on input planes
 // attn_bwd_fused16_kernel (attention16.h: same workgroup = (b, h, key block), same wave = key tile in passes, same ordered dQ
 // accumulation, dropout stream, plane outputs and repair protocol) with Q, K and V read from the P32 planes of the projection
@@ -375,9 +369,9 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? SEGMM_ATT16_WPS : 4) void attn_b
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
     static_assert(DH % 16 == 0, "fp16 attention: head dim must be a multiple of 16");
-    constexpr int RS = DH + 4;                 // LDS row stride (floats): 16-byte aligned rows, conflict-free row-fragment reads
+    constexpr int RS = att_lds_rs(DH);         // LDS row stride (floats)
     constexpr int RSB = RS * 4;                // ... in bytes
-    constexpr int TS = 20;                     // row stride of the 16 x 16 transpose scratch
+    constexpr int TS = ATT_LDS_TS;             // row stride of the 16 x 16 transpose scratch
     constexpr int QC = ATT_FUSED_QCHUNK;       // queries staged at a time (3 query tiles)
     constexpr int MAXQT = QC / 16;
     constexpr int NCH = DH / 16;               // k = 16 blocks of a product over the head dim (= C::CT)
@@ -426,20 +420,22 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? SEGMM_ATT16_WPS : 4) void attn_b
     }
     const bool f32_q = !repair && !((p.pflags & ATT_PLANES_ONLY) && want_q);          // fp32 copies of dQ / of dK, dV
     const bool f32_k = !repair && !((p.pflags & ATT_PLANES_ONLY) && want_k);
-    constexpr int KTP = DH * 2 + 8;                                        // row pitch (bytes) of a wave's K tile image: [16 keys][DH fp16] + pad
-    char* sQ = (char*)smem_f;                              // [QC][RSB]: [4 hi | 4 lo] groups of the Q planes (written as staged)
-    char* sdO = sQ + QC * RSB;                             // [QC][RSB]: fp32 rows while staging, then [4 hi | 4 lo] groups
-    float* sdQ = (float*)(sdO + QC * RSB);                 // [QC][RS] dQ accumulators (zeroed once D is formed)
+    constexpr int KTP = att_lds_ktp(DH);                                   // row pitch (bytes) of a wave's K tile image: [16 keys][DH fp16] + pad
+    const AttLdsPl L = att_lds_pl(DH, QC, nw);
+    char* const sm = (char*)smem_f;
+    char* sQ = sm + L.q;                                   // [QC][RSB]: [4 hi | 4 lo] groups of the Q planes (written as staged)
+    char* sdO = sm + L.dO;                                 // [QC][RSB]: fp32 rows while staging, then [4 hi | 4 lo] groups
+    float* sdQ = (float*)(sm + L.dq);                      // [QC][RS] dQ accumulators (zeroed once D is formed)
     float* s_Dp = sdQ;                                     // [QC][DH/4] partial products dO . O: alive from the staging to D only
-    float* s_mx = sdQ + QC * RS;
-    float* s_inv = s_mx + QC;
-    float* s_D = s_inv + QC;
-    char* sKt = (char*)(s_D + QC) + wave * (2 * 16 * KTP);                  // this wave's K tile, hi image then lo image (row fragments in,
+    float* s_mx = (float*)(sm + L.mx);
+    float* s_inv = (float*)(sm + L.inv);
+    float* s_D = (float*)(sm + L.D);
+    char* sKt = sm + L.kimg + wave * att_lds_kimg_pl_wave(DH);             // this wave's K tile, hi image then lo image (row fragments in,
     float* s_tr = (float*)sKt;                                              // transposed fragments out) ... and then its transpose scratch
-    int* s_turn = (int*)((char*)(s_D + QC) + nw * (2 * 16 * KTP));          // [4] whose turn it is to add dQ of query tile qt
-    float* s_wm = (float*)(s_turn + 4);                                     // [3][12] per-wave maxima: (unused), |dO|, |D|
-    uint8_t* qm = (uint8_t*)(s_wm + 36);                                    // [QC] 1 valid query, 0 masked, 2 pad
-    static_assert(16 * TS * 4 <= 2 * 16 * KTP, "transpose scratch inside the K image");
+    int* s_turn = (int*)(sm + L.turn);                                      // [4] whose turn it is to add dQ of query tile qt
+    float* s_wm = (float*)(sm + L.wm);                                      // [3][12] per-wave maxima: (unused), |dO|, |D|
+    uint8_t* qm = (uint8_t*)(sm + L.qm);                                    // [QC] 1 valid query, 0 masked, 2 pad
+    static_assert(att_lds_pl_scratch_fits(DH), "transpose scratch inside the K image");
     // ---- input planes (the P32 planes of the projection GEMMs; see attn_fwd_pl_kernel): a lane's 4 consecutive reduction elements
     // of a row fragment ARE 8 contiguous bytes of the hi terms and 8 of the lo terms -- fragments come straight to registers with
     // the site's scale, no per-tile maxima, no splits

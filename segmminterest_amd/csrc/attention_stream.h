@@ -34,7 +34,7 @@ __global__ __launch_bounds__(att_stream_fwd_threads(DH)) void attn_fwd_stream_ke
     const int bh = xcd_remap(blockIdx.x, gridDim.x) * p.hpb + wave / wq, b = bh / p.H, h = bh % p.H;
     const int La_p = round16(p.La), Lb_p = round16(p.Lb), Tp = La_p + Lb_p, nta = La_p >> 4, nt = Tp >> 4;
     const int col0 = h * DH;
-    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p);
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, blockDim.x);
     __syncthreads();
     const int qt = blockIdx.y * wq + wave % wq;      // this wave's query tile
     if (16 * qt >= p.Lq) return;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(att_bwd_threads(DH)) void attn_bwd_dq_stream_kernel
     const int bh = xcd_remap(blockIdx.x, gridDim.x) * p.hpb + wave / wq, b = bh / p.H, h = bh % p.H;
     const int La_p = round16(p.La), Lb_p = round16(p.Lb), Tp = La_p + Lb_p, nta = La_p >> 4, nt = Tp >> 4;
     const int col0 = h * DH;
-    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p);
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, blockDim.x);
     __syncthreads();
     const int qt = blockIdx.y * wq + wave % wq;
     if (16 * qt >= p.Lq) return;

@@ -39,8 +39,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_wide_kernel(const A
     static_assert(att_wide(DH) && DH % 16 == 0 && NW <= ATT_WIDE_MAXW, "wide heads only");
     using C = AttnCfg<DH>;
     const DropCfg drop_ = drop_live(p.drop);
-    constexpr int RS = DH + 4;                 // LDS row stride (floats): 16-byte aligned rows, conflict-free fragment reads
-    constexpr int TS = 20;                     // row stride of the 16 x 16 transpose scratch
+    constexpr int RS = att_lds_rs(DH);         // LDS row stride (floats)
+    constexpr int TS = ATT_LDS_TS;             // row stride of the 16 x 16 transpose scratch
     constexpr int QC = QCH;                    // queries staged at a time (1 - 3 query tiles)
     constexpr int MAXQT = QC / 16;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -99,12 +99,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_wide_kernel(const A
     uint8_t* km = qm + QC;                                                  // [Tp]
     KeyBlocks<DH> kbk;
     kbk.init(p, b, col0, l15, g);
-    for (int j = threadIdx.x; j < Tp; j += nthr) {         // key flags (stage_kmask with the surviving thread count)
-        uint8_t v;
-        if (j < La_p) v = (j < p.La) ? (p.mka[(size_t)b * p.La + j] ? 1 : 0) : 2;
-        else { const int jb = j - La_p; v = (jb < p.Lb) ? (p.mkb[(size_t)b * p.Lb + jb] ? 1 : 0) : 2; }
-        km[j] = v;
-    }
+    stage_kmask(km, p.mka, p.mkb, b, p.La, p.Lb, La_p, Lb_p, nthr);
     const float fscale = p.scale;
     float am_q = 0.f, am_k = 0.f;
 

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../../include/segmm_hip.h"
 #include "attention16.h"
@@ -195,6 +196,23 @@ static void attn_shape(int n, int H, int max_waves, int want_default, int kn, in
         if (H % c == 0 && c * wq <= max_waves) { hpb = c; break; }
 }
 
+// more than 12 key tiles: the streamed kernels (online softmax, attention_stream.h).  SEGMM_ATT_STREAM=1: at every size (A/B, tests)
+static bool attn_streamed(int Tp) { return Tp > 16 * 12 || knob(K_ATT_STREAM) != 0; }
+// the key-tile count a held one-wave-per-tile kernel is unrolled for: launch(integral_constant<int, NT>)
+template <class F>
+static void attn_by_key_tiles(int Tp, F launch) {
+    if (Tp <= 64) launch(std::integral_constant<int, 4>{});
+    else if (Tp <= 160) launch(std::integral_constant<int, 10>{});
+    else launch(std::integral_constant<int, 12>{});
+}
+// the wave count a fused backward instance is bounded for (4 / 8 / 12; MAXW = 8: wide heads): launch(integral_constant<int, NW>)
+template <int MAXW, class F>
+static void attn_by_waves(int nw, F launch) {
+    if (nw <= 4) launch(std::integral_constant<int, 4>{});
+    else if (MAXW <= 8 || nw <= 8) launch(std::integral_constant<int, 8>{});
+    else if constexpr (MAXW > 8) launch(std::integral_constant<int, 12>{});
+}
+
 // round 5: the planes-in forward (attention_pl.h) when the caller hands the Q / K / V planes of the projection GEMMs and the
 // shape qualifies.  SEGMM_ATT_FWD_PL=0 keeps the fp32-operand kernels (A/B, tests).
 template <int DH>
@@ -245,9 +263,8 @@ static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
     const int nqt = (a.Lq + 15) / 16;
     int wq, hpb;
     attn_shape(nqt, a.H, 5, 1, K_ATT_HPB_FWD, wq, hpb);          // measured: grouping heads does not pay in the forward
-    // more than 12 key tiles: the streamed forward (online softmax, attention_stream.h), before any held form is considered -- the
-    // staged form below would be picked by its LDS test alone.  SEGMM_ATT_STREAM=1: at every size (A/B, tests)
-    if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) {
+    // the streamed forward, before any held form is considered -- the staged form below would be picked by its LDS test alone
+    if (attn_streamed(Tp)) {
         if constexpr (att_wide(DH)) attn_shape(nqt, a.H, ATT_WIDE_THREADS / 64, 1, K_ATT_HPB_FWD, wq, hpb);
         a.hpb = hpb;
         dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);       // one wave per 16-query tile of a head
@@ -285,9 +302,7 @@ static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
                 (void)hipFuncSetAttribute((const void*)attn_fwd_lds_kernel<DH, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 lds_optin = true;
             }
-            if (Tp <= 64) hipLaunchKernelGGL((attn_fwd_lds_kernel<DH, 4>), grid2, block2, lds3, s, a);
-            else if (Tp <= 160) hipLaunchKernelGGL((attn_fwd_lds_kernel<DH, 10>), grid2, block2, lds3, s, a);
-            else hipLaunchKernelGGL((attn_fwd_lds_kernel<DH, 12>), grid2, block2, lds3, s, a);
+            attn_by_key_tiles(Tp, [&](auto NT) { hipLaunchKernelGGL((attn_fwd_lds_kernel<DH, decltype(NT)::value>), grid2, block2, lds3, s, a); });
             LAUNCH_CHECK();
             return 0;
         }
@@ -296,9 +311,7 @@ static int attn_launch_fwd(AttnArgs& a, hipStream_t s) {
     dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);       // one wave per 16-query tile of a head
     const int fpad = knob(K_ATT_FWD_LDS_PAD);      // probe: fewer workgroups per CU
     const size_t lds = (size_t)Tp + (size_t)fpad;
-    if (Tp <= 64) hipLaunchKernelGGL((attn_fwd_kernel<DH, 4>), grid, block, lds, s, a);
-    else if (Tp <= 160) hipLaunchKernelGGL((attn_fwd_kernel<DH, 10>), grid, block, lds, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<DH, 12>), grid, block, lds, s, a);
+    attn_by_key_tiles(Tp, [&](auto NT) { hipLaunchKernelGGL((attn_fwd_kernel<DH, decltype(NT)::value>), grid, block, lds, s, a); });
     LAUNCH_CHECK();
     return 0;
 }
@@ -308,7 +321,7 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
     const int Tp = ((a.La + 15) & ~15) + ((a.Lb + 15) & ~15);
     if (phase == 1) {          // D only
         const long long n = (long long)a.B * a.Lq * a.H;
-        if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) {          // the streamed backward's D: the bits its dQ kernel stores in phase 0
+        if (attn_streamed(Tp)) {          // the streamed backward's D: the bits its dQ kernel stores in phase 0
             const long long tiles = (long long)a.B * a.H * ((a.Lq + 15) / 16);
             hipLaunchKernelGGL((attn_D_stream_kernel<DH>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
             LAUNCH_CHECK();
@@ -365,13 +378,13 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
                 Lq_p = Lq_small;
                 const size_t lds = ((size_t)3 * Lq_p * (DH + 4) + (size_t)nw * 16 * (DH + 4) + 3 * Lq_p + (size_t)nw * 16 * 20 + 4 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp +
                                    (size_t)knob(K_ATT_LDS_PAD);
-#define FUSEDW(NWV) do { if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, true, 16>), grid, block, lds, s, a); \
-                         else if (Lq_p == 32) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, true, 32>), grid, block, lds, s, a); \
-                         else if (one) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, true>), grid, block, lds, s, a); \
-                         else hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, NWV, false>), grid, block, lds, s, a); } while (0)
-                if (nw <= 4) FUSEDW(4);
-                else FUSEDW(8);
-#undef FUSEDW
+                attn_by_waves<ATT_WIDE_MAXW>(nw, [&](auto NWV) {
+                    constexpr int W = decltype(NWV)::value;
+                    if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, W, true, 16>), grid, block, lds, s, a);
+                    else if (Lq_p == 32) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, W, true, 32>), grid, block, lds, s, a);
+                    else if (one) hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, W, true>), grid, block, lds, s, a);
+                    else hipLaunchKernelGGL((attn_bwd_fused_wide_kernel<DH, W, false>), grid, block, lds, s, a);
+                });
             }
             LAUNCH_CHECK();
             return 0;
@@ -386,7 +399,7 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
                 a.hpb = 3;
                 const dim3 grid(a.B * a.H), block(64 * nw);
                 Lq_p = Lq_small;
-                const size_t lds = ((size_t)5 * Lq_p * (DH + 4) + 3 * Lq_p + (size_t)nw * 16 * 20 + 8 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp;
+                const size_t lds = att_lds_fused(DH, Lq_p, nw, Tp, /*merged*/ true).bytes();
                 if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, 4, true, 16>), grid, block, lds, s, a);
                 else hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, 4, true, 32>), grid, block, lds, s, a);
                 LAUNCH_CHECK();
@@ -404,9 +417,6 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
             const dim3 grid((fmode == 1 ? 2 : 1) * a.B * a.H), block(64 * nw);
             const bool one = a.Lq <= ATT_FUSED_QCHUNK;
             Lq_p = ATT_FUSED_QCHUNK;
-            size_t lds = ((size_t)3 * Lq_p * (DH + 4) + 3 * Lq_p + (size_t)nw * 16 * 20 + 4 + 36 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp;
-            const int lds_pad = knob(K_ATT_LDS_PAD);      // probe: fewer workgroups per CU
-            lds += (size_t)lds_pad;
             if constexpr (DH % 16 == 0 && DH <= 48) {
                 if (a.in.Qa) {          // round 5: Q / K / V from the projection GEMMs' planes (attention_pl.h); always in passes of <= 4 waves
                     // (single chunk: the key tiles of a block in passes over <= ATT_WAVES_PL waves.  Three: the 7 tiles of a 100-key block as 3 + 3 + 1,
@@ -414,20 +424,19 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
                     // the weight-gradient GEMMs of the step, +0.5 % of the step: profiles/r6/att_waves_ab.txt.  Results do not depend on it.)
                     const int wcap_pl = knob(K_ATT_WAVES_PL) >= 1 && knob(K_ATT_WAVES_PL) <= 4 ? knob(K_ATT_WAVES_PL) : 3;
                     const int nwp = one && nw > wcap_pl ? wcap_pl : nw;
-                    const size_t ldsp = attn_bwd_pl_lds_bytes<DH>(Lq_p, nwp, Tp);
+                    const size_t ldsp = att_lds_pl(DH, Lq_p, nwp).bytes();
                     const dim3 blockp(64 * nwp);
                     // the repair launch: 512 workgroups that walk the heads (and normally leave at once) instead of one per head
                     const bool walk = (a.pflags & ATT_REPAIR) != 0;
                     const unsigned nwalk = (unsigned)knob(K_ATT_REPAIR_WALK) & ~1u;          // (even: a workgroup keeps its key block)
                     const dim3 gridp(walk && nwalk && grid.x > nwalk ? nwalk : grid.x);
-#define FUSEDPL(NWV) do { if (walk) { if (one) hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, NWV, true, true>), gridp, blockp, ldsp, s, a); \
-                                      else hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, NWV, false, true>), gridp, blockp, ldsp, s, a); } \
-                          else if (one) hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, NWV, true>), grid, blockp, ldsp, s, a); \
-                          else hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, NWV, false>), grid, blockp, ldsp, s, a); } while (0)
-                    if (nwp <= 4) FUSEDPL(4);
-                    else if (nwp <= 8) FUSEDPL(8);
-                    else FUSEDPL(12);
-#undef FUSEDPL
+                    attn_by_waves<ATT_FUSED_MAXW>(nwp, [&](auto NWV) {
+                        constexpr int W = decltype(NWV)::value;
+                        if (walk) { if (one) hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, W, true, true>), gridp, blockp, ldsp, s, a);
+                                    else hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, W, false, true>), gridp, blockp, ldsp, s, a); }
+                        else if (one) hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, W, true>), grid, blockp, ldsp, s, a);
+                        else hipLaunchKernelGGL((attn_bwd_pl_kernel<DH, W, false>), grid, blockp, ldsp, s, a);
+                    });
                     continue;
                 }
                 // fp16x3 matrix-core form (attention16.h).  By default only single-chunk launches with more than 32 queries: with
@@ -444,27 +453,26 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
 #endif
                     const int nw16 = one && wcap >= 1 && nw > wcap ? wcap : nw;
                     const dim3 block16(64 * nw16);
-                    const size_t lds16 = lds - (size_t)(nw - nw16) * 16 * 20 * 4;
-#define FUSED16(NWV) do { if (one) hipLaunchKernelGGL((attn_bwd_fused16_kernel<DH, NWV, true>), grid, block16, lds16, s, a); \
-                          else hipLaunchKernelGGL((attn_bwd_fused16_kernel<DH, NWV, false>), grid, block16, lds16, s, a); } while (0)
-                    if (nw16 <= 4) FUSED16(4);
-                    else if (nw16 <= 8) FUSED16(8);
-                    else FUSED16(12);
-#undef FUSED16
+                    const size_t lds16 = ((size_t)3 * Lq_p * (DH + 4) + 3 * Lq_p + (size_t)nw16 * 16 * 20 + 4 + 36 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp +
+                                         (size_t)knob(K_ATT_LDS_PAD);      // (the pad: probe, fewer workgroups per CU)
+                    attn_by_waves<ATT_FUSED_MAXW>(nw16, [&](auto NWV) {
+                        constexpr int W = decltype(NWV)::value;
+                        if (one) hipLaunchKernelGGL((attn_bwd_fused16_kernel<DH, W, true>), grid, block16, lds16, s, a);
+                        else hipLaunchKernelGGL((attn_bwd_fused16_kernel<DH, W, false>), grid, block16, lds16, s, a);
+                    });
                     continue;
                 }
             }
             SEGMM_REQUIRE(a.Qa, "attn_bwd: no fp32 views were given and the planes-in backward does not take this call (head dims 16, 32, 48)");
             Lq_p = Lq_small;
-            lds = ((size_t)3 * Lq_p * (DH + 4) + 3 * Lq_p + (size_t)nw * 16 * 20 + 4 + (size_t)Lq_p * (DH / 4)) * 4 + Lq_p + Tp;
-#define FUSED(NWV) do { if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, NWV, true, 16>), grid, block, lds, s, a); \
-                        else if (Lq_p == 32) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, NWV, true, 32>), grid, block, lds, s, a); \
-                        else if (one) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, NWV, true>), grid, block, lds, s, a); \
-                        else hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, NWV, false>), grid, block, lds, s, a); } while (0)
-            if (nw <= 4) FUSED(4);
-            else if (nw <= 8) FUSED(8);
-            else FUSED(12);
-#undef FUSED
+            const size_t lds = att_lds_fused(DH, Lq_p, nw, Tp, /*merged*/ false).bytes();
+            attn_by_waves<ATT_FUSED_MAXW>(nw, [&](auto NWV) {
+                constexpr int W = decltype(NWV)::value;
+                if (Lq_p == 16) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, W, true, 16>), grid, block, lds, s, a);
+                else if (Lq_p == 32) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, W, true, 32>), grid, block, lds, s, a);
+                else if (one) hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, W, true>), grid, block, lds, s, a);
+                else hipLaunchKernelGGL((attn_bwd_fused_kernel<DH, W, false>), grid, block, lds, s, a);
+            });
         }
         LAUNCH_CHECK();
         return 0;
@@ -477,10 +485,8 @@ static int attn_launch_bwd(AttnArgs& a, int phase, hipStream_t s) {
         attn_shape(nqt, a.H, att_bwd_threads(DH) / 64, 1, K_ATT_HPB_DQ, wq, hpb);
         a.hpb = hpb;
         dim3 grid(a.B * a.H / hpb, (nqt + wq - 1) / wq), block(64 * wq * hpb);
-        if (Tp > 16 * 12 || knob(K_ATT_STREAM) != 0) hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<DH>), grid, block, Tp, s, a);
-        else if (Tp <= 64) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 4>), grid, block, Tp, s, a);
-        else if (Tp <= 160) hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 10>), grid, block, Tp, s, a);
-        else hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, 12>), grid, block, Tp, s, a);
+        if (attn_streamed(Tp)) hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<DH>), grid, block, Tp, s, a);
+        else attn_by_key_tiles(Tp, [&](auto NT) { hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, decltype(NT)::value>), grid, block, Tp, s, a); });
         LAUNCH_CHECK();
     }
     if (phase == 0 || phase == 3) {

@@ -719,6 +719,87 @@ def test_attention_bwd_on_input_planes_is_independent_of_the_wave_count(request)
         assert torch.equal(dYv, outs[0][0]) and torch.equal(dYu, outs[0][1])
 
 
+def _attn_bwd_repair_protocol(H, B, H_, dh, Lq, La, Lb, bad, seed, with_pin):
+    """The planes-only protocol of a fused attention backward at the op level: an fp32 run, a planes-only run whose delayed scales
+    are ``bad`` times the fitting ones, segmm_site_fixup, the REPAIR launch.  bad != 1 (overflow / below the fp16 window): the
+    repair must leave exactly the planes of the fp32 gradients under the exact scale of their maxima, and that scale in the
+    headers.  bad == 1: site_fixup finds nothing and the repair launch changes nothing -- shown on planes overwritten with a
+    pattern in between, which a repair pass that ran would replace.  The fp32 buffers handed to the planes-only launches stay zero.
+    ``with_pin``: Q / K / V as input planes and no fp32 views in the planes-only launches (the planes-in kernel); Lq != La: the
+    queries are a tensor, a plane buffer and a site of their own."""
+    p = 0.1
+    d = H_ * dh
+    g = torch.Generator().manual_seed(seed)
+    nv, nu = 4, 2
+    own_q = Lq != La
+    Yv = (torch.randn(B * La, nv * d, generator=g) * 0.7).to(DEV)
+    Yu = (torch.randn(B * Lb, nu * d, generator=g) * 0.7).to(DEV)
+    mq = (torch.rand(B, Lq, generator=g) < 0.8).to(DEV)
+    mkb = (torch.rand(B, Lb, generator=g) < 0.7).to(DEV)
+    pin = None
+    if with_pin:
+        assert not own_q
+        plv, hv = _site_planes(H, Yv, Yv.shape[0], nv * d)
+        plu, hu = _site_planes(H, Yu, Yu.shape[0], nu * d)
+        pin = dict(q=(plv, hv, 2 * nv * d), a=(plv, hv, 2 * nv * d), b=(plu, hu, 2 * nu * d))
+    dO = torch.randn(B * Lq, d, generator=g).to(DEV)
+    Qs, mka = Yv, mq
+    if own_q:
+        Qs = (torch.randn(B * Lq, nv * d, generator=g) * 0.7).to(DEV)
+        mka = (torch.rand(B, La, generator=g) < 0.8).to(DEV)
+    views = ((Qs, 0), (Qs, d), nv * d, (Yv, 2 * d), (Yv, 3 * d), nv * d, (Yu, 0), (Yu, d), nu * d)
+    none_views = ((None, 0), (None, d), nv * d, (None, 2 * d), (None, 3 * d), nv * d, (None, 0), (None, d), nu * d)
+    O = torch.empty(B * Lq, d, device=DEV); lse = torch.empty(2, B, H_, Lq, device=DEV)
+    H.attn_fwd(B, H_, dh, Lq, La, Lb, *views, mq, mka, mkb, O, d, lse, drop_p=p, seed=11, site=3, pin=pin)
+    Dv = torch.empty(B * H_ * Lq, device=DEV)
+
+    def bwd(dQs, dYv, dYu, planes=None):
+        dq = dQs if own_q else dYv
+        H.attn_bwd(B, H_, dh, Lq, La, Lb, *(none_views if with_pin and planes is not None else views), mq, mka, mkb, lse, O, d, dO, d, Dv,
+                   (dq, 0), (dq, d), nv * d, (dYv, 2 * d), (dYv, 3 * d), nv * d, (dYu, 0), (dYu, d), nu * d,
+                   drop_p=p, seed=11, site=3, phase=4, pin=pin, planes=planes)
+    grads = [torch.zeros_like(Qs) if own_q else None, torch.zeros_like(Yv), torch.zeros_like(Yu)]
+    bwd(*grads)                                                # fp32 gradients of the same kernel
+    live = [(x, rows, cols) for x, rows, cols in zip(grads, (B * Lq, B * La, B * Lb), (nv * d, nv * d, nu * d)) if x is not None]
+
+    def scale_of(m):          # common.h f16_scale_of: the power of two with m * s in [2^14, 2^15)
+        return 2.0 ** (14 - math.floor(math.log2(m)))
+    fit = [scale_of(float(x.abs().max())) for x, _, _ in live]
+    outs = [_po(H, rows, cols, s_ * bad) for (_, rows, cols), s_ in zip(live, fit)]          # (planes, -, scale tensor, -)
+    hdrs = [H.new_site(DEV)[0] for _ in live]
+    iq, iv, iu = (0, 1, 2) if own_q else (0, 0, 1)          # the query side shares the video tensor, its planes and its site unless Lq != La
+    oq, ov, ou = outs[iq][0], outs[iv][0], outs[iu][0]
+    pln = H.AttnPlanes()
+    bq, bv, bu = oq.data_ptr(), ov.data_ptr(), ou.data_ptr()
+    pln.dqa, pln.dqb, pln.lddq2 = bq, bq + 4 * d, 2 * nv * d
+    pln.dka, pln.dva, pln.lddka2 = bv + 8 * d, bv + 12 * d, 2 * nv * d
+    pln.dkb, pln.dvb, pln.lddkb2 = bu, bu + 4 * d, 2 * nu * d
+    pln.hdr_q, pln.hdr_ka, pln.hdr_kb = hdrs[iq].data_ptr(), hdrs[iv].data_ptr(), hdrs[iu].data_ptr()
+    pln.sin_q, pln.sin_ka, pln.sin_kb = outs[iq][2].data_ptr(), outs[iv][2].data_ptr(), outs[iu][2].data_ptr()
+    pln.flags = H.ATTN_PLANES_ONLY
+    zeros = [None if x is None else torch.zeros_like(x) for x in grads]          # (no fp32 gradient is written under ATTN_PLANES_ONLY)
+    stats = torch.zeros(4, device=DEV)
+    bwd(*zeros, planes=pln)
+    H.site_fixup(*hdrs, stats=stats)
+    exact = [_ref_planes(H, x, rows, cols, s_)[0] for (x, rows, cols), s_ in zip(live, fit)]
+    pln.flags = H.ATTN_PLANES_ONLY | H.ATTN_REPAIR
+    if bad == 1.0:
+        assert all(float(h_[2]) == 0.0 for h_ in hdrs) and float(stats[0]) == 0.0
+        assert all(torch.equal(o[0], e) for o, e in zip(outs, exact))
+        for o in outs:
+            o[0].fill_(9.0)
+        before = [h_.clone() for h_ in hdrs]
+        bwd(*zeros, planes=pln)
+        assert all(bool((o[0] == 9.0).all()) for o in outs)
+        assert all(torch.equal(h_, b_) for h_, b_ in zip(hdrs, before))
+    else:
+        assert all(float(h_[2]) != 0.0 for h_ in hdrs) and float(stats[0]) == float(len(hdrs))
+        bwd(*zeros, planes=pln)
+        assert [float(h_[0]) for h_ in hdrs] == fit
+        assert all(torch.equal(o[0], e) for o, e in zip(outs, exact))
+    assert all(float(z.abs().max()) == 0.0 for z in zeros if z is not None)
+
+
 @pytest.mark.parametrize("B,H_,bad,walk,La,Lb", [(40, 16, 2.0 ** 30, 512, 40, 100), (40, 16, 2.0 ** -30, 512, 40, 100), (3, 16, 2.0 ** 30, 512, 40, 100),
                                                   (3, 16, 2.0 ** 30, 2, 40, 100), (5, 16, 2.0 ** -30, 6, 40, 100), (36, 16, 2.0 ** 30, 512, 100, 40),
                                                   (2, 16, 2.0 ** -30, 4, 100, 40)])
@@ -732,60 +813,25 @@ def test_attention_bwd_repair_launch_walks_the_heads(request, B, H_, bad, walk, 
     H = _abi()
     prev_walk = H.config_set("ATT_REPAIR_WALK", walk)
     request.addfinalizer(lambda: H.config_set("ATT_REPAIR_WALK", prev_walk))
-    dh, Lq, p = 48, La, 0.1
-    d = H_ * dh
-    g = torch.Generator().manual_seed(B + 5)
-    nv, nu = 4, 2
-    Yv = (torch.randn(B * La, nv * d, generator=g) * 0.7).to(DEV)
-    Yu = (torch.randn(B * Lb, nu * d, generator=g) * 0.7).to(DEV)
-    mq = (torch.rand(B, Lq, generator=g) < 0.8).to(DEV)
-    mkb = (torch.rand(B, Lb, generator=g) < 0.7).to(DEV)
-    plv, hv = _site_planes(H, Yv, Yv.shape[0], nv * d)
-    plu, hu = _site_planes(H, Yu, Yu.shape[0], nu * d)
-    pin = dict(q=(plv, hv, 2 * nv * d), a=(plv, hv, 2 * nv * d), b=(plu, hu, 2 * nu * d))
-    views = ((Yv, 0), (Yv, d), nv * d, (Yv, 2 * d), (Yv, 3 * d), nv * d, (Yu, 0), (Yu, d), nu * d)
-    none_views = ((None, 0), (None, d), nv * d, (None, 2 * d), (None, 3 * d), nv * d, (None, 0), (None, d), nu * d)
-    O = torch.empty(B * Lq, d, device=DEV); lse = torch.empty(2, B, H_, Lq, device=DEV)
-    H.attn_fwd(B, H_, dh, Lq, La, Lb, *views, mq, mq, mkb, O, d, lse, drop_p=p, seed=11, site=3, pin=pin)
-    dO = torch.randn(B * Lq, d, generator=g).to(DEV)
-    Dv = torch.empty(B * H_ * Lq, device=DEV)
+    _attn_bwd_repair_protocol(H, B, H_, 48, La, La, Lb, bad, B + 5, True)
 
-    def bwd(dYv, dYu, planes=None):
-        H.attn_bwd(B, H_, dh, Lq, La, Lb, *(views if planes is None else none_views), mq, mq, mkb, lse, O, d, dO, d, Dv,
-                   (dYv, 0), (dYv, d), nv * d, (dYv, 2 * d), (dYv, 3 * d), nv * d, (dYu, 0), (dYu, d), nu * d,
-                   drop_p=p, seed=11, site=3, phase=4, pin=pin, planes=planes)
-    dYv, dYu = torch.zeros_like(Yv), torch.zeros_like(Yu)
-    bwd(dYv, dYu)                                              # fp32 gradients of the same kernel
-    import math
 
-    def scale_of(m):          # common.h f16_scale_of: the power of two with m * s in [2^14, 2^15)
-        return 2.0 ** (14 - math.floor(math.log2(m)))
-    sv, su = scale_of(float(dYv.abs().max())), scale_of(float(dYu.abs().max()))
-    ov, _, scv, _ = _po(H, B * La, nv * d, sv * bad)
-    ou, _, scu, _ = _po(H, B * Lb, nu * d, su * bad)
-    hov, hou = H.new_site(DEV)[0], H.new_site(DEV)[0]
-    pln = H.AttnPlanes()
-    bv, bu = ov.data_ptr(), ou.data_ptr()
-    pln.dqa, pln.dqb, pln.lddq2 = bv, bv + 4 * d, 2 * nv * d
-    pln.dka, pln.dva, pln.lddka2 = bv + 8 * d, bv + 12 * d, 2 * nv * d
-    pln.dkb, pln.dvb, pln.lddkb2 = bu, bu + 4 * d, 2 * nu * d
-    pln.hdr_q = pln.hdr_ka = hov.data_ptr()
-    pln.hdr_kb = hou.data_ptr()
-    pln.sin_q = pln.sin_ka = scv.data_ptr()
-    pln.sin_kb = scu.data_ptr()
-    pln.flags = H.ATTN_PLANES_ONLY
-    zv, zu = torch.zeros_like(Yv), torch.zeros_like(Yu)          # (no fp32 gradient is written under ATTN_PLANES_ONLY)
-    stats = torch.zeros(4, device=DEV)
-    bwd(zv, zu, planes=pln)
-    H.site_fixup(hov, hou, stats=stats)
-    assert float(hov[2]) != 0.0 and float(hou[2]) != 0.0 and float(stats[0]) == 2.0
-    pln.flags = H.ATTN_PLANES_ONLY | H.ATTN_REPAIR
-    bwd(zv, zu, planes=pln)
-    assert float(zv.abs().max()) == 0.0 and float(zu.abs().max()) == 0.0
-    rv, _ = _ref_planes(H, dYv, B * La, nv * d, sv)
-    ru, _ = _ref_planes(H, dYu, B * Lb, nu * d, su)
-    assert float(hov[0]) == sv and float(hou[0]) == su
-    assert torch.equal(ov, rv) and torch.equal(ou, ru)
+@pytest.mark.parametrize("Lq,La,Lb,bad", [(Lq, La, Lb, bad) for Lq, La, Lb in [(40, 40, 100), (20, 20, 1), (100, 40, 100)]
+                                          for bad in (2.0 ** 30, 2.0 ** -30)] + [(40, 40, 100, 1.0)])
+@pytest.mark.parametrize("kernel,dh,mode", [("fused", 64, None), ("fused16", 48, 2), ("wide", 96, None)])
+def test_attention_bwd_repair_of_the_fp32_view_kernels(request, kernel, dh, mode, Lq, La, Lb, bad):
+    """The same protocol through the other three fused backward kernels, on the fp32 views (no input planes): the fp32 kernel
+    (dh = 64), the fp16x3 kernel (dh = 48 under attn_mode 2) and the wide kernel (dh = 96) -- the engine runs planes-only + repair
+    through whichever of them a shape selects.  B = 3, H = 2.  (40, 40, 100): one chunk, 3 and 7 key tiles, the repair pass as
+    ONE launch for both blocks with surplus waves.  (20, 20, 1): the merged short-head form (one workgroup per head for both
+    blocks, its verdict over both blocks' sites) at dh = 64 and 96; the per-block fp16x3 form at dh = 48.  (100, 40, 100): several
+    query chunks, the queries a site of their own.  No block has more than 8 tiles, so the wide kernel's multi-pass carry does not
+    write the fp32 buffers.  bad = 1: a fitting scale, the repair launch leaves everything alone."""
+    H = _abi()
+    if mode is not None:
+        prev = H.attn_mode(mode)
+        request.addfinalizer(lambda: H.attn_mode(prev))
+    _attn_bwd_repair_protocol(H, 3, 2, dh, Lq, La, Lb, bad, 8 + Lq + Lb, False)
 
 
 def test_scales_update():
