@@ -151,9 +151,33 @@ class MLP_Block(_FusedOnly):
 ABLATION_TYPES = ("ours", "CrossAtt", "SelfAtt", "noPos", "noUser", "SelfMLP", "CrossMLP", "noUser_SelfAtt", "w/oAtt")
 
 
+def check_ff_dim_lvls(ff_dim_lvls, n_layers):
+    """The per-layer feed-forward widths as a list of ints -- the ONE statement of which widths run and how.
+
+    A layer's GELU feed-forward network is ``MLP([d_model, ff, d_model])`` (encoder.py:183-184): ``layers.0.weight`` is [ff, d],
+    ``layers.1.weight`` is [d, ff].  Any positive multiple of 4 runs.  A multiple of 32 runs on the plane GEMMs (P32 planes come in
+    blocks of 32 columns); any other multiple of 4 takes, for the four GEMMs that have ff as a dimension, the on-the-fly kernels of
+    the fp32 operands -- what every GEMM of a model whose ``d_model`` is such a number takes.  The fp32 kernels move 4 floats at a
+    time, so a width that is no multiple of 4 is refused here, by layer."""
+    ff = [int(f) for f in ff_dim_lvls]
+    if len(ff) != n_layers:
+        raise ValueError("ff_dim_lvls has %d entries for %d layers" % (len(ff), n_layers))
+    for i, f in enumerate(ff):
+        if f <= 0 or f % 4:
+            raise ValueError("ff_dim_lvls[%d] = %d (layer %d): a feed-forward width must be a positive multiple of 4 "
+                             "(multiples of 32 run on the plane GEMMs)" % (i, f, i))
+    return ff
+
+
 class SegFormerX(nn.Module):
     """Drop-in for encoder.py:327-520.  ``forward(usr_feat, usr_mask, vid_feat, vid_mask)`` returns
-    ``([vid_state[B,S,d]], usr_embedding[B,Lt,d])`` exactly like the reference with output_layers=[-1]."""
+    ``([vid_state[B,S,d]], usr_embedding[B,Lt,d])`` exactly like the reference with output_layers=[-1].
+
+    ``ff_dim_lvls`` gives every encoder layer its own feed-forward width (``check_ff_dim_lvls``: positive multiples of 4; state
+    dict keys and shapes are the reference's, so its checkpoints load unchanged).  Still refused, each with its own message:
+    ``d_model_lvls`` other than ``[d_model_in] * N``, more than one head count, ``sr_ratio > 1``, patch merging and
+    ``output_layers`` other than ``[-1]``.  The MLP ablations (SelfMLP, CrossMLP, w/oAtt) build no encoder layers and ignore
+    ``ff_dim_lvls``, as the reference does."""
 
     def __init__(self, d_model_in=128, d_model_lvls=[128, 256, 512, 1024], num_head_lvls=[2, 4, 8, 16],
                  ff_dim_lvls=[256, 512, 1024, 2048], sr_ratio_lvls=[8, 4, 2, 1], input_vid_dim=768, input_usr_dim=768,
@@ -162,10 +186,12 @@ class SegFormerX(nn.Module):
                  video_id_max=-1, use_pe=1):
         super().__init__()
         d = d_model_in
-        if any(x != d for x in d_model_lvls) or any(x != d for x in ff_dim_lvls):
-            raise NotImplementedError("the reference trainers use d_model_lvls = ff_dim_lvls = [d_model]*N (main...SegMM.py:88-96)")
-        if any(sr != 1 for sr in sr_ratio_lvls) or any(use_patch_merge):
-            raise NotImplementedError("sr_ratio > 1 / patch merging are disabled in the reference trainers (main...SegMM.py:94)")
+        if any(x != d for x in d_model_lvls):
+            raise NotImplementedError("d_model_lvls must be [d_model_in] * N: one model width per backbone (main...SegMM.py:88-96)")
+        if any(sr != 1 for sr in sr_ratio_lvls):
+            raise NotImplementedError("sr_ratio > 1 is disabled in the reference trainers (main...SegMM.py:94)")
+        if any(use_patch_merge):
+            raise NotImplementedError("patch merging is disabled in the reference trainers (main...SegMM.py:94)")
         if len(set(num_head_lvls)) != 1:
             raise NotImplementedError("one head count per backbone")
         self.id_vid = video_id_max != -1
@@ -200,7 +226,8 @@ class SegFormerX(nn.Module):
                                          hidden_activations="ReLU", dropout_rates=dropout, batch_norm=0)
         else:
             self.encoder = SegFormerXEncoder(d, lvls, list(num_head_lvls), list(sr_ratio_lvls),
-                                             list(ff_dim_lvls), list(use_patch_merge), dropout, self.ablation_type)
+                                             check_ff_dim_lvls(ff_dim_lvls, len(lvls)), list(use_patch_merge), dropout,
+                                             self.ablation_type)
         self.output_layers = list(range(len(sr_ratio_lvls))) if output_layers is None else list(output_layers)
         if self.output_layers != [-1]:
             raise NotImplementedError("output_layers must be [-1] as in the reference trainers (main...SegMM.py:95)")

@@ -13,6 +13,9 @@ Per encoder layer (video side; the user side mirrors it when live), reference fi
     Av = attention(Q from Yv, K/V blocks from Yv and Yu, masks, logits dropout)    [encoder.py:64-71,138-156]
     R1 = Xv + dropout(Av . Wff^T + b) ; X1 = LN(R1)                                GEMM epilogue + LN [:163-171]
     H  = dropout(gelu(X1 . W0^T + b0)) ; R2 = X1 + dropout(H . W1^T + b1) ; X2 = LN(R2)            [:202-203; mlp.py:17-23]
+
+W0 is [ff, d] and W1 is [d, ff]: the feed-forward width ff is the layer's and the side's own (``ff_dim_lvls``, encoder.py:183-184),
+H and everything saved of it are [M, ff]; every other tensor of the layer is [M, d].
 """
 from __future__ import annotations
 
@@ -1168,20 +1171,26 @@ class BackboneRun:
         H.pool_tokens(Zu, Lt, Zv, S, out, B, d, POOL_BINS)       # AdaptiveAvgPool1d(40) over cat(user, video) tokens
         return out
 
+    def _ff_width(self, L, side):
+        """Feed-forward width of the layer named ``L`` on ``side``: the rows of its first MLP matrix (``ff_dim_lvls`` entry)."""
+        return int(self.store._params[L + "ff_%s.layers.0.weight" % side].shape[0])
+
     def _side_post_alloc(self, i, side, ref, M, out_is_operand):
         """Buffers and Acts of _side_post, allocated by the caller on the MAIN stream (the chain itself may run on the side
         stream: the caching allocator must never see a block whose first owner is the side stream)."""
         st, d, am = self.store, self.d, self.am
         sn = "%sL%d.%s." % (self.pre, i, side)
+        f = self._ff_width("%sencoder.layers.%d." % (self.pre, i), side)
         return dict(R1=_empty(ref, M, d), m1=_empty(ref, M), r1=_empty(ref, M),
-                    X1=new_act(st, am, M, d, site=sn + "X1", delayed=self.delayed), G=_empty(ref, M, d),
-                    Hh=new_act(st, am, M, d, site=sn + "H", delayed=self.delayed), R2=_empty(ref, M, d), m2=_empty(ref, M), r2=_empty(ref, M),
+                    X1=new_act(st, am, M, d, site=sn + "X1", delayed=self.delayed), G=_empty(ref, M, f),
+                    Hh=new_act(st, am, M, f, site=sn + "H", delayed=self.delayed), R2=_empty(ref, M, d), m2=_empty(ref, M), r2=_empty(ref, M),
                     X2=new_act(st, am, M, d, planes=out_is_operand, site=sn + "X2", delayed=self.delayed))
 
     def _side_post(self, i, L, side, X, A, M, kinds, out_is_operand, bufs=None, head_dot=None):
         """R1 = X + drop(A.Wff^T+b); X1 = LN(R1); H = drop(gelu(X1.W0^T+b0)); R2 = X1 + drop(H.W1^T+b1); X2 = LN(R2).
-        X, A: Acts; returns (X2 Act, saved)."""
+        X, A: Acts; returns (X2 Act, saved).  H (and G, the pre-activation the backward reads) are [M, ff]."""
         st, d, seed = self.store, self.d, self.seed
+        f = self._ff_width(L, side)
         k_ao, k_mi, k_mo = kinds
         ca = L + "cross_attn."
         b = bufs if bufs is not None else self._side_post_alloc(i, side, X.t, M, out_is_operand)
@@ -1191,10 +1200,10 @@ class BackboneRun:
         H.layernorm_fwd(R1, st.p(ca + "ln_%s.weight" % side), st.p(ca + "ln_%s.bias" % side), X1.t, m1, r1, amax=X1.slots, po=X1.po)
         finish_act(st, produced(X1))
         ff = L + "ff_%s.layers." % side
-        _lin_fwd(st, M, d, d, X1, ff + "0.weight", Hh.t, d, bias=st.p(ff + "0.bias"), c_act=Hh,
-                 activation=H.ACT_GELU, aux=G, ldaux=d, drop_p=self.p_inner, seed=seed, site=_site(self.bi, i, k_mi))
+        _lin_fwd(st, M, f, d, X1, ff + "0.weight", Hh.t, f, bias=st.p(ff + "0.bias"), c_act=Hh,
+                 activation=H.ACT_GELU, aux=G, ldaux=f, drop_p=self.p_inner, seed=seed, site=_site(self.bi, i, k_mi))
         finish_act(st, Hh)
-        _lin_fwd(st, M, d, d, Hh, ff + "1.weight", R2, d, bias=st.p(ff + "1.bias"),
+        _lin_fwd(st, M, d, f, Hh, ff + "1.weight", R2, d, bias=st.p(ff + "1.bias"),
                  residual=X1.t, ldr=d, res_period=M, drop_p=self.p_drop, seed=seed, site=_site(self.bi, i, k_mo))
         if head_dot is not None:          # the backbone's output LayerNorm: the Linear(d, 1) head's logits from the same launch
             H.layernorm_fwd_dot(R2, st.p(L + "ln_%s.weight" % side), st.p(L + "ln_%s.bias" % side), X2.t, m2, r2, head_dot[0], head_dot[1],
@@ -1363,25 +1372,27 @@ class BackboneRun:
         return finish_act(st, produced(a))
 
     def _side_post_bwd(self, i, L, side, sv, dX2, M, kinds, gbuf, tag, deferred=None):
-        """Reverse of _side_post.  Returns (dR1, dA): gradient wrt the residual input X and wrt the attention output."""
+        """Reverse of _side_post.  Returns (dR1, dA): gradient wrt the residual input X and wrt the attention output.
+        dG is [M, ff]; its scratch is named by side and layer (``tag``) and keyed by shape, so no two widths share a buffer."""
         st, d, seed, am = self.store, self.d, self.seed, self.amb
+        f = self._ff_width(L, side)
         k_ao, k_mi, k_mo = kinds
         ca = L + "cross_attn."
         ff = L + "ff_%s.layers." % side
         dR2 = st.buf("dR2" + tag, (M, d))
         dM = self._ln_bwd_act("dM" + tag, dX2, sv["R2"], sv["m2"], sv["r2"], L + "ln_%s.weight" % side, L + "ln_%s.bias" % side, gbuf,
                               dR2, M, (self.p_drop, _site(self.bi, i, k_mo)), st.g(ff + "1.bias", gbuf))
-        side_or_defer(st, lambda: _wgrad(st, dM, 0, sv["Hh"], 0, M, d, d, st.g(ff + "1.weight", gbuf)), deferred)
-        dG = new_act(st, am, M, d, key="dG" + tag, site=self.pre + "dG" + tag, delayed=self.delayed)
-        _lin_dgrad(st, M, d, d, dM, ff + "1.weight", dG.t, c_act=dG, activation=H.ACT_DGELU, aux=sv["G"], ldaux=d,
+        side_or_defer(st, lambda: _wgrad(st, dM, 0, sv["Hh"], 0, M, d, f, st.g(ff + "1.weight", gbuf)), deferred)
+        dG = new_act(st, am, M, f, key="dG" + tag, site=self.pre + "dG" + tag, delayed=self.delayed)
+        _lin_dgrad(st, M, f, d, dM, ff + "1.weight", dG.t, c_act=dG, activation=H.ACT_DGELU, aux=sv["G"], ldaux=f,
                    drop_p=self.p_inner, seed=seed, site=_site(self.bi, i, k_mi))
         finish_act(st, dG)
 
         def _w0():
-            _wgrad(st, dG, 0, sv["X1"], 0, M, d, d, st.g(ff + "0.weight", gbuf), gb=st.g(ff + "0.bias", gbuf))
+            _wgrad(st, dG, 0, sv["X1"], 0, M, f, d, st.g(ff + "0.weight", gbuf), gb=st.g(ff + "0.bias", gbuf))
         side_or_defer(st, _w0, deferred)
         dX1 = st.buf("dX1" + tag, (M, d))
-        _lin_dgrad(st, M, d, d, dG, ff + "0.weight", dX1, residual=dR2, ldr=d, res_period=M)
+        _lin_dgrad(st, M, d, f, dG, ff + "0.weight", dX1, residual=dR2, ldr=d, res_period=M)
         dR1 = st.buf("dR1" + tag, (M, d))
         dZ = self._ln_bwd_act("dZ" + tag, dX1, sv["R1"], sv["m1"], sv["r1"], ca + "ln_%s.weight" % side, ca + "ln_%s.bias" % side, gbuf,
                               dR1, M, (self.p_drop, _site(self.bi, i, k_ao)), st.g(ca + "ff_%s.bias" % side, gbuf))
