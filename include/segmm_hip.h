@@ -35,6 +35,16 @@ int segmm_abi_version(void); /* SEGMM_ABI_VERSION of the header the library was 
  * amax: optional zeroed [SEGMM_AMAX_SLOTS] array receiving the partial maxima of |y| (see segmm_gemm_h). */
 int segmm_l1norm(const float* x, float* y, float* inv_scale, int64_t rows, int D, float* amax, uint16_t* planes, int ld2, float* hdr,
                  const float* scale_in, segmm_stream_t stream);
+/* 16-BIT INPUT FEATURES.  The two kernels at the front of the step -- this normalisation (host-fed batches) and segmm_gather_l1 (the
+ * resident table) -- also take their INPUT as IEEE half or bfloat16: half the bytes over PCIe, half the table in HBM.  `elem` names
+ * the element type of the 16-bit words; any other value is an error return, never a launch.  Every element is widened to fp32
+ * exactly (both formats embed in fp32) and the fp32 kernel's arithmetic follows, so the outputs -- fp32 rows, masks, maxima, planes
+ * -- are those of the fp32 entry point on the widened input, bit for bit.  x / table: 8-byte aligned, D % 4 == 0 (rows of a 16-bit
+ * tensor are 8-byte aligned only); every other argument as in the fp32 entry point. */
+#define SEGMM_ELEM_F16 1
+#define SEGMM_ELEM_BF16 2
+int segmm_l1norm_h(const uint16_t* x, int elem, float* y, float* inv_scale, int64_t rows, int D, float* amax, uint16_t* planes, int ld2,
+                   float* hdr, const float* scale_in, segmm_stream_t stream);
 /* PLANE OUTPUTS of producers (the four trailing arguments `planes, ld2, hdr, scale_in` of segmm_l1norm, segmm_gather_l1,
  * segmm_layernorm_fwd / _bwd; segmm_attn_planes_t; c_planes / c_hdr / c_scale_in of segmm_gemm_p): a kernel that writes a
  * tensor some GEMM reads can also write that tensor's P32 fp16 planes (format: segmm_gemm_p) with the DELAYED scale
@@ -470,6 +480,11 @@ int segmm_row_metrics_accumulate(const int32_t* irec, const float* frec, int B, 
  * table[idx[r], :] (/ (sum|.| + 1e-6) if normalize), mask[r] = 1, for idx[r] in [0, n_lines); zeros / 0 otherwise. */
 int segmm_gather_l1(const float* table, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize, float* out,
                     uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in, segmm_stream_t stream);
+/* the same from a table of 16-bit elements (SEGMM_ELEM_F16 / SEGMM_ELEM_BF16, see segmm_l1norm_h): out, mask, maxima and planes are
+ * those of segmm_gather_l1 on the widened table, bit for bit.  table: 8-byte aligned, D % 4 == 0. */
+int segmm_gather_l1_h(const uint16_t* table, int elem, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize,
+                      float* out, uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in,
+                      segmm_stream_t stream);
 /* (f)-1, the step before the gather: index batches assembled on the device from a COMPILED interaction table
  * (FrameDatasetSeq_SegMM._getitem, dataloader_SegMM.py:295-357, as an integer function of data resolved once on the host;
  * segmminterest_amd/feature_store.py: InteractionTable.compile builds the table, DeviceBatches drives this entry point).

@@ -640,6 +640,38 @@ int segmm_l1norm(const float* x, float* y, float* inv_scale, int64_t rows, int D
     return 0;
 }
 
+static inline bool aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
+// the instance of a 16-bit row kernel for (elem, D): the register form with V = 1, 2, 3, 4, 6, 8 raw vectors per lane up to D = 256 V,
+// the two-pass loop form (V = 0) above 2048 columns
+#define ROW_H_LAUNCH(KERNEL, ...)                                                                                        \
+    do {                                                                                                                 \
+        if (elem == SEGMM_ELEM_F16) { ROW_H_LAUNCH_V(KERNEL, ELEM_F16, __VA_ARGS__); }                                   \
+        else { ROW_H_LAUNCH_V(KERNEL, ELEM_BF16, __VA_ARGS__); }                                                         \
+    } while (0)
+#define ROW_H_LAUNCH_V(KERNEL, E, ...)                                                                                   \
+    do {                                                                                                                 \
+        if (D <= 256) hipLaunchKernelGGL((KERNEL<E, 1>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);              \
+        else if (D <= 512) hipLaunchKernelGGL((KERNEL<E, 2>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);         \
+        else if (D <= 768) hipLaunchKernelGGL((KERNEL<E, 3>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);         \
+        else if (D <= 1024) hipLaunchKernelGGL((KERNEL<E, 4>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);        \
+        else if (D <= 1536) hipLaunchKernelGGL((KERNEL<E, 6>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);        \
+        else if (D <= 256 * ROW_MAXV) hipLaunchKernelGGL((KERNEL<E, 8>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERNEL<E, 0>), grid, block, 0, (hipStream_t)stream, __VA_ARGS__);                       \
+    } while (0)
+
+int segmm_l1norm_h(const uint16_t* x, int elem, float* y, float* inv_scale, int64_t rows, int D, float* amax, uint16_t* planes, int ld2,
+                   float* hdr, const float* scale_in, segmm_stream_t stream) {
+    PLANE_OUT_CHECK("l1norm_h", D);
+    SEGMM_REQUIRE(elem == SEGMM_ELEM_F16 || elem == SEGMM_ELEM_BF16, "l1norm_h: elem = %d (SEGMM_ELEM_F16 = 1, SEGMM_ELEM_BF16 = 2)", elem);
+    SEGMM_REQUIRE(x && (y || inv_scale || (planes && scale_in)), "l1norm_h: null pointer");
+    SEGMM_REQUIRE(D > 0 && D % 4 == 0 && aligned8(x) && (!y || aligned16(y)), "l1norm_h: D %% 4 / alignment (D=%d)", D);
+    if (rows <= 0) return 0;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    ROW_H_LAUNCH(l1norm_h_kernel, x, y, inv_scale, (long long)rows, D, amax, plane_out(planes, ld2, hdr, scale_in));
+    LAUNCH_CHECK();
+    return 0;
+}
+
 static int gemm_impl(int layout, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                      const float* bias, const float* row_scale, const float* residual, int ldr, int res_period,
                      int activation, float* aux, int ldaux, float drop_p, uint64_t seed, uint32_t site, int splits,
@@ -1802,6 +1834,21 @@ int segmm_gather_l1(const float* table, int64_t n_lines, int D, const int64_t* i
     if (rows <= 0) return 0;
     hipLaunchKernelGGL(gather_l1_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, (long long)n_lines, D,
                        (const long long*)idx, (long long)rows, normalize, out, mask, amax, plane_out(planes, ld2, hdr, scale_in));
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_gather_l1_h(const uint16_t* table, int elem, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize,
+                      float* out, uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in,
+                      segmm_stream_t stream) {
+    PLANE_OUT_CHECK("gather_l1_h", D);
+    SEGMM_REQUIRE(elem == SEGMM_ELEM_F16 || elem == SEGMM_ELEM_BF16, "gather_l1_h: elem = %d (SEGMM_ELEM_F16 = 1, SEGMM_ELEM_BF16 = 2)", elem);
+    SEGMM_REQUIRE(table && idx && out && n_lines > 0 && D > 0 && D % 4 == 0 && aligned8(table) && aligned16(out),
+                  "gather_l1_h: pointer / D %% 4 / alignment (D=%d)", D);
+    if (rows <= 0) return 0;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    ROW_H_LAUNCH(gather_l1_h_kernel, table, (long long)n_lines, D, (const long long*)idx, (long long)rows, normalize, out, mask, amax,
+                 plane_out(planes, ld2, hdr, scale_in));
     LAUNCH_CHECK();
     return 0;
 }

@@ -68,6 +68,39 @@ __device__ __forceinline__ void st_row4b(float* p, f32x4 v) {
 #endif
 }
 
+// ---- 16-bit input features (ELEM = SEGMM_ELEM_F16 / SEGMM_ELEM_BF16 of the header): four consecutive elements are ONE 8-byte load
+// (a row of a 16-bit [n, D] tensor with D % 4 == 0 is 8-byte aligned, not 16: D = 260 has a 520-byte pitch), ld_row4b's cache
+// policy; the raw words stay in registers (2 VGPRs per 4 elements, as two scalar arrays: an array of 2-vectors is promoted to
+// one wide vector whose every update copies the whole row) and are widened where they are used.  Both formats embed in
+// fp32 exactly: IEEE half through the hardware convert (subnormals included), bfloat16 as bits << 16 -- so a kernel that widens and
+// then does its fp32 twin's arithmetic gives that twin's result on the widened tensor, bit for bit.
+constexpr int ELEM_F16 = 1, ELEM_BF16 = 2;
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 ld_row4h(const uint16_t* p) {
+#if SEGMM_ROW_NT >= 2
+    return __builtin_nontemporal_load((const u32x2*)p);
+#else
+    return *(const u32x2*)p;
+#endif
+}
+template <int ELEM>
+__device__ __forceinline__ f32x4 widen4(uint32_t a, uint32_t b) {
+    if constexpr (ELEM == ELEM_F16) {
+        // the convert instruction itself, on the 32-bit words: written as (float)half the compiler turns the row's raw words into one
+        // wide vector of halves and copies it whole at every update (120 VGPRs at D = 2048 instead of 44)
+        f32x4 v;
+        asm("v_cvt_f32_f16_e32 %0, %1" : "=v"(v.x) : "v"(a));
+        asm("v_cvt_f32_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(v.y) : "v"(a));
+        asm("v_cvt_f32_f16_e32 %0, %1" : "=v"(v.z) : "v"(b));
+        asm("v_cvt_f32_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(v.w) : "v"(b));
+        return v;
+    } else {
+        return f32x4{__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u), __uint_as_float(b << 16), __uint_as_float(b & 0xffff0000u)};
+    }
+}
+template <int ELEM>
+__device__ __forceinline__ f32x4 widen4(u32x2 r) { return widen4<ELEM>(r.x, r.y); }
+
 // ---------------------------------------------------------------- counter-based dropout stream
 // Dropout masks are a pure function of (seed, site, element index), so the backward kernels
 // regenerate them instead of storing them.  The generator is a stateless integer hash (two chained

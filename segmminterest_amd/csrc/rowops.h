@@ -79,6 +79,69 @@ __global__ __launch_bounds__(256) void l1norm_reg_kernel(const float* __restrict
     }
 }
 
+// The same for a 16-bit x (ELEM: IEEE half or bfloat16, common.h widen4): every element is widened to fp32 exactly, then the
+// arithmetic above -- the same four columns per lane, summation order, wave reduction, true division, plane calls -- so the result
+// is segmm_l1norm's on the widened tensor, bit for bit.  V > 0: the row's RAW words stay in registers between the two passes (2 VGPRs
+// per 4 elements, D <= 256 V <= 2048) and x is read once; V == 0: l1norm_kernel's two-pass loop, for wider rows.
+template <int ELEM, int V>
+__global__ __launch_bounds__(256) void l1norm_h_kernel(const uint16_t* __restrict__ x, float* y, float* inv_scale, long long rows, int D,
+                                                       float* amax, PlaneOut po) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const uint16_t* xr = x + row * D;
+    uint32_t ra[V > 0 ? V : 1], rb[V > 0 ? V : 1];
+    float s = 0.f;
+    if constexpr (V > 0) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const int c = lane * 4 + i * 256;
+            ra[i] = rb[i] = 0u;
+            if (c < D) {
+                const u32x2 w = ld_row4h(xr + c);
+                ra[i] = w.x; rb[i] = w.y;
+                const f32x4 v = widen4<ELEM>(ra[i], rb[i]);
+                s += fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w);
+            }
+        }
+    } else {
+        for (int c = lane * 4; c < D; c += 256) {
+            const f32x4 v = widen4<ELEM>(ld_row4h(xr + c));
+            s += fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w);
+        }
+    }
+    s = wave_sum(s);
+    const float inv = 1.0f / (s + 1e-6f);
+    if (inv_scale && lane == 0) inv_scale[row] = inv;
+    const float ps = plane_scale(po);
+    if (y || ps > 0.f) {
+        const float den = s + 1e-6f;
+        float am = 0.f;
+        if constexpr (V > 0) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const int c = lane * 4 + i * 256;
+                if (c < D) {
+                    f32x4 o = widen4<ELEM>(ra[i], rb[i]);
+                    o.x /= den; o.y /= den; o.z /= den; o.w /= den;
+                    if (y) st_row4b(y + row * D + c, o);
+                    if (ps > 0.f) plane_store4_pair(po.p, po.ld2, row, c, o, ps);
+                    am = absmax4(am, o);
+                }
+            }
+        } else {
+            for (int c = lane * 4; c < D; c += 256) {
+                f32x4 o = widen4<ELEM>(ld_row4h(xr + c));
+                o.x /= den; o.y /= den; o.z /= den; o.w /= den;
+                if (y) *(f32x4*)(y + row * D + c) = o;
+                if (ps > 0.f) plane_store4_pair(po.p, po.ld2, row, c, o, ps);
+                am = absmax4(am, o);
+            }
+        }
+        plane_finish(po, amax, am, (unsigned)row, ps, row == 0 && lane == 0);
+    }
+}
+
 // ---------------------------------------------------------------- LayerNorm forward (eps 1e-12, encoder.py:39-40)
 // y = LN(x) * gamma + beta, optional dropout on y (embedding, encoder.py:461,471); saves mean / rstd.
 // V = float4 per lane (d <= 256 V): the row lives in 4V registers, so the register count -- and with it the

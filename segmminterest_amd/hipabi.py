@@ -226,7 +226,7 @@ def torch_fallback(what):
     result without any error."""
     if RECORDER is not None:
         raise RuntimeError("record(): %s runs a torch kernel inside the step; a recorded step would silently drop it "
-                           "(pass bool masks, int64 ids / labels and contiguous fp32 features, at most %d ids per table lookup)" % (what, ARGSORT_MAX))
+                           "(pass bool masks, int64 ids / labels and contiguous float32 / float16 / bfloat16 features, at most %d ids per table lookup)" % (what, ARGSORT_MAX))
 
 
 def mark(kind, backbone=0, layer=0):
@@ -397,13 +397,34 @@ def _po(po):
     return _NO_PO if po is None else po.args()
 
 
+ELEM_F16, ELEM_BF16 = _K["SEGMM_ELEM_F16"], _K["SEGMM_ELEM_BF16"]
+_ELEM = {torch.float16: ELEM_F16, torch.bfloat16: ELEM_BF16}          # 16-bit input features -> the ``elem`` code of the _h entry points
+
+
+def _feat(t, name):
+    """The ``elem`` code of an input feature tensor (None: float32); refuses every other dtype and non-contiguous views."""
+    if t.dtype != torch.float32 and t.dtype not in _ELEM:
+        raise RuntimeError("%s is %s; input features are torch.float32, torch.float16 or torch.bfloat16" % (name, t.dtype))
+    if not t.is_contiguous():
+        raise RuntimeError("%s (%s) must be contiguous" % (name, t.dtype))
+    return _ELEM.get(t.dtype)
+
+
 def l1norm(x, out=None, inv_scale=None, amax=None, po=None):
-    """``amax``: optional zeroed [AMAX_SLOTS] vector that receives the partial maxima of |out| (fp16x3 GEMM operand);
-    ``po``: optional plane output (PO)."""
+    """``x``: float32, or float16 / bfloat16 (widened exactly in the kernel: the float32 result on ``x.float()``, bit for bit);
+    ``out`` / ``inv_scale``: float32.  ``amax``: optional zeroed [AMAX_SLOTS] vector that receives the partial maxima of |out|
+    (fp16x3 GEMM operand); ``po``: optional plane output (PO)."""
     _dev(x)
+    elem = _feat(x, "l1norm: x")
+    for t, name in ((out, "out"), (inv_scale, "inv_scale")):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError("l1norm: %s must be float32 whatever x is (got %s)" % (name, t.dtype))
     D = x.shape[-1]
     rows = x.numel() // D
-    _check(lib().segmm_l1norm(_ptr(x), _ptr(out), _ptr(inv_scale), rows, D, _ptr(amax), *_po(po), _stream()), "segmm_l1norm")
+    if elem is None:
+        _check(lib().segmm_l1norm(_ptr(x), _ptr(out), _ptr(inv_scale), rows, D, _ptr(amax), *_po(po), _stream()), "segmm_l1norm")
+    else:
+        _check(lib().segmm_l1norm_h(_ptr(x), elem, _ptr(out), _ptr(inv_scale), rows, D, _ptr(amax), *_po(po), _stream()), "segmm_l1norm_h")
 
 
 def gemm(layout, M, N, K, A, lda, B, ldb, Cout, ldc, bias=None, row_scale=None, residual=None, ldr=0, res_period=0,
@@ -1116,17 +1137,28 @@ def row_metrics_accumulate(irec, frec, acc, S):
 
 
 def gather_l1(table, idx, normalize=True, out=None, mask=None, amax=None, po=None):
-    """out[..., :] = (L1-normalised) table[idx[...]], mask[...] = idx in range; idx int64 of any shape."""
+    """out[..., :] = (L1-normalised) table[idx[...]], mask[...] = idx in range; idx int64 of any shape.  ``table``: float32, or
+    float16 / bfloat16 (widened exactly in the kernel: the float32 result on ``table.float()``, bit for bit); ``out``: float32."""
     _dev(table, idx)
+    elem = _feat(table, "gather_l1: table")
+    if table.dim() != 2:
+        raise RuntimeError("gather_l1: table must be [n_lines, D] (got %s)" % (tuple(table.shape),))
+    if out is not None and out.dtype != torch.float32:
+        raise RuntimeError("gather_l1: out must be float32 whatever the table is (got %s)" % out.dtype)
     D = table.shape[1]
     rows = idx.numel()
     if out is None:
         out = torch.empty(tuple(idx.shape) + (D,), dtype=torch.float32, device=table.device)
     if mask is None:
         mask = torch.empty(tuple(idx.shape), dtype=torch.uint8, device=table.device)
-    with _kprof("gather_l1", rows * (8 * D + 9)):
-        _check(lib().segmm_gather_l1(_ptr(_f32c(table, "table")), table.shape[0], D, _ptr(idx.contiguous()), rows, int(bool(normalize)),
-                                     _ptr(out), _ptr(mask), _ptr(amax), *_po(po), _stream()), "segmm_gather_l1")
+    if elem is None:
+        with _kprof("gather_l1", rows * (8 * D + 9)):
+            _check(lib().segmm_gather_l1(_ptr(table), table.shape[0], D, _ptr(idx.contiguous()), rows, int(bool(normalize)),
+                                         _ptr(out), _ptr(mask), _ptr(amax), *_po(po), _stream()), "segmm_gather_l1")
+    else:          # a 16-bit table: 2 D bytes read, 4 D written per row
+        with _kprof("gather_l1", rows * (6 * D + 9)):
+            _check(lib().segmm_gather_l1_h(_ptr(table), elem, table.shape[0], D, _ptr(idx.contiguous()), rows, int(bool(normalize)),
+                                           _ptr(out), _ptr(mask), _ptr(amax), *_po(po), _stream()), "segmm_gather_l1_h")
     return out, mask.view(torch.bool)
 
 

@@ -878,11 +878,12 @@ class Trainer:
         return True
 
     def normalize(self, key, x):
-        """a1: x / (sum|x| + 1e-6) over the feature dim, into a persistent buffer."""
+        """a1: x / (sum|x| + 1e-6) over the feature dim, into a persistent float32 buffer.  ``x``: float32, or float16 / bfloat16 (half
+        the bytes over the host link; hipabi.l1norm widens exactly) -- the single point where a batch's feature dtype enters the step."""
         bk = (key, self._slot)
         buf = self._norm.get(bk)
         if buf is None or buf.shape != x.shape or buf.device != x.device:
-            buf = self._norm[bk] = torch.empty_like(x)
+            buf = self._norm[bk] = torch.empty(x.shape, dtype=torch.float32, device=x.device)
         act = self._input_act(key, buf, planes_only=True)
         # the GEMM that reads ``buf`` needs max|buf| (and, on the plane engine, its fp16 planes): both are folded into this
         # kernel instead of separate passes over the features.  Planes only (training steps after the first): ``buf`` is then
@@ -1133,12 +1134,22 @@ class Trainer:
                 raise RuntimeError("record(): batch[%r] is not contiguous" % k)
             # the zero-copy paths of the step: anything else is converted by a torch kernel, which a replay would drop (the
             # conversions also raise by themselves while recording: hipabi.torch_fallback)
-            if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32:
-                raise RuntimeError("record(): batch[%r] is %s; the recorded step takes fp32 features" % (k, v.dtype))
+            # (16-bit features: only the two tensors that go through normalize(); the recorded commands carry their element size, and
+            # run_recorded() refuses a batch of another dtype)
+            if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32 and not (
+                    k in ("user", "photo") and v.dtype in (torch.float16, torch.bfloat16)):
+                raise RuntimeError("record(): batch[%r] is %s; the recorded step takes float32 features (batch['user'] / batch['photo']: "
+                                   "float32, float16 or bfloat16)" % (k, v.dtype))
             if torch.is_tensor(v) and k.endswith("_mask") and v.dtype != torch.bool:
                 raise RuntimeError("record(): batch[%r] is %s; the recorded step takes bool masks" % (k, v.dtype))
             if torch.is_tensor(v) and not v.is_floating_point() and v.dtype not in (torch.bool, torch.int64):
                 raise RuntimeError("record(): batch[%r] is %s; the recorded step takes int64 ids and labels" % (k, v.dtype))
+        # one feature dtype per recorded batch: a batch that carries 16-bit features carries both tensors so (a pipeline stores its
+        # features in one format); a half-precision tensor next to a float32 one is the stray conversion record() has always refused
+        fdt = {k: batch[k].dtype for k in ("user", "photo") if torch.is_tensor(batch.get(k)) and batch[k].is_floating_point()}
+        if len(set(fdt.values())) > 1:
+            raise RuntimeError("record(): batch['user'] is %s and batch['photo'] is %s; the recorded step takes both feature tensors in "
+                               "one dtype (float32, float16 or bfloat16)" % (fdt["user"], fdt["photo"]))
         # the step may name tensors of the PREVIOUS step's batch (id mode: the rows the last backward scattered into the table
         # gradient are cleared by id list): the last warm-up step runs on a copy of the batch, so that such pointers can be told
         # from the current batch's and re-based to the previous batch at replay
