@@ -458,6 +458,18 @@ int segmm_auc_counts(const float* score, const int8_t* label, const int64_t* seg
                      segmm_stream_t stream);
 int segmm_survival(const float* interest, int ld, const int64_t* gt, float* surv, int8_t* label, int B, int S,
                    segmm_stream_t stream);
+/* The tail of a validation batch in ONE launch (Trainer.valid_model(recorded=True); additive to ABI 30): what the eager pass does
+ * with sigmoid, * exposure, one host permutation per valid row and segmm_rank_leave.
+ * segmm_valid_rows: logits [B, ld] (ld >= S), exposure [S], gt [B, S] in {1,0,-1,-2}.  interest[b, s] = sigmoid(logits[b, s]) *
+ *   exposure[s] in fp32 (the loss kernels' sigmoid); validity, the 1.1 fill (masked), the target and ranks[B] are segmm_rank_leave's
+ *   on those interests (0 <= seq_valid <= S).  permute != 0 (S <= 256): the candidates of row b are shuffled by a permutation of
+ *   0 .. S-1 drawn in the kernel from the library's counter hash, keyed by (seed, site, row0 + b) -- segmm_rand_perm_rows' draw for
+ *   row row0 + b: the reference's distribution, not numpy's bit stream; a row draws the same permutation in whichever batch it sits.
+ *   interests [B, S] and perm_out [B, S] (the permutation used: candidate j is position perm_out[b, j]; the identity without
+ *   permute) are optional outputs.  Any S >= 1 without permute; B == 0 launches nothing; row0 >= 0. */
+int segmm_valid_rows(const float* logits, int ld, const float* exposure, const int64_t* gt, int B, int S, int masked, int seq_valid,
+                     int permute, uint64_t seed, uint32_t site, int64_t row0, int32_t* ranks, float* interests, int32_t* perm_out,
+                     segmm_stream_t stream);
 /* Per-row metrics of the test phase (main_eval_batch, my_evaluation.py:249-266; TOP_K_leave(test=1); --eval_cold,
  * --count_view_completion).  Floating-point results, unlike the three above; one thread per row with segmm_survival's
  * sequential fp32 recurrence, so surv is bit-identical to it.

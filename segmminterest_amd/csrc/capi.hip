@@ -1776,6 +1776,28 @@ int segmm_rank_leave(const float* x, int ldx, const int64_t* gt, const int32_t* 
     return 0;
 }
 
+int segmm_valid_rows(const float* logits, int ld, const float* exposure, const int64_t* gt, int B, int S, int masked, int seq_valid,
+                     int permute, uint64_t seed, uint32_t site, int64_t row0, int32_t* ranks, float* interests, int32_t* perm_out,
+                     segmm_stream_t stream) {
+    SEGMM_REQUIRE(exposure, "valid_rows: exposure is null (the [S] exposure probabilities the interests are multiplied by)");
+    SEGMM_REQUIRE(logits && gt && ranks, "valid_rows: null logits / gt / ranks");
+    SEGMM_REQUIRE(S >= 1 && B >= 0 && ld >= S, "valid_rows: S = %d < 1 / B = %d < 0 / ld = %d < S", S, B, ld);
+    SEGMM_REQUIRE(seq_valid >= 0 && seq_valid <= S, "valid_rows: seq_valid = %d outside 0 .. S = %d", seq_valid, S);
+    SEGMM_REQUIRE(!permute || S <= 256, "valid_rows: permute draws a row's permutation in one wave, S = %d > 256 is not supported", S);
+    SEGMM_REQUIRE(row0 >= 0, "valid_rows: row0 < 0");
+    if (B == 0) return 0;
+    const DropCfg d = make_drop(0.5f, seed, site);
+    if (permute) {
+        LAUNCH_ROW_WAVES(valid_rows_kernel, B, S, stream, logits, ld, exposure, (const long long*)gt, B, S, masked, seq_valid, d,
+                         (long long)row0, (int*)ranks, interests, (int*)perm_out);
+    } else {
+        hipLaunchKernelGGL(valid_rows_kernel<0>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, ld, exposure,
+                           (const long long*)gt, B, S, masked, seq_valid, d, (long long)row0, (int*)ranks, interests, (int*)perm_out);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int segmm_auc_counts(const float* score, const int8_t* label, const int64_t* seg_off, int n_seg, int64_t* out,
                      segmm_stream_t stream) {
     SEGMM_REQUIRE(score && label && seg_off && out, "auc_counts: null pointer");

@@ -176,6 +176,35 @@ __device__ __forceinline__ uint2 drop_rand_quad(const DropCfg& d, uint64_t q) {
     const uint32_t b = mix32(a ^ d.seed_hi ^ 0x68E31DA4u);
     return make_uint2(a, b);
 }
+// One row's uniformly random permutation of 0 .. S-1 by rank counting (rand_perm_rows_kernel, valid_rows_kernel): one wave per row,
+// lane l draws the 32-bit keys of the indices l, l + 64, ... (R = ceil(S / 64) of them, counters row * stride + index of the site's
+// stream) and counts, for each, the (key, index) pairs of the row below it: rank[r] = the position of index r * 64 + lane in the
+// permutation.  The row's keys go through ``keys`` (this wave's 64 R words of LDS): every lane reads key j at the same address, a
+// broadcast read.  Contains a workgroup barrier: EVERY thread of the workgroup calls it, ``active`` = false skips the counting.
+// Counter stride of a row: 64 for S <= 64 (R = 1), 256 beyond -- rows of up to 64 keep the stream recorded noPos steps drew from.
+template <int R>
+__device__ __forceinline__ void perm_row_draw(const DropCfg& d, uint64_t row, int S, int lane, uint32_t* keys, bool active, int (&rank)[R]) {
+    constexpr uint64_t kStride = R == 1 ? 64u : 256u;
+    uint32_t key[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint2 x = drop_rand_quad(d, row * kStride + (uint64_t)(r * 64 + lane));
+        key[r] = x.x;
+        rank[r] = 0;
+        keys[r * 64 + lane] = x.x;
+    }
+    __syncthreads();
+    if (!active) return;
+    for (int j = 0; j < S; ++j) {
+        const uint32_t kj = keys[j];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            rank[r] += (kj < key[r] || (kj == key[r] && j < r * 64 + lane)) ? 1 : 0;
+    }
+}
+// the logistic function of the loss kernels (loss.h) and of the validation tail (evalops.h valid_rows_kernel)
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 __device__ __forceinline__ f32x4 drop_apply4(const DropCfg& d, uint64_t q, f32x4 v) {
     const uint2 r = drop_rand_quad(d, q);
     v.x = ((r.x & 0xffffu) >= d.thresh) ? v.x * d.scale : 0.f;

@@ -4,7 +4,8 @@
 //    INTEGER count ("how many positions sort before the target, ties by the lower index" -- what np.argsort gives),
 //    AUC is the Mann-Whitney statistic as INTEGER pair counts (2*less + equal), so both are bit-exact against the
 //    numpy/sklearn reference for the same float inputs; nothing here rounds.  The reference moves the whole dev set
-//    to the host every 30 steps to do this with numpy.
+//    to the host every 30 steps to do this with numpy.  valid_rows_kernel is the whole tail of a validation batch (interests, the
+//    candidate shuffles, the rank) in one launch, for a pass that never waits for the host between batches.
 //  * feature gather (dataloader_SegMM.py:271-362): per row up to S + Lt feature vectors picked from a resident
 //    [n_lines, D] table by index, padded, L1-normalised (main...SegMM.py:272-273) and masked -- HBM-bound,
 //    (S + Lt) * D * 4 bytes per row in, the same out, instead of a 573 KB/row host->device copy.
@@ -73,6 +74,81 @@ __global__ __launch_bounds__(256) void rank_leave_kernel(const float* __restrict
         ranks[b] = rank;
         atomicAdd(hist + rank, 1);
     }
+}
+
+// ---------------------------------------------------------------- the tail of a validation batch in one launch
+// (Trainer.valid_model: interests = sigmoid(logits) * exposure, the candidate shuffles of TOP_K_leave, the leave rank).  One wave
+// per row, four rows per workgroup.  interest[b, s] = sigmoidf_(logits[b, s]) * exposure[s] in fp32 (the loss kernels' sigmoid);
+// validity, the 1.1 fill of padded positions (masked), the target and the rank are rank_leave_kernel's, on those interests.
+// R > 0 (permute, S <= 64 R <= 256): the row's candidate permutation is drawn here by perm_row_draw (common.h), keyed by
+// (seed, site, row0 + b) -- a row draws the same permutation in whichever batch or slot it sits.  Lane l owns the source indices
+// i = l, l + 64, ...; rank[r] is the candidate position j of index i (perm[j] = i), so the permuted row is never materialised: the
+// target sits at the position of index view_len, every lane compares its own values at their positions.  R == 0: candidates as
+// they are (j = i), any S.  interests [B, S] / perm_out [B, S] (the permutation used; the identity for R == 0) are optional.
+__device__ __forceinline__ float valid_interest(float logit, float expo) { return sigmoidf_(logit) * expo; }
+template <int R>
+__global__ __launch_bounds__(256) void valid_rows_kernel(const float* __restrict__ logits, int ld, const float* __restrict__ exposure,
+                                                         const long long* __restrict__ gt, int B, int S, int masked, int seq_valid,
+                                                         DropCfg d0, long long row0, int* __restrict__ ranks,
+                                                         float* __restrict__ interests, int* __restrict__ perm_out) {
+    constexpr int RR = R > 0 ? R : 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + w;
+    int pos[RR];
+    if constexpr (R > 0) {
+        __shared__ uint32_t keys[4][64 * RR];
+        perm_row_draw<RR>(drop_live(d0), (uint64_t)(row0 + b), S, lane, keys[w], b < B, pos);
+    }
+    if (b >= B) return;
+    const long long* g = gt + (size_t)b * S;
+    const float* xr = logits + (size_t)b * ld;
+    int vl = 0, dur = 0;
+    for (int i = lane; i < S; i += 64) {
+        const long long v = g[i];
+        vl += v == 1;
+        dur += v != -2;
+    }
+    vl = wave_sum_i(vl);
+    dur = wave_sum_i(dur);
+    const bool valid = masked ? (vl != dur) : (vl < seq_valid);
+    const int ts = min(vl, S - 1);          // source index of the target (a valid row has view_len < S)
+    float tv = valid_interest(xr[ts], exposure[ts]);
+    if (masked && g[ts] == -2) tv = 1.1f;
+    int t = ts;                             // ... and its candidate position
+    if constexpr (R > 0) {
+        int mine = 0;
+#pragma unroll
+        for (int r = 0; r < RR; ++r)
+            if (r == (ts >> 6)) mine = pos[r];
+        t = __shfl(mine, ts & 63, 64);
+    }
+    int cnt = 0;
+    float* ir = interests ? interests + (size_t)b * S : nullptr;
+    int* pr = perm_out ? perm_out + (size_t)b * S : nullptr;
+    if constexpr (R > 0) {
+#pragma unroll
+        for (int r = 0; r < RR; ++r) {
+            const int i = r * 64 + lane;
+            if (i < S) {
+                float v = valid_interest(xr[i], exposure[i]);
+                if (ir) ir[i] = v;
+                if (masked && g[i] == -2) v = 1.1f;
+                const int j = pos[r];          // < S: only indices < S were counted
+                if (pr) pr[j] = i;
+                cnt += (v < tv) || (v == tv && j < t);
+            }
+        }
+    } else {
+        for (int i = lane; i < S; i += 64) {
+            float v = valid_interest(xr[i], exposure[i]);
+            if (ir) ir[i] = v;
+            if (masked && g[i] == -2) v = 1.1f;
+            if (pr) pr[i] = i;
+            cnt += (v < tv) || (v == tv && i < t);
+        }
+    }
+    cnt = wave_sum_i(cnt);
+    if (lane == 0) ranks[b] = valid ? cnt + 1 : 0;
 }
 
 // ---------------------------------------------------------------- AUC as integer pair counts, per segment

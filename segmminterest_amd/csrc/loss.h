@@ -37,7 +37,7 @@ struct LossArgs {
     float* parts;                   // [B, L_PSTRIDE] per-row, already normalised, contributions (cols >= 9 zero)
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// (sigmoidf_: common.h)
 __device__ __forceinline__ float bce_logits(float x, float t) {
     return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
 }
@@ -460,35 +460,18 @@ __global__ void rand_ids_kernel(long long* __restrict__ out, long long n, long l
         if (2 * q + 1 < n) out[2 * q + 1] = lo + (long long)(((unsigned long long)r.y * span) >> 32);
     }
 }
-// noPos (encoder.py:428-429: a fresh torch.randperm(S) per row): one wave per row, striped as in loss_fwd_bwd_kernel -- lane l
-// draws the 32-bit keys of the indices l, l + 64, ... (R = ceil(S / 64) of them) and counts, for each, the (key, index) pairs of
-// the row below it: the index's position in the permutation, a uniformly random one.  The row's keys go through LDS (256 R bytes
-// per wave): every lane reads key j at the same address, a broadcast read -- 256 cross-lane reads with compile-time lanes put
-// the whole row into scalar registers and spilled them.  Only indices < S are counted, so every rank is < S.
+// noPos (encoder.py:428-429: a fresh torch.randperm(S) per row): one wave per row, striped as in loss_fwd_bwd_kernel -- the draw
+// is perm_row_draw (common.h: keys from the counter hash, each index's position by rank counting, the row's keys through 256 R
+// bytes of LDS per wave -- 256 cross-lane reads with compile-time lanes put the whole row into scalar registers and spilled
+// them).  Only indices < S are counted, so every rank is < S.
 template <int R>
 __global__ __launch_bounds__(256) void rand_perm_rows_kernel(float* __restrict__ out, int rows, int S, DropCfg d0) {
     __shared__ uint32_t keys[4][64 * R];
-    // counter stride of a row: 64 for S <= 64 (R = 1), 256 beyond -- rows of up to 64 keep the stream recorded noPos steps drew from
-    constexpr uint64_t kStride = R == 1 ? 64u : 256u;
     const DropCfg d = drop_live(d0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, row = blockIdx.x * 4 + w;
-    uint32_t key[R];
     int rank[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint2 x = drop_rand_quad(d, (uint64_t)row * kStride + (uint64_t)(r * 64 + lane));
-        key[r] = x.x;
-        rank[r] = 0;
-        keys[w][r * 64 + lane] = x.x;
-    }
-    __syncthreads();
+    perm_row_draw<R>(d, (uint64_t)row, S, lane, keys[w], row < rows, rank);
     if (row >= rows) return;
-    for (int j = 0; j < S; ++j) {
-        const uint32_t kj = keys[w][j];
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            rank[r] += (kj < key[r] || (kj == key[r] && j < r * 64 + lane)) ? 1 : 0;
-    }
 #pragma unroll
     for (int r = 0; r < R; ++r)
         if (r * 64 + lane < S) out[(size_t)row * S + rank[r]] = (float)(r * 64 + lane);      // row: a permutation of 0 .. S-1 (floats)

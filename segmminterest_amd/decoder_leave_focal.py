@@ -413,6 +413,7 @@ class MultiScaleTemporalDetrLeaveFocal(nn.Module):
             if self._loss_spec is None:
                 self._loss_spec = LossSpec(self.model_cfg)
             total, losses, logits = HeadLossFn.apply(self, True, v1, v2, gt, *hp)
+            self.__dict__["_losses_vec"] = losses          # the 12 loss slots as ONE tensor (Trainer._valid_tail copies them in one command)
             out = {}
             for name in self._loss_spec.loss_list:
                 out[name] = losses[_LIDX[name]]

@@ -46,6 +46,7 @@ MLP_VARIANTS = ("CrossMLP", "SelfMLP", "w/oAtt")       # ablations that replace 
 K_MLP0 = 11                                             # dropout kinds 11.. : hidden layers of the ablation MLP_Block
 # streams of the device-side draws that replace the reference's host draws in a device-state / recorded step (same hash, own sites)
 SITE_NOUSER_FEAT, SITE_NOUSER_IDS, SITE_NOPOS = 3 * 4096 + 1, 3 * 4096 + 2, 3 * 4096 + 3
+SITE_VALID_PERM = 3 * 4096 + 64                         # candidate shuffles of a recorded validation pass (segmm_valid_rows)
 POOL_BINS = 40                                          # nn.AdaptiveAvgPool1d(40), encoder.py:396
 
 
@@ -231,6 +232,27 @@ class ParamStore:
 
     def hdr_step_end(self):
         self.step_arena = False
+
+    @contextlib.contextmanager
+    def hdr_private_arena(self, holder: dict):
+        """Step-arena mode on an arena of the CALLER's (``holder["arena"]``, made on first use; ``holder["used"]`` = the most rows a
+        pass under it has drawn): the launch sequence of a validation batch is recorded under it (Trainer.valid_enqueue), so that its
+        replays name header rows that nothing else hands out -- neither the training step's arena nor the wrapping ring.  Rows are
+        handed out from row 0; clearing them before the producers start is the caller's (a fill command inside the replay)."""
+        dev = self.flat.device
+        if holder.get("arena") is None or holder["arena"].device != dev:
+            holder["arena"] = torch.zeros((self.HDR_RING_ROWS, H.SITE_FLOATS), dtype=torch.float32, device=dev)
+            holder["used"] = 0
+        keys = ("_hdr_arena", "_arena_off", "_arena_used", "step_arena")
+        saved = {k: self.__dict__[k] for k in keys if k in self.__dict__}
+        self._hdr_arena, self._arena_off, self._arena_used, self.step_arena = holder["arena"], 0, 0, True
+        try:
+            yield holder["arena"]
+        finally:
+            holder["used"] = max(holder["used"], self._arena_used)
+            for k in keys:
+                self.__dict__.pop(k, None)
+            self.__dict__.update(saved)
 
     def hdr_rows(self, n: int) -> torch.Tensor:
         dev = self.flat.device

@@ -105,6 +105,13 @@ def cmd_arg(c, name, param):
     return getattr(c.a[k], _member(SIGNATURES[name][k]))
 
 
+def cmd_set_arg(c, name, param, value):
+    """Rewrites parameter ``param`` (its name in the header) of the recorded command ``c`` of the entry point ``name``: the slots of
+    a replayed command that change from replay to replay, found by name -- never by matching addresses."""
+    k = PARAMS[name].index(param)
+    setattr(c.a[k], _member(SIGNATURES[name][k]), value)
+
+
 _op_ids = None
 
 
@@ -1076,6 +1083,38 @@ def rank_leave(x, gt, perm=None, masked=False, seq_valid=None):
     _check(lib().segmm_rank_leave(_ptr(x), x.stride(0), _ptr(gt), _ptr(perm), B, S, int(bool(masked)),
                                   S if seq_valid is None else int(seq_valid), _ptr(ranks), _ptr(hist), _stream()), "segmm_rank_leave")
     return ranks, hist
+
+
+SEED_MASK = (1 << 63) - 1          # the seed bits below LIVE_SEED
+
+
+def valid_rows(logits, exposure, gt, ranks=None, masked=False, seq_valid=None, permute=False, seed=0, site=0, row0=0,
+               interests=None, perm_out=None):
+    """The tail of a validation batch in one launch (segmm_valid_rows in include/segmm_hip.h): ranks int32 [B] of the leave segment
+    under interests = sigmoid(logits) * exposure, the candidates shuffled (``permute``) by a permutation drawn in the kernel for
+    (seed, site, row0 + b).  ``ranks`` (written in place: a slice of a pass's table) or a fresh tensor is returned; ``interests``
+    float32 [B, S] / ``perm_out`` int32 [B, S]: optional outputs (tests)."""
+    _dev(logits, exposure, gt)
+    if gt.dim() != 2 or gt.dtype != torch.int64 or not gt.is_contiguous():
+        raise RuntimeError("valid_rows: gt must be a contiguous int64 [B, S] tensor")
+    B, S = gt.shape
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.shape != gt.shape or (S > 1 and logits.stride(1) != 1):
+        raise RuntimeError("valid_rows: logits must be float32 [B, S] with unit inner stride")
+    if exposure is not None and (exposure.dtype != torch.float32 or not exposure.is_contiguous() or exposure.numel() < S):
+        raise RuntimeError("valid_rows: exposure must be a contiguous float32 tensor of at least S elements")
+    if ranks is None:
+        ranks = torch.empty(B, dtype=torch.int32, device=gt.device)
+    if ranks.dtype != torch.int32 or not ranks.is_contiguous() or ranks.numel() != B:
+        raise RuntimeError("valid_rows: ranks must be a contiguous int32 [B] tensor")
+    for t, dt, nm in ((interests, torch.float32, "interests"), (perm_out, torch.int32, "perm_out")):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.shape != gt.shape):
+            raise RuntimeError("valid_rows: %s must be a contiguous %s [B, S] tensor" % (nm, str(dt).replace("torch.", "")))
+    if B == 0:          # (an empty tensor has no address to pass)
+        return ranks
+    _check(lib().segmm_valid_rows(_ptr(logits), logits.stride(0) if B > 1 else max(logits.stride(0), S), _ptr(exposure), _ptr(gt), B, S,
+                                  int(bool(masked)), S if seq_valid is None else int(seq_valid), int(bool(permute)), int(seed) & SEED_MASK,
+                                  int(site), int(row0), _ptr(ranks), _ptr(interests), _ptr(perm_out), _stream()), "segmm_valid_rows")
+    return ranks
 
 
 def auc_counts(score, label, seg_off):

@@ -12,6 +12,8 @@ Device path: when the interests / labels are HIP tensors, t
 three counters come back), instead of moving [B, S] interests, labels and masks to the host like the reference.
 The per-row metrics of the test phase (the row loop at the end of ``main_eval_batch``) have a device form too, opt-in through
 ``Trainer.test_model(device_metrics=True)``: ``row_metrics_device`` / ``RowMetricAccumulator`` / ``seen_table``.
+A validation pass can keep its results on the device until its end (``Trainer.valid_model(recorded=True)``): ``ValidationAccumulator``
+owns the pass's rank and loss-scalar tables and turns them into the metrics dict with one read-back.
 """
 from __future__ import annotations
 
@@ -224,6 +226,61 @@ class RowMetricAccumulator:
         n = s["n"]
         return {"LeaveMAE": self._mean(s["abs_err"], n), "TOP1MSE": self._mean(s["top1_sq_err"], n), "TOP1MAE": self._mean(s["top1_abs_err"], n),
                 "view_complete": int(s["n_complete"]), "rows": int(n)}
+
+
+class ValidationAccumulator:
+    """The device-resident results of one validation pass (``Trainer.valid_enqueue`` / ``valid_model(recorded=True)``):
+    ``ranks`` int32 [total_rows] -- batch i's leave ranks at ``offsets[i]`` (segmm_valid_rows writes them there) -- and ``scalars``
+    float32 [n_batches, 13]: the 12 loss slots of the head's loss kernel plus the total (two segmm_copy_bytes per batch).  Nothing
+    is read back per batch.  ``finish()`` copies both tables to the host once (the pass's only synchronisation) and computes, per
+    batch, ``_evaluations(r[r > 0])`` and sum / len over the batches with the arithmetic of the eager ``valid_model``: the same
+    ranks and losses in give the same floats out, bit for bit (without its per-batch print of the metrics).
+    ``loss_slots``: metric name -> column of ``scalars`` (the keys of the model's output dict; "loss" -> 12), set by the pass.
+    ``logits``: with ``keep_logits`` the pass appends a copy of every batch's logits (a debugging hook; tests)."""
+    N_SCALARS = 13
+    TOTAL = 12
+
+    def __init__(self, batch_rows, device, metrics, keep_logits=False):
+        self.batch_rows = [int(b) for b in batch_rows]
+        self.offsets = [0]
+        for b in self.batch_rows:
+            self.offsets.append(self.offsets[-1] + b)
+        self.metrics = tuple(metrics)
+        self.ranks = torch.zeros(max(self.offsets[-1], 1), dtype=torch.int32, device=device)
+        self.scalars = torch.zeros((max(len(self.batch_rows), 1), self.N_SCALARS), dtype=torch.float32, device=device)
+        self.loss_slots = {}
+        self.logits = [] if keep_logits else None
+
+    def rank_slice(self, i):
+        return self.ranks[self.offsets[i]:self.offsets[i + 1]]
+
+    def add_scalars(self, i, losses, total):
+        """Enqueue the copies of batch i's loss scalars (``losses`` float32 [12], ``total`` 0-dim) into row i; no synchronisation."""
+        from . import hipabi as H
+        H.copy_bytes(self.scalars[i, :self.TOTAL], losses)
+        H.copy_bytes(self.scalars[i, self.TOTAL:], total.view(1))
+
+    def finish(self):
+        """One synchronising read-back of both tables -> the dict ``valid_model`` returns."""
+        ranks = self.ranks.cpu().numpy()
+        scalars = self.scalars.cpu().numpy()
+        return self.finalize(ranks, scalars, self.offsets, self.metrics, self.loss_slots)
+
+    @staticmethod
+    def finalize(ranks, scalars, offsets, metrics, loss_slots):
+        """Host finalisation on the tables' host copies (``ranks`` int [total_rows], ``scalars`` float32 [n_batches, 13])."""
+        acc = {k: [] for k in metrics}
+        for i in range(len(offsets) - 1):
+            r = np.asarray(ranks[offsets[i]:offsets[i + 1]]).astype(np.int64)
+            ev = _evaluations(r[r > 0], verbose=False)
+            for k in acc:
+                if k == "valid_loss":
+                    acc[k].append(float(scalars[i, ValidationAccumulator.TOTAL]))
+                elif k in loss_slots:
+                    acc[k].append(float(scalars[i, loss_slots[k]]))
+                elif k in ev:
+                    acc[k].append(float(ev[k]))
+        return {k: (sum(v) / len(v) if v else float("nan")) for k, v in acc.items()}
 
 
 def auc_rank_sum(labels, scores):

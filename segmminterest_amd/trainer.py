@@ -717,6 +717,7 @@ class Trainer:
             if self.comm.rank:          # data-parallel ranks seed torch identically: every rank drops different elements of its rows
                 seed0 = (seed0 ^ (self.comm.rank * 0x9E3779B97F4A7C15)) & (2 ** 62 - 1)
             H.step_set(seed0, self.opt.step_count, *self.opt.betas)
+            self._seed0 = seed0          # (the host's copy: the seeds of the recorded validation passes are mixed from it)
             if self.opt.schedule is not None:
                 self.opt._install_schedule()
             st.live_seed = H.LIVE_SEED | 0x5E6D0001          # the (constant) seed argument of every dropout launch
@@ -1129,27 +1130,7 @@ class Trainer:
         model, st = self.model, self.model._store
         if self._param_hooks():
             raise RuntimeError("record(): parameter hooks only fire when the gradients travel through autograd; use train_step")
-        for k, v in batch.items():
-            if torch.is_tensor(v) and not v.is_contiguous():
-                raise RuntimeError("record(): batch[%r] is not contiguous" % k)
-            # the zero-copy paths of the step: anything else is converted by a torch kernel, which a replay would drop (the
-            # conversions also raise by themselves while recording: hipabi.torch_fallback)
-            # (16-bit features: only the two tensors that go through normalize(); the recorded commands carry their element size, and
-            # run_recorded() refuses a batch of another dtype)
-            if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32 and not (
-                    k in ("user", "photo") and v.dtype in (torch.float16, torch.bfloat16)):
-                raise RuntimeError("record(): batch[%r] is %s; the recorded step takes float32 features (batch['user'] / batch['photo']: "
-                                   "float32, float16 or bfloat16)" % (k, v.dtype))
-            if torch.is_tensor(v) and k.endswith("_mask") and v.dtype != torch.bool:
-                raise RuntimeError("record(): batch[%r] is %s; the recorded step takes bool masks" % (k, v.dtype))
-            if torch.is_tensor(v) and not v.is_floating_point() and v.dtype not in (torch.bool, torch.int64):
-                raise RuntimeError("record(): batch[%r] is %s; the recorded step takes int64 ids and labels" % (k, v.dtype))
-        # one feature dtype per recorded batch: a batch that carries 16-bit features carries both tensors so (a pipeline stores its
-        # features in one format); a half-precision tensor next to a float32 one is the stray conversion record() has always refused
-        fdt = {k: batch[k].dtype for k in ("user", "photo") if torch.is_tensor(batch.get(k)) and batch[k].is_floating_point()}
-        if len(set(fdt.values())) > 1:
-            raise RuntimeError("record(): batch['user'] is %s and batch['photo'] is %s; the recorded step takes both feature tensors in "
-                               "one dtype (float32, float16 or bfloat16)" % (fdt["user"], fdt["photo"]))
+        self._refuse_unrecordable(batch, "record()", "step")
         # the step may name tensors of the PREVIOUS step's batch (id mode: the rows the last backward scattered into the table
         # gradient are cleared by id list): the last warm-up step runs on a copy of the batch, so that such pointers can be told
         # from the current batch's and re-based to the previous batch at replay
@@ -1220,6 +1201,31 @@ class Trainer:
                               n_cmds=sum(ph.n_cmds for ph, a in phases if a is not None),
                               hyper=self._hyper())
         return out
+
+    @staticmethod
+    def _refuse_unrecordable(batch, who, what):
+        """What a replay would drop, refused by name (``who``: the caller in the message; ``what``: "step" / "validation batch")."""
+        for k, v in batch.items():
+            if torch.is_tensor(v) and not v.is_contiguous():
+                raise RuntimeError("%s: batch[%r] is not contiguous" % (who, k))
+            # the zero-copy paths of the step: anything else is converted by a torch kernel, which a replay would drop (the
+            # conversions also raise by themselves while recording: hipabi.torch_fallback)
+            # (16-bit features: only the two tensors that go through normalize(); the recorded commands carry their element size, and
+            # run_recorded() refuses a batch of another dtype)
+            if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32 and not (
+                    k in ("user", "photo") and v.dtype in (torch.float16, torch.bfloat16)):
+                raise RuntimeError("%s: batch[%r] is %s; the recorded %s takes float32 features (batch['user'] / batch['photo']: "
+                                   "float32, float16 or bfloat16)" % (who, k, v.dtype, what))
+            if torch.is_tensor(v) and k.endswith("_mask") and v.dtype != torch.bool:
+                raise RuntimeError("%s: batch[%r] is %s; the recorded %s takes bool masks" % (who, k, v.dtype, what))
+            if torch.is_tensor(v) and not v.is_floating_point() and v.dtype not in (torch.bool, torch.int64):
+                raise RuntimeError("%s: batch[%r] is %s; the recorded %s takes int64 ids and labels" % (who, k, v.dtype, what))
+        # one feature dtype per recorded batch: a batch that carries 16-bit features carries both tensors so (a pipeline stores its
+        # features in one format); a half-precision tensor next to a float32 one is the stray conversion record() has always refused
+        fdt = {k: batch[k].dtype for k in ("user", "photo") if torch.is_tensor(batch.get(k)) and batch[k].is_floating_point()}
+        if len(set(fdt.values())) > 1:
+            raise RuntimeError("%s: batch['user'] is %s and batch['photo'] is %s; the recorded %s takes both feature tensors in "
+                               "one dtype (float32, float16 or bfloat16)" % (who, fdt["user"], fdt["photo"], what))
 
     def _hyper(self):
         # under an lr_schedule the recorded commands carry the sentinel, not a rate: the rate may move, the schedule's presence not
@@ -1510,11 +1516,15 @@ class Trainer:
 
     @torch.no_grad()
     def valid_model(self, batches, metrics=("valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"),
-                    permutation=1, top_k_mask=False):
+                    permutation=1, top_k_mask=False, recorded=False, seed=None):
         """``valid_model`` of the reference trainer (main_for_seq_leave_earlystop_SegMM.py:132-186): eval-mode forward
         with ``mode="train"`` (loss + logits), interests = sigmoid(logits) * exposure_prob, leave-rank metrics per batch,
         mean over batches.  The ranks are computed on the device (csrc/evalops.h); only B integers per batch reach the
-        host instead of the [B, S] interests, labels and masks."""
+        host instead of the [B, S] interests, labels and masks.
+        ``recorded=True`` (opt-in; single process): the pass never waits for the host between batches -- :meth:`valid_enqueue`
+        followed by ``finish()`` of the accumulator it returns; ``seed``: the seed of the pass's candidate shuffles (see there)."""
+        if recorded:
+            return self.valid_enqueue(batches, metrics=metrics, permutation=permutation, top_k_mask=top_k_mask, seed=seed).finish()
         from .my_evaluation import TOP_K_leave_device
         model = self.model
         exposure = None
@@ -1538,6 +1548,179 @@ class Trainer:
                 elif k in ev:
                     acc[k].append(float(ev[k]))
         return {k: (sum(v) / len(v) if v else float("nan")) for k, v in acc.items()}
+
+    # ---- a validation pass that never waits for the host between batches (recorded eval forward + device tail)
+    @staticmethod
+    def _shapes_of(batch):
+        return {k: (tuple(v.shape), v.dtype) for k, v in batch.items() if torch.is_tensor(v) and v.numel()}
+
+    def _valid_seed(self, ordinal):
+        """The seed of the candidate shuffles of the ``ordinal``-th recorded validation pass of this trainer: a splitmix64 mix of the
+        model seed -- the seed word the device step state was initialised with (``device_state``), else ``torch.initial_seed()`` --
+        and the pass ordinal.  Nothing is drawn from torch's generator."""
+        base = self.__dict__.get("_seed0")
+        if base is None:
+            base = torch.initial_seed()
+        m = (1 << 64) - 1
+        z = (int(base) + 0x9E3779B97F4A7C15 * (int(ordinal) + 1)) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return (z ^ (z >> 31)) & H.SEED_MASK
+
+    def _valid_exposure(self, S, dev):
+        """(key, tensor) of exposure_prob[:S] on the device, made once per value."""
+        key = (tuple(float(x) for x in list(self.model.exposure_prob)[:S]), str(dev))
+        c = self.__dict__.setdefault("_valid_expo", {})
+        if key not in c:
+            if len(key[0]) < S:
+                raise RuntimeError("exposure_prob has %d entries, S=%d" % (len(key[0]), S))
+            c[key] = torch.tensor(key[0], dtype=torch.float32, device=dev)
+        return key, c[key]
+
+    def _valid_tail(self, out, acc, i, cfg, seed):
+        """The device tail of validation batch ``i``: ranks of its rows (segmm_valid_rows) at the batch's row offset of the pass's
+        table, its loss scalars into the batch's row (two segmm_copy_bytes).  No synchronisation."""
+        logits = out["logits"]
+        H.mark(H.PHASE_STEP_TAIL)
+        H.valid_rows(logits, self._valid_exposure(logits.shape[1], logits.device)[1], out["gt"], ranks=acc.rank_slice(i), masked=cfg[1],
+                     permute=cfg[0], seed=seed, site=E.SITE_VALID_PERM, row0=acc.offsets[i])
+        acc.add_scalars(i, self.model.__dict__["_losses_vec"], out["loss"])
+
+    @torch.no_grad()
+    def valid_enqueue(self, batches, metrics=("valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"),
+                      permutation=1, top_k_mask=False, seed=None, keep_logits=False):
+        """The enqueue part of ``valid_model(recorded=True)``: every batch of the pass is put on the stream without one host
+        synchronisation (the pass that records excepted) and a :class:`my_evaluation.ValidationAccumulator` is returned, whose
+        ``finish()`` does the pass's single read-back and gives the dict ``valid_model`` returns.
+
+        Per batch the eval-mode forward with ``mode="train"`` is followed by a device tail: ONE segmm_valid_rows launch (interests =
+        sigmoid(logits) * exposure, the candidate shuffles, the leave ranks, written at the batch's row offset of the pass's rank
+        table) and two segmm_copy_bytes (the 12 loss slots and the total into the batch's row of the scalar table).
+        The FIRST batch of the first such pass runs launch by launch while it is recorded (``H.Recorder``, a private memory pool, the
+        batch's tensors re-based per replay, as :meth:`record` does for the training step); every later batch of that shape, in this
+        and in later passes, is replayed with one C call per phase.  A batch of any other shape (the short last batch) takes the
+        eager launches with the same device tail: still no synchronisation, just not replayed -- one shape is recorded.
+        * Site headers: the recorded batch draws its header rows from an arena of its own (``ParamStore.hdr_private_arena``), cleared
+          by a fill command at the head of the replay; the training step's arena and the wrapping ring of the eager passes are not
+          touched.  The recording also has its own memory pool and events, and shares the trainer's three streams: it coexists with
+          a recorded training step.
+        * Weight planes: the split runs EAGERLY ahead of each pass (``ParamStore.ensure`` at its head re-splits iff the weights moved
+          since the last split); the recording carries no split, a replay reads the planes of the moment.
+        * Per replay the named slots that change are rewritten (``hipabi.cmd_set_arg``, by op and parameter name): ``ranks``, ``row0``
+          and ``seed`` of segmm_valid_rows, ``dst`` of the two copies.
+        * ``permutation``: the shuffles are drawn in the kernel, keyed by (seed, site, row index in the pass): the reference's
+          distribution, not numpy's bit stream.  ``seed``: None = :meth:`_valid_seed` of this trainer's pass counter (a new draw
+          per pass, reproducible under torch.manual_seed); an int = that seed (bits 0 .. 62).
+        Refused by name: data parallelism (``comm.active``: the per-batch rank gather and loss all-reduce need a design of their
+        own), non-contiguous batch tensors, stray dtypes, any ``hipabi.torch_fallback`` while recording.  ``keep_logits``: the
+        accumulator also keeps a copy of every batch's logits (debugging hook)."""
+        from .decoder_leave_focal import _LIDX
+        from .my_evaluation import ValidationAccumulator
+        if self.comm.active:
+            raise RuntimeError("valid_model(recorded=True) is not supported under data parallelism (an active DPComm): the per-batch "
+                               "rank gather and loss all-reduce are host-driven collectives; use recorded=False")
+        batches = list(batches)
+        for b in batches:
+            self._refuse_unrecordable(b, "valid_model(recorded=True)", "validation batch")
+        model, st = self.model, self.model._store
+        ordinal = self.__dict__.get("_valid_passes", 0)
+        self._valid_passes = ordinal + 1
+        seed = (self._valid_seed(ordinal) if seed is None else int(seed)) & H.SEED_MASK
+        model.eval()
+        acc = ValidationAccumulator([b["label"].shape[0] for b in batches], next(model.parameters()).device, metrics, keep_logits=keep_logits)
+        if not batches:
+            return acc
+        st.ensure()          # the weights of the moment: their planes are split here, ahead of the pass's first replay
+        self._pf = None      # (like eval_step: a prefetched input stage is dropped)
+        for i, batch in enumerate(batches):
+            S = batch["label"].shape[1]
+            cfg = (bool(permutation), bool(top_k_mask), self._valid_exposure(S, st.flat.device)[0])
+            r = self.__dict__.get("_valid_rec")
+            if r is None:
+                out = self._valid_record(batch, acc, i, cfg, seed)
+            elif r["cfg"] == cfg and self._shapes_of(batch) == r["spans"]:
+                out = self._valid_replay(r, batch, acc, i, seed)
+            else:
+                out = self.eval_step(batch, mode="train")
+                self._valid_tail(out, acc, i, cfg, seed)
+            if not acc.loss_slots:
+                acc.loss_slots = dict({k: _LIDX[k] for k in out if k in _LIDX}, loss=acc.TOTAL)
+            if acc.logits is not None:
+                acc.logits.append(out["logits"].clone())
+        return acc
+
+    def _valid_record(self, batch, acc, i, cfg, seed):
+        """Runs validation batch ``i`` launch by launch while recording it (see :meth:`valid_enqueue`) -> its output dict."""
+        model, st = self.model, self.model._store
+        side, aux = st.side_stream(), st.aux_stream()          # both exist before the recorder maps their handles to slots
+        hold = self.__dict__.setdefault("_valid_hdr", {})
+        torch.cuda.synchronize()
+        main = H._stream()
+        pool = torch.cuda.MemPool()
+        rec = H.Recorder(main, side.cuda_stream, aux.cuda_stream)
+        H.RECORDER = rec
+        try:
+            with st.rec_pool(pool), st.hdr_private_arena(hold) as arena:
+                H.mark(H.PHASE_STEP_BEGIN)
+                H.fill_zero(arena[:1])          # (the arena is clean now; the replays clear what this batch drew: size patched below)
+                out = self.eval_step(batch, mode="train")
+                self._valid_tail(out, acc, i, cfg, seed)
+        finally:
+            H.RECORDER = None
+        torch.cuda.synchronize()
+        phases = rec.finish()
+        ops = H.op_ids()
+        cmds = [(arr, ci) for ph, arr in phases if arr is not None for ci in range(ph.n_cmds)]
+        tail = [(ph, arr) for ph, arr in phases if arr is not None][-1]
+        named = {n: [tail[1][ci] for ci in range(tail[0].n_cmds) if tail[1][ci].op == ops[n]] for n in ("segmm_valid_rows", "segmm_copy_bytes")}
+        fill = cmds[0][0][cmds[0][1]]
+        if (fill.op != ops["segmm_fill_zero"] or tail[0].kind != H.PHASE_STEP_TAIL or len(named["segmm_valid_rows"]) != 1
+                or len(named["segmm_copy_bytes"]) != 2):
+            raise RuntimeError("valid_model(recorded=True): the recorded launch sequence does not have the expected head (header fill) "
+                               "and tail (segmm_valid_rows, two segmm_copy_bytes)")
+        H.cmd_set_arg(fill, "segmm_fill_zero", "bytes", hold["used"] * H.SITE_FLOATS * 4)
+        # the batch's tensors: every recorded POINTER argument that falls inside one of them is re-based per replay (see record())
+        spans = [(k, v.data_ptr(), v.numel() * v.element_size()) for k, v in batch.items() if torch.is_tensor(v) and v.numel()]
+        relocs = []
+        for pi, (ph, arr) in enumerate(phases):
+            if arr is None:
+                continue
+            for ci, ai in rec.pslots[pi]:
+                pv = arr[ci].a[ai].p
+                for k, base, nb in spans:
+                    if base <= pv < base + nb:
+                        relocs.append((arr, ci, ai, k, pv - base))
+                        break
+        evs = tuple(torch.cuda.Event() for _ in range(4))
+        for e in evs:
+            e.record()
+        self._valid_rec = dict(phases=phases, keep=rec.keep, pool=pool, out=out, relocs=relocs, spans=self._shapes_of(batch), cfg=cfg, main=main,
+                               events=evs, table=H.stream_table([main, side.cuda_stream, aux.cuda_stream], [e.cuda_event for e in evs]),
+                               valid_rows=named["segmm_valid_rows"][0], copies=named["segmm_copy_bytes"], losses=model.__dict__["_losses_vec"],
+                               n_cmds=len(cmds), n_replays=0)
+        return out
+
+    def _valid_replay(self, r, batch, acc, i, seed):
+        """Enqueues validation batch ``i`` from the recorded launch sequence: the batch's addresses and the per-batch slots of the
+        tail are patched, then one C call per phase.  Returns the recording's output dict (rewritten by every replay)."""
+        if H._stream() != r["main"]:
+            raise RuntimeError("valid_model(recorded=True): the current stream is not the stream the validation batch was recorded on")
+        for arr, ci, ai, k, off in r["relocs"]:
+            arr[ci].a[ai].p = batch[k].data_ptr() + off
+        vr = r["valid_rows"]
+        H.cmd_set_arg(vr, "segmm_valid_rows", "ranks", acc.rank_slice(i).data_ptr())
+        H.cmd_set_arg(vr, "segmm_valid_rows", "row0", acc.offsets[i])
+        H.cmd_set_arg(vr, "segmm_valid_rows", "seed", seed)
+        dst = acc.scalars[i].data_ptr()
+        H.cmd_set_arg(r["copies"][0], "segmm_copy_bytes", "dst", dst)
+        H.cmd_set_arg(r["copies"][1], "segmm_copy_bytes", "dst", dst + 4 * acc.TOTAL)
+        for ph, arr in r["phases"]:
+            if arr is None:
+                ph()
+            else:
+                H.run_phase(ph, r["table"])
+        r["n_replays"] += 1
+        return r["out"]
 
 
 def early_stop_reached(metric_history: List[float], early_stop: int) -> bool:
@@ -1573,7 +1756,7 @@ def compute_final_result(results_list):
 def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_step: int = 30, early_stop: int = 0,
         main_metric: str = "NDCG@5", ckpt: Optional["CheckPointer"] = None, logging_step: int = 0, log=None,
         permutation: int = 1, top_k_mask: bool = False, metrics=None, recorded: bool = False, eager_steps: int = 3,
-        lr_plateau: Optional[dict] = None):
+        lr_plateau: Optional[dict] = None, recorded_valid: bool = False):
     """The train / validate / checkpoint / early-stop loop of the reference trainer around ``Trainer.train_step``
     (main_for_seq_leave_earlystop_SegMM.py:247-354): one validation over ``valid_batches`` BEFORE training, then per epoch every
     ``valid_step`` local steps a validation whose ``main_metric`` (mean over the validation batches, :179-181) drives
@@ -1589,6 +1772,9 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
     "max", the sense of the early-stop tests): reduce-on-plateau with torch.optim.lr_scheduler.ReduceLROnPlateau's rules, fed after
     every validation of the loop the number early stopping reads -- every data-parallel rank decides alike -- and acting through
     ``opt.set_base_lr``, so it needs ``Trainer(lr_schedule=...)`` ("constant" suffices) and works under ``recorded=True``.
+    ``recorded_valid=True`` (independent of ``recorded``; single process): every validation of the loop goes through
+    ``Trainer.valid_model(recorded=True)`` -- no host round trip between its batches, one read-back per validation; with
+    ``permutation=0`` the history equals the eager validations' exactly, with ``permutation=1`` the shuffles come from the device.
     Returns the history dict the reference calls ``total_valid_loss_metrics`` (+ "stopped_epoch", "global_step")."""
     metrics = list(metrics) if metrics is not None else ["valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"]
     hist: Dict[str, list] = {"train_loss": [0.0]}
@@ -1596,7 +1782,8 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
         hist[k] = []
 
     def validate():
-        vm = trainer.valid_model(valid_batches, metrics=tuple(metrics), permutation=permutation, top_k_mask=top_k_mask)
+        vm = trainer.valid_model(valid_batches, metrics=tuple(metrics), permutation=permutation, top_k_mask=top_k_mask,
+                                 **({"recorded": True} if recorded_valid else {}))
         for k in metrics:
             hist[k].append(vm[k])
         return vm
