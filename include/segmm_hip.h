@@ -688,6 +688,12 @@ int segmm_copy_bytes(void* dst, const void* src, int64_t bytes, segmm_stream_t s
 /* test hook: multiplier (0 or 1/(1-p)) of elements [0,n) of a dropout site */
 int segmm_dropout_mult(float* out, int64_t n, float p, uint64_t seed, uint32_t site, segmm_stream_t stream);
 
+/* out[i] = a[i] + b[i] (one IEEE fp32 add, nothing contracted), i < n; n >= 0; out may be exactly a or exactly b; any other overlap
+ * of out with an operand is refused (nothing is written).  The gradient sum of a micro-batched step (Trainer(micro_batch=m)): 16-byte
+ * accesses where the three pointers share their offset from a 16-byte boundary (scalar head and tail), one dword per lane otherwise;
+ * pointers need 4-byte alignment only.  Added under ABI version 30: nothing that existed changed. */
+int segmm_vec_add(float* out, const float* a, const float* b, int64_t n, segmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2085,6 +2085,35 @@ int segmm_copy_bytes(void* dst, const void* src, int64_t bytes, segmm_stream_t s
     return 0;
 }
 
+int segmm_vec_add(float* out, const float* a, const float* b, int64_t n, segmm_stream_t stream) {
+    SEGMM_REQUIRE(out && a && b, "vec_add: null pointer");
+    SEGMM_REQUIRE(((((uintptr_t)out) | ((uintptr_t)a) | ((uintptr_t)b)) & 3u) == 0, "vec_add: pointers must be 4-byte aligned");
+    SEGMM_REQUIRE(n >= 0, "vec_add: n=%lld", (long long)n);
+    SEGMM_REQUIRE(n <= (int64_t)1 << 40, "vec_add: n=%lld (<= 2^40)", (long long)n);
+    // out is exactly an operand or shares no byte with it: a lane adds only the elements it then writes
+    const uintptr_t nb = (uintptr_t)n * 4u, po = (uintptr_t)out, pa = (uintptr_t)a, pb = (uintptr_t)b;
+    SEGMM_REQUIRE(po == pa || po + nb <= pa || pa + nb <= po, "vec_add: out overlaps a partially (out must be exactly a, exactly b, or disjoint)");
+    SEGMM_REQUIRE(po == pb || po + nb <= pb || pb + nb <= po, "vec_add: out overlaps b partially (out must be exactly a, exactly b, or disjoint)");
+    if (n == 0) return 0;
+    const long long cap = (long long)num_cus() * VEC_ADD_WG_PER_CU;          // one round of resident workgroups
+    const unsigned oo = (unsigned)((po >> 2) & 3u);
+    if (oo == ((pa >> 2) & 3u) && oo == ((pb >> 2) & 3u)) {
+        const int to16 = (int)((4u - oo) & 3u);          // floats before the first 16-byte boundary
+        const int lead = n < to16 ? (int)n : to16;
+        const long long n4 = (n - lead) >> 2;
+        const int tail = (int)((n - lead) & 3);
+        long long blocks = (n4 + 255) / 256;
+        blocks = blocks > cap ? cap : blocks < 1 ? 1 : blocks;
+        hipLaunchKernelGGL(vec_add_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, a, b, lead, n4, tail);
+    } else {
+        long long blocks = (n + 255) / 256;
+        blocks = blocks > cap ? cap : blocks;
+        hipLaunchKernelGGL(vec_add_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, a, b, 0, (long long)n, 0);
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
 #include "cmd_dispatch.inc"
 
 int segmm_cmd_op_count(void) { return SEGMM_N_CMD_OPS; }

@@ -830,6 +830,52 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
     }
 }
 
+// ---------------------------------------------------------------- out = a + b over a flat range (segmm_vec_add)
+// The gradient sum of a micro-batched step (Trainer(micro_batch=m)): one IEEE fp32 add per element, nothing to contract.  12 bytes of
+// traffic per element and no arithmetic worth the name, so the kernel is its loads: one round of resident workgroups (eight of 256
+// threads per CU, <= 64 registers) walks the range.  A lane with four or more grid-stride steps left issues four 16-byte loads of each
+// operand before its first add; what is left after that goes one vector per iteration (load, load, add, store: `out` may alias an
+// operand, so the compiler keeps the next loads behind the store).  With 8 CUs' worth of workgroups the stride is 2048 x CUs lanes: at the
+// config-2 model's 1.65 M vectors on 256 CUs only the lanes below n4 - 3 stride (about one in seven) take the unrolled loop, the others
+// three single iterations -- there the 32 resident waves per CU are what covers the load latency (profiles/micro_batch/vec_add_bench.txt);
+// from 4 x that size on every lane unrolls.
+// `out` may be exactly `a` or exactly `b` (no __restrict__): a lane reads the elements it owns before it writes them and owns them alone.
+// VEC: the three pointers share their offset from a 16-byte boundary -- `lead` (< 4) scalar elements, n4 whole vectors, `tail` (< 4)
+// scalar elements, the scalars by workgroup 0.  Otherwise (the pointers disagree mod 16 bytes; no caller in the step) one dword per
+// lane: coalesced, and no unaligned vector access.
+constexpr int VEC_ADD_WG_PER_CU = 8;
+template <bool VEC>
+__global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void vec_add_kernel(float* out, const float* a, const float* b, int lead, long long n4, int tail) {
+#pragma clang fp contract(off)
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if constexpr (VEC) {
+        f32x4* o4 = (f32x4*)(out + lead);
+        const f32x4 *a4 = (const f32x4*)(a + lead), *b4 = (const f32x4*)(b + lead);
+        for (; i + 3 * stride < n4; i += 4 * stride) {
+            const f32x4 a0 = a4[i], a1 = a4[i + stride], a2 = a4[i + 2 * stride], a3 = a4[i + 3 * stride];
+            const f32x4 b0 = b4[i], b1 = b4[i + stride], b2 = b4[i + 2 * stride], b3 = b4[i + 3 * stride];
+            o4[i] = a0 + b0; o4[i + stride] = a1 + b1; o4[i + 2 * stride] = a2 + b2; o4[i + 3 * stride] = a3 + b3;
+        }
+        for (; i < n4; i += stride) o4[i] = a4[i] + b4[i];
+        if (blockIdx.x == 0) {
+            const int t = threadIdx.x;
+            if (t < lead) out[t] = a[t] + b[t];
+            if (t < tail) {
+                const long long k = lead + (n4 << 2) + t;
+                out[k] = a[k] + b[k];
+            }
+        }
+    } else {          // n4 counts single elements here
+        for (; i + 3 * stride < n4; i += 4 * stride) {
+            const float a0 = a[i], a1 = a[i + stride], a2 = a[i + 2 * stride], a3 = a[i + 3 * stride];
+            const float b0 = b[i], b1 = b[i + stride], b2 = b[i + 2 * stride], b3 = b[i + 3 * stride];
+            out[i] = a0 + b0; out[i + stride] = a1 + b1; out[i + 2 * stride] = a2 + b2; out[i + 3 * stride] = a3 + b3;
+        }
+        for (; i < n4; i += stride) out[i] = a[i] + b[i];
+    }
+}
+
 // ---------------------------------------------------------------- CrossMLP ablation: AdaptiveAvgPool1d over tokens
 // out[b, i, :] = mean over t in [floor(i T / bins), ceil((i+1) T / bins)) of cat(U[b], V[b])[t, :], T = Lu + Lv
 // (encoder.py:396,503-506: nn.AdaptiveAvgPool1d(40) over the token axis of the concatenated user and video tokens;

@@ -1108,7 +1108,7 @@ class BackboneRun:
                 # generator exactly like the reference (encoder.py:428-429: B x torch.randperm(Lv)) -- or, when the step's state
                 # lives on the device (Trainer(device_state=True): the step may be recorded), drawn on the device: the same
                 # distribution (a uniformly random permutation per row), another bit stream
-                live = st.__dict__.get("live_seed")
+                live = live_seed(st)
                 if live is not None and train and S <= 256:
                     fpos = st.buf("nopos_fpos%d" % self.bi, (B, S))
                     H.rand_perm_rows(fpos, B, S, live, SITE_NOPOS + 16 * self.bi)
@@ -1667,11 +1667,15 @@ class BackboneRun:
             width = d // 2 if side == "vid" else d
             # the dense table gradient (360 MB at config 3) is zero except for the rows the PREVIOUS step scattered into it
             # (AdamW reads it, nobody else writes it): clear those rows instead of filling the whole table again
-            prev = st._tab_rows.get(P + side)
-            if gbuf is None and prev is not None and prev[0] == gtab.data_ptr() and prev[1].device == gtab.device:
-                H.zero_rows(gtab, prev[1])
-            else:
-                H.fill_zero(gtab)
+            # A micro-batched step (Trainer(micro_batch=m); ``st.micro_pass`` = (pass index, the WHOLE batch's id tensor per side)):
+            # the passes of one step accumulate into the table gradient, so only pass 0 clears -- what the previous STEP left
+            mp = st.__dict__.get("micro_pass")
+            if mp is None or mp[0] == 0:
+                prev = st._tab_rows.get(P + side)
+                if gbuf is None and prev is not None and prev[0] == gtab.data_ptr() and prev[1].device == gtab.device:
+                    H.zero_rows(gtab, prev[1])
+                else:
+                    H.fill_zero(gtab)
             st._tab_rows.pop(P + side, None)
             if st.row_exchange is not None:
                 # Data parallel: a rank touches at most B rows of the table, so the ranks exchange
@@ -1708,7 +1712,14 @@ class BackboneRun:
                 H.embed_id_bwd(dpre, L, d, 0, width, order, ids, gtab, B)
                 touched = ids
             # (a dense all-reduce of the table under data parallelism adds the OTHER ranks' rows: no row list then)
-            if gbuf is None and (st.bucket_hook is None or st.row_exchange is not None):
+            if mp is not None:
+                # every pass of the step leaves the row list of the whole step: the batch's FULL id tensor (Trainer.record matches it
+                # by its base address).  Data parallel, or ids the trainer cannot name (the noUser draws): no list, the next step
+                # clears the table densely
+                full = mp[1].get(side) if st.bucket_hook is None else None
+                if gbuf is None and full is not None:
+                    st._tab_rows[P + side] = (gtab.data_ptr(), full.reshape(-1))
+            elif gbuf is None and (st.bucket_hook is None or st.row_exchange is not None):
                 st._tab_rows[P + side] = (gtab.data_ptr(), touched.reshape(-1))          # (zero_rows skips ids outside the table)
         else:
             x = sv["%s_x" % side]
@@ -1751,13 +1762,25 @@ def _group_view(store, first_name, numel, gbuf):
 _STEP_SEED = [0x5E6D0001]
 
 
+def live_seed(store=None):
+    """The constant seed argument of a device-state step's random launches (None without a device step state).  In pass j > 0 of a
+    micro-batched step (``store.micro_pass``) j is mixed into the bits below bit 63: the passes of one step share the device's seed
+    words, so without the mix they would all drop the same elements; the mix is a per-pass constant, which a recording carries by
+    value."""
+    live = None if store is None else store.__dict__.get("live_seed")
+    mp = None if store is None else store.__dict__.get("micro_pass")
+    if live is None or mp is None or mp[0] == 0:
+        return live
+    return live ^ ((mp[0] * 0x9E3779B97F4A7C15) & H.SEED_MASK)
+
+
 def next_seed(store=None) -> int:
     """A fresh dropout seed per training forward, drawn from torch's CPU generator so that
     ``torch.manual_seed`` makes train-mode runs reproducible.  Data-parallel ranks seed torch identically (identical
     replicas), so the rank is mixed in: every rank drops different elements of its own rows.
     With a device-side step state the ARGUMENT is the same every step (bit 63 set: the kernels XOR in the seed words that
     segmm_step_advance derives on the device), so that a recorded step can be replayed."""
-    live = None if store is None else store.__dict__.get("live_seed")          # set by Trainer(device_state=True)
+    live = live_seed(store)          # set by Trainer(device_state=True)
     if live is not None:
         return live
     s = int(torch.randint(0, 2 ** 62, (1,)).item())

@@ -280,6 +280,21 @@ def copy_bytes(dst: torch.Tensor, src: torch.Tensor):
         _check(lib().segmm_copy_bytes(dst.data_ptr(), src.data_ptr(), nb, _stream()), "segmm_copy_bytes")
 
 
+def vec_add(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor, n=None, out_off=0, a_off=0, b_off=0):
+    """segmm_vec_add: ``out[out_off + i] = a[a_off + i] + b[b_off + i]`` for i < n (default: all of ``out``) over contiguous float32
+    tensors, offsets in floats like ``adamw``'s ``p_off``.  ``out`` may be exactly an operand; a partial overlap is refused by the
+    library.  A recordable, re-basable command."""
+    for t, name in ((out, "out"), (a, "a"), (b, "b")):
+        _f32c(t, "vec_add: " + name)
+    _dev(out, a, b)
+    n = out.numel() - out_off if n is None else int(n)
+    if n < 0 or min(out_off, a_off, b_off) < 0 or out_off + n > out.numel() or a_off + n > a.numel() or b_off + n > b.numel():
+        raise RuntimeError("vec_add: %d elements from offsets %d / %d / %d do not fit tensors of %d / %d / %d"
+                           % (n, out_off, a_off, b_off, out.numel(), a.numel(), b.numel()))
+    with _kprof("vec_add", 12 * n):
+        _check(lib().segmm_vec_add(out.data_ptr() + 4 * out_off, a.data_ptr() + 4 * a_off, b.data_ptr() + 4 * b_off, n, _stream()), "segmm_vec_add")
+
+
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError("%s failed (%d): %s" % (what, rc, _lib_real().segmm_last_error().decode()))

@@ -33,7 +33,7 @@ import torch.nn as nn
 from . import engine as E
 from . import hipabi as H
 from . import switches
-from .decoder_leave_focal import MultiScaleTemporalDetrLeaveFocal
+from .decoder_leave_focal import _LIDX, LossSpec, MultiScaleTemporalDetrLeaveFocal
 from .encoder import SegFormerX
 
 
@@ -653,6 +653,23 @@ def shard_rows(n_rows: int, world: int, rank: int):
     return start, start + base + (1 if rank < rem else 0)
 
 
+def batch_rows(batch) -> int:
+    """Row count of a batch dict: that of its labels, else of its first tensor."""
+    t = batch.get("label")
+    if not torch.is_tensor(t):
+        t = next(v for v in batch.values() if torch.is_tensor(v) and v.dim())
+    return int(t.shape[0])
+
+
+def micro_slices(batch, m: int):
+    """The micro-batches of ``batch`` for ``Trainer(micro_batch=m)``: ceil(B / m) dicts whose tensors are row slices -- VIEWS along
+    dim 0, contiguous where the batch's are -- of the batch's tensors of B rows, in row order, the last one possibly shorter;
+    everything else is passed along as it is."""
+    B = batch_rows(batch)
+    return [{k: (v[r0:r0 + m] if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v) for k, v in batch.items()}
+            for r0 in range(0, B, m)]
+
+
 # ------------------------------------------------------------------------------------------------ trainer
 class Trainer:
     """zero_grad -> L1-normalise -> forward -> backward (-> bucketed all-reduce) -> AdamW, i.e. the body of
@@ -663,8 +680,14 @@ class Trainer:
 
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
-                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None):
+                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None):
         self.model = model
+        # micro_batch=m: a batch of more than m rows is stepped in ceil(B / m) micro-batches with ONE optimizer step on the whole
+        # batch's gradient (train_step / _train_step_micro); None, or m >= the batch's rows: the plain step, launch for launch
+        if micro_batch is not None and (isinstance(micro_batch, bool) or not isinstance(micro_batch, int) or micro_batch < 1):
+            raise ValueError("micro_batch must be a positive int or None, not %r" % (micro_batch,))
+        self.micro_batch = micro_batch
+        self._micro_on = False
         if lr_schedule is not None and not device_state:
             raise ValueError("Trainer(lr_schedule=...) needs device_state=True: the rate of a step is evaluated in the device step state")
         # device_state: what changes from step to step (dropout seed words, AdamW's step count and bias corrections, the
@@ -723,6 +746,8 @@ class Trainer:
             st.live_seed = H.LIVE_SEED | 0x5E6D0001          # the (constant) seed argument of every dropout launch
 
     def _on_bucket(self, name, after_side=False):
+        if self._micro_on:          # a micro-batched step reduces the SUMMED gradient once, after its last pass (_train_step_micro)
+            return
         # a host action of the step: a recorded step (record / run_recorded) calls it again at the same point of the launch order
         H.host_action(functools.partial(self._on_bucket_now, name, after_side))
 
@@ -918,7 +943,8 @@ class Trainer:
             with E.aux_work(st):
                 early = self._features_compute(batch, hdr_rows=rows, only="photo") if both else None
                 gt = batch.get("label")
-                if (self.model._dp_hook is None and gt is not None and gt.dtype == torch.int64 and gt.is_contiguous() and gt.dim() == 2
+                # (a micro-batched step hands every pass the WHOLE batch's statistics: never those of the slice)
+                if (not self._micro_on and self.model._dp_hook is None and gt is not None and gt.dtype == torch.int64 and gt.is_contiguous() and gt.dim() == 2
                         and getattr(self.model, "_loss_spec", None) is not None):
                     self.model._stats_pre = self.model._label_stats(gt, gt.shape[0], gt.shape[1])
             st.ensure()          # first ParamStore.ensure() of the step: the full check, the weight planes of this step
@@ -988,7 +1014,11 @@ class Trainer:
 
     def train_step(self, batch: Dict[str, torch.Tensor], next_batch: Optional[Dict[str, torch.Tensor]] = None):
         """One optimisation step on ``batch``.  ``next_batch``: the batch of the FOLLOWING step, if known -- its input stage is
-        enqueued on a side stream right away (:meth:`prefetch`) and overlaps this step's backward."""
+        enqueued on a side stream right away (:meth:`prefetch`) and overlaps this step's backward.
+        ``Trainer(micro_batch=m)`` and a batch of more than m rows: the step runs in micro-batches (:meth:`_train_step_micro`; nothing
+        is prefetched then)."""
+        if self.micro_batch is not None and batch_rows(batch) > self.micro_batch:
+            return self._train_step_micro(batch, self.micro_batch)
         model, st = self.model, self.model._store
         if self.device_state:
             H.step_bind(self._step_state)          # (a host-side pointer: the launches below carry it in their arguments)
@@ -1004,7 +1034,9 @@ class Trainer:
             usr, um, vid, vm = self._features(batch)          # first ParamStore.ensure() of the step: the full check
             st._trusted = True
             self._tables_early(batch)
-            if next_batch is not None:
+            # (a next batch the micro-batched step will take in slices gets no prefetch: that step could not use a whole-batch input
+            # stage, whose buffers would be those of all its rows)
+            if next_batch is not None and not (self.micro_batch is not None and batch_rows(next_batch) > self.micro_batch):
                 self.prefetch(next_batch)
             out = self._train_step(batch, usr, um, vid, vm)
             r = self.__dict__.get("_recorded")
@@ -1017,13 +1049,160 @@ class Trainer:
             if self.device_state:
                 st.hdr_step_end()          # evaluation passes between steps draw their headers from the wrapping ring
 
+    # ---- one optimizer step over a batch taken in micro-batches (Trainer(micro_batch=m))
+    def _micro_ranges(self, st):
+        """[start, end) pieces of the live range OUTSIDE the id tables: what the flat gradient sum covers (the dense table
+        gradients accumulate in place -- segmm_embed_id_bwd adds -- and never go through it)."""
+        key = (st.flat.data_ptr(), st.n_live)
+        c = self.__dict__.get("_micro_rng")
+        if c is None or c[0] != key:
+            out, pos = [], 0
+            for ts, te in st.table_ranges():
+                if ts > pos:
+                    out.append((pos, min(ts, st.n_live)))
+                pos = max(pos, te)
+            if pos < st.n_live:
+                out.append((pos, st.n_live))
+            c = self._micro_rng = (key, out)
+        return c[1]
+
+    def _micro_accumulate(self, st, j, k):
+        """After pass j of k, both streams joined: acc <- g (pass 0), acc <- acc + g (the middle passes), g <- acc + g (the last):
+        the flat gradient buffer ends up holding the batch's gradient, summed in pass order -- the same bits every run."""
+        acc = self.__dict__.get("_micro_acc")
+        if acc is None or acc.numel() != st.n_live or acc.device != st.gflat.device:
+            acc = self._micro_acc = torch.empty(st.n_live, dtype=torch.float32, device=st.gflat.device)
+        g = st.gflat
+        for s, e in self._micro_ranges(st):
+            if j == 0:
+                H.copy_bytes(acc[s:e], g[s:e])
+            elif j < k - 1:
+                H.vec_add(acc, acc, g, e - s, s, s, s)
+            else:
+                H.vec_add(g, acc, g, e - s, s, s, s)
+
+    def _micro_reduce(self):
+        """Data parallel: ONE all-reduce of the dense live ranges of the summed gradient, waited for (a host action of the step)."""
+        self._reduce_dense(0, self.model._store.n_live)
+        self.comm.finish()
+
+    def _train_step_micro(self, batch, m):
+        """One optimizer step on ``batch`` (B > m rows) in k = ceil(B / m) micro-batches, row slices of the batch's own tensors.
+        The head of the step runs once (step state, header arena, the tables' first AdamW pass and the label statistics of the WHOLE
+        batch); every pass gets those statistics, so its loss terms and gradients are already divided by the batch's normalisers and
+        simply sum: the flat gradient outside the id tables through segmm_vec_add, the id tables in place.  Then one tail: (data
+        parallel: one all-reduce of the sum,) norm / clip and AdamW on the whole batch's gradient.  Activation memory is that of m
+        rows.  Dropout differs between the passes of a step (engine.live_seed).  Every pass draws its site headers from the step's
+        arena: with the device step state k x the headers of a pass must fit ParamStore.HDR_RING_ROWS = 8192, a larger k is refused.
+        Parameter hooks are refused: the gradients must stay in the flat buffer."""
+        model, st = self.model, self.model._store
+        if self._param_hooks():
+            raise RuntimeError("Trainer(micro_batch=%d) does not support parameter hooks: the micro-batches' gradients are summed in "
+                               "the flat gradient buffer, where autograd's hooks never see them" % m)
+        for key, v in batch.items():
+            if torch.is_tensor(v) and not v.is_contiguous():
+                raise RuntimeError("train_step(micro_batch=%d): batch[%r] is not contiguous" % (m, key))
+        slices = micro_slices(batch, m)
+        k = len(slices)
+        if self.device_state:
+            H.step_bind(self._step_state)
+        if model.training != bool(self.dropout):
+            model.train(self.dropout)
+        self.opt.zero_grad()
+        H.mark(H.PHASE_STEP_BEGIN)
+        if self.device_state:          # ONE count and one rate per optimizer step
+            H.step_advance(*self.opt.betas)
+            st.hdr_step_begin()
+        st._trusted = False
+        self._micro_on = True
+        try:
+            st.ensure()          # the full check and the weight planes of this step, once
+            st._trusted = True
+            if model._loss_spec is None:
+                model._loss_spec = LossSpec(model.model_cfg)
+            gt = E._as(batch["label"], torch.int64, "the labels")
+            stats = model._label_stats(gt, gt.shape[0], gt.shape[1])          # of the whole batch (data parallel: all-gathered, once)
+            if callable(stats):
+                stats = stats()
+            ids = {}
+            for side, key in (("vid", "photo_identity_id"), ("usr", "user_identity_id")):
+                t = batch.get(key)
+                if torch.is_tensor(t) and t.dtype == torch.int64 and not (side == "usr" and "noUser" in getattr(model.backbone1, "ablation_type", "ours")):
+                    ids[side] = t
+            dev = st.flat.device
+            sums = torch.empty(13, dtype=torch.float32, device=dev)          # the 12 loss slots, then the total
+            logits = None
+            hdr0 = st._arena_off if self.device_state else 0
+            for j, mb in enumerate(slices):
+                st.micro_pass = (j, ids)
+                model._stats_pre = stats
+                if j:
+                    self.opt.zero_grad()          # (host only: the pass writes the flat buffer again and re-delivers the views)
+                usr, um, vid, vm = self._features(mb)
+                if j == 0:
+                    self._tables_early(batch)          # the rows of the WHOLE batch are the ones left for the second pass
+                out = self._fwd_bwd(mb, usr, um, vid, vm)
+                if j == 0 and self.device_state:
+                    per = st._arena_off - hdr0
+                    if st._arena_off + (k - 1) * per > st.HDR_RING_ROWS:
+                        raise RuntimeError("Trainer(micro_batch=%d): %d micro-batches of %d site headers each do not fit the step's header "
+                                           "arena of %d rows; use a micro_batch of at least %d for this batch"
+                                           % (m, k, per, st.HDR_RING_ROWS, -(-batch_rows(batch) // max((st.HDR_RING_ROWS - hdr0) // max(per, 1), 1))))
+                self._micro_accumulate(st, j, k)
+                lv, lg = model._losses_vec, out["logits"]
+                if logits is None:
+                    logits = torch.empty((gt.shape[0],) + tuple(lg.shape[1:]), dtype=lg.dtype, device=dev)
+                    H.copy_bytes(sums[:12], lv)
+                    H.copy_bytes(sums[12:], out["loss"].detach().view(1))
+                else:
+                    H.vec_add(sums, sums, lv, 12)
+                    H.vec_add(sums, sums, out["loss"].detach().view(1), 1, 12, 12, 0)
+                H.copy_bytes(logits[j * m:j * m + lg.shape[0]], lg)
+                keys = list(out)
+                del out
+            if self.comm.active:
+                H.host_action(self._micro_reduce)
+            H.mark(H.PHASE_STEP_TAIL)
+            if self.opt.__dict__.get("_early"):
+                E.join_aux(st)          # the tables' first pass (aux stream) is complete before their listed rows are stepped
+            self.opt.step()
+            res = {}
+            for key in keys:
+                res[key] = logits if key == "logits" else batch["label"] if key == "gt" else sums[12] if key == "loss" else sums[_LIDX[key]]
+            r = self.__dict__.get("_recorded")
+            if r is not None and H.RECORDER is None:
+                r["prev_batch"] = batch
+            return res
+        except BaseException:
+            if self.device_state and self.opt.__dict__.get("_early") is None:
+                # the step failed after the device step count had advanced: put it back, with its bias corrections and rate (a
+                # queued table pass is undone, with the count, by the next step's _tables_early).  The seed words keep the failed
+                # step's advance: the steps that follow draw another dropout stream of the same distribution
+                try:
+                    seed, _, _ = H.step_get()
+                    H.step_set(seed, self.opt.step_count, *self.opt.betas)
+                except RuntimeError:          # (the device itself failed: the first error is the one to report)
+                    pass
+            raise
+        finally:
+            self._micro_on = False
+            st._trusted = False
+            st.__dict__.pop("micro_pass", None)
+            model.__dict__.pop("_stats_pre", None)
+            if self.device_state:
+                st.hdr_step_end()
+
     def _train_step(self, batch, usr, um, vid, vm):
+        return self._finish_step(self._fwd_bwd(batch, usr, um, vid, vm))
+
+    def _fwd_bwd(self, batch, usr, um, vid, vm):
+        """Forward and backward of one pass: the whole batch of a plain step, one micro-batch of a micro-batched one."""
         model, st = self.model, self.model._store
         usr_id = batch["user_identity_id"]
         if "noUser" in getattr(model.backbone1, "ablation_type", "ours"):
             # 'noUser' / 'noUser_SelfAtt' (main...SegMM.py:275-280, main...KuaiRand.py:254-258): the TRAINING forward sees
             # uniform-random user features and random user ids in [1, n_users); validation keeps the real ones
-            live = st.__dict__.get("live_seed")
+            live = E.live_seed(st)
             n_users = self._n_users()
             if live is not None:
                 # device-side step state (the step may be recorded): the draws come from the library's counter hash, into persistent
@@ -1062,6 +1241,11 @@ class Trainer:
             out["loss"].backward()
         else:
             torch.autograd.backward(out["loss"], grad_tensors=[model.unit_grad(out["loss"].device)])
+        return out
+
+    def _finish_step(self, out):
+        """The tail of the plain step: the data-parallel reductions still outstanding, then AdamW."""
+        st = self.model._store
         if self.comm.active and self.overlap:
             H.host_action(self._flush_bucket)          # the tail of the backward (embedding gradients) that stayed below the merge threshold
         if self.comm.active and self.overlap and self.per_bucket_adamw and self._covers_live(st):
