@@ -397,6 +397,33 @@ int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, 
 int segmm_adamw_table_scaled(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                              uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* coef,
                              segmm_stream_t stream);
+/* Parameter groups: per-group learning-rate scale, weight decay and freezing inside the one-launch step.  The flat buffers are cut
+ * into n_seg SEGMENTS, device arrays of n_seg entries each: segment s covers the floats [seg_end[s - 1], seg_end[s]) counted from
+ * the buffers' BASE (seg_end[-1] = 0; ends ascending; every end but the last a multiple of 4; floats at or beyond the last end go
+ * with the last segment), steps at the rate fp32(lr * seg_lr_scale[s]) with the decay seg_weight_decay[s], and with
+ * seg_frozen[s] != 0 is left alone.
+ * segmm_adamw_groups: ONE launch over the floats [start, start + n) of p, g, m, v (base pointers, 16-byte aligned; start a
+ *   multiple of 4; the range may begin and end inside a segment; the n % 4 tail belongs to the last segment the range touches).
+ *   For every element the result is bit for bit that of segmm_adamw (coef == NULL) or segmm_adamw_scaled (coef: the device float
+ *   the gradient is multiplied by first) launched on that element's segment alone with lr = fp32(lr * seg_lr_scale[s]) and
+ *   weight_decay = seg_weight_decay[s]; with one segment of scale 1 that is segmm_adamw itself.  Elements of frozen segments are
+ *   neither read nor written: no p, no g, no m, no v.  seg_frozen == NULL says that no segment is frozen (the kernel then need not
+ *   wait for the table before it loads its elements: the faster form when nothing is frozen).  lr = SEGMM_LIVE_LR with step == -1:
+ *   lr is the device step state's rate (the scale applies to it), the bias corrections the state's, as in segmm_adamw.
+ * segmm_grad_norm_groups: segmm_grad_norm over g[0, n) (g the 16-byte aligned base the ends count from) WITHOUT the elements of
+ *   frozen segments, which are not read: a NaN or inf there does not reach out2.  fp64 partials, fixed order, the coefficient
+ *   arithmetic of segmm_grad_norm.
+ * segmm_adamw_table_lrs: segmm_adamw_table (phase 0 and 1, coef == NULL) and segmm_adamw_table_scaled (phase 1, coef != NULL) at
+ *   the rate fp32(lr * lr_scale) -- lr the argument or, with SEGMM_LIVE_LR, the device state's; lr_scale finite and >= 0.  The
+ *   same row kernels; lr_scale = 1 gives the bits of the two older entry points. */
+int segmm_adamw_groups(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end,
+                       const float* seg_lr_scale, const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr,
+                       float beta1, float beta2, float eps, int step, const float* coef, segmm_stream_t stream);
+int segmm_grad_norm_groups(const float* g, int64_t n, const int64_t* seg_end, const uint8_t* seg_frozen, int n_seg, float max_norm,
+                           double* scratch, float* out2, segmm_stream_t stream);
+int segmm_adamw_table_lrs(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                          uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step,
+                          int phase, const float* coef, segmm_stream_t stream);
 /* Device-side step state, so that a whole training step (main_for_seq_leave_earlystop_SegMM.py:265-300) can be replayed from its
  * recorded launch sequences with unchanged kernel arguments: two dropout seed words and the optimizer's step count with its bias
  * corrections live in device memory -- a struct of segmm_step_state_bytes() bytes in CALLER-OWNED, 16-byte aligned device memory

@@ -1609,18 +1609,22 @@ int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, 
     return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream);
 }
 
-int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
-                      uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
-                      segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && m && v && flags && (ids || n_ids == 0) && aligned16(p) && aligned16(m) && aligned16(v), "adamw_table: pointer/alignment");
-    SEGMM_REQUIRE(phase == 0 || (phase == 1 && g && aligned16(g)), "adamw_table: phase %d (0: rows without a gradient, 1: the listed rows; needs g)", phase);
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "adamw_table: width %% 4, sizes");
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+// segmm_adamw_table / segmm_adamw_table_scaled / segmm_adamw_table_lrs: one body (`who`: the entry point's name in the messages)
+static int adamw_table_impl(const char* who, float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                            uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
+                            const float* coef, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && m && v && flags && (ids || n_ids == 0) && aligned16(p) && aligned16(m) && aligned16(v), "%s: pointer/alignment", who);
+    SEGMM_REQUIRE(phase == 0 || (phase == 1 && g && aligned16(g)), "%s: phase %d (0: rows without a gradient, 1: the listed rows; needs g)", who, phase);
+    SEGMM_REQUIRE(!coef || phase == 1, "%s: a scaled update is phase 1 only (phase 0 has g = 0)", who);
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "%s: width %% 4, sizes", who);
+    SEGMM_REQUIRE(step >= 1 || step == -1, "%s: step=%d (>= 1, or -1: the device-side step state)", who, step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "%s: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", who, (double)lr);
+    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "%s: lr_scale=%g (finite, >= 0)", who, (double)lr_scale);
     if (n_rows == 0) return 0;
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     hipStream_t s = (hipStream_t)stream;
     const int w4 = width / 4;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
     if (phase == 0) {
         if (n_ids > 0) {
             hipLaunchKernelGGL(table_mark_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, s, (const long long*)ids, n_ids, (long long)n_rows, flags);
@@ -1629,32 +1633,92 @@ int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_ro
         long long blocks = (n_rows * w4 + 255) / 256;
         if (blocks > 4096) blocks = 4096;
         hipLaunchKernelGGL(adamw_table_rest_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4, (const unsigned int*)flags,
-                           lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr);
+                           lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, lr_scale);
         LAUNCH_CHECK();
         return 0;
     }
     if (n_ids == 0) return 0;
-    hipLaunchKernelGGL(adamw_table_rows_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids, n_ids,
-                       flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr,
-                       (const float*)nullptr);
+    if (coef)
+        hipLaunchKernelGGL(adamw_table_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids,
+                           n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
+    else
+        hipLaunchKernelGGL(adamw_table_rows_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids,
+                           n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, (const float*)nullptr, lr_scale);
     LAUNCH_CHECK();
     return 0;
+}
+
+int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                      uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
+                      segmm_stream_t stream) {
+    return adamw_table_impl("adamw_table", p, g, m, v, n_rows, width, ids, n_ids, flags, lr, 1.0f, beta1, beta2, eps, weight_decay, step, phase, nullptr,
+                            stream);
 }
 
 int segmm_adamw_table_scaled(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                              uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* coef,
                              segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && flags && (ids || n_ids == 0) && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v),
-                  "adamw_table_scaled: pointer/alignment");
+    SEGMM_REQUIRE(g && aligned16(g), "adamw_table_scaled: pointer/alignment");
     SEGMM_REQUIRE(coef, "adamw_table_scaled: null coef (use segmm_adamw_table for an unscaled step)");
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "adamw_table_scaled: width %% 4, sizes");
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_scaled: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table_scaled: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    if (n_rows == 0 || n_ids == 0) return 0;
+    return adamw_table_impl("adamw_table_scaled", p, g, m, v, n_rows, width, ids, n_ids, flags, lr, 1.0f, beta1, beta2, eps, weight_decay, step, 1, coef,
+                            stream);
+}
+
+int segmm_adamw_table_lrs(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                          uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
+                          const float* coef, segmm_stream_t stream) {
+    return adamw_table_impl("adamw_table_lrs", p, g, m, v, n_rows, width, ids, n_ids, flags, lr, lr_scale, beta1, beta2, eps, weight_decay, step, phase,
+                            coef, stream);
+}
+
+int segmm_adamw_groups(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end, const float* seg_lr_scale,
+                       const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1, float beta2, float eps, int step,
+                       const float* coef, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_groups: pointer/alignment");
+    SEGMM_REQUIRE(seg_end && seg_lr_scale && seg_weight_decay && n_seg >= 1 && (((uintptr_t)seg_end) & 7u) == 0 &&
+                  (((uintptr_t)seg_lr_scale) & 3u) == 0 && (((uintptr_t)seg_weight_decay) & 3u) == 0, "adamw_groups: segment table (n_seg=%d)", n_seg);
+    SEGMM_REQUIRE(start >= 0 && start % 4 == 0 && n >= 0, "adamw_groups: start=%lld (>= 0, a multiple of 4), n=%lld", (long long)start, (long long)n);
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_groups: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_groups: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+    if (n <= 0) return 0;
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
-    hipLaunchKernelGGL(adamw_table_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, width / 4,
-                       (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
-                       step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr, coef);
+    long long blocks = ((n >> 2) + 255) / 256;          // the grid of segmm_adamw
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+#define SEGMM_ADAMW_GROUPS(SCALED, FROZEN)                                                                                                        \
+    hipLaunchKernelGGL((adamw_groups_kernel<SCALED, FROZEN>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)start, \
+                       (long long)n, (const long long*)seg_end, seg_lr_scale, seg_weight_decay, (const unsigned char*)seg_frozen, n_seg, lr, beta1,   \
+                       beta2, eps, (float)bc1, (float)sqrt(bc2), live, coef)
+    if (coef && seg_frozen) SEGMM_ADAMW_GROUPS(true, true);
+    else if (coef) SEGMM_ADAMW_GROUPS(true, false);
+    else if (seg_frozen) SEGMM_ADAMW_GROUPS(false, true);
+    else SEGMM_ADAMW_GROUPS(false, false);
+#undef SEGMM_ADAMW_GROUPS
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_grad_norm_groups(const float* g, int64_t n, const int64_t* seg_end, const uint8_t* seg_frozen, int n_seg, float max_norm, double* scratch,
+                           float* out2, segmm_stream_t stream) {
+    SEGMM_REQUIRE(g && scratch && out2, "grad_norm_groups: null pointer");
+    SEGMM_REQUIRE((((uintptr_t)scratch) & 7u) == 0 && (((uintptr_t)out2) & 3u) == 0, "grad_norm_groups: alignment");
+    SEGMM_REQUIRE(n >= 0, "grad_norm_groups: n=%lld", (long long)n);
+    SEGMM_REQUIRE(max_norm > 0.f, "grad_norm_groups: max_norm=%f (> 0, or inf: report the norm, never clip)", (double)max_norm);
+    SEGMM_REQUIRE(aligned16(g) && seg_end && seg_frozen && n_seg >= 1 && (((uintptr_t)seg_end) & 7u) == 0,
+                  "grad_norm_groups: g is the 16-byte aligned base the segment ends count from; segment table (n_seg=%d)", n_seg);
+    hipStream_t s = (hipStream_t)stream;
+    int nparts = 0;
+    if (n > 0) {
+        long long blocks = ((n >> 2) + 255) / 256;
+        if (blocks > GRAD_NORM_PARTS) blocks = GRAD_NORM_PARTS;
+        if (blocks < 1) blocks = 1;
+        nparts = (int)blocks;
+        hipLaunchKernelGGL(sumsq_parts_groups_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g, (long long)n, (const long long*)seg_end,
+                           (const unsigned char*)seg_frozen, n_seg, scratch);
+        LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)scratch, nparts, max_norm, out2);
     LAUNCH_CHECK();
     return 0;
 }

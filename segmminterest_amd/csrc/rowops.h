@@ -722,7 +722,88 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---------------------------------------------------------------- AdamW over a flat range cut into parameter-group segments
+// (segmm_adamw_groups).  Segment s covers the floats [seg_end[s - 1], seg_end[s]) counted from the buffers' base (seg_end[-1] = 0);
+// floats at or beyond seg_end[n_seg - 1] go with the last segment.  Every end but the last is a multiple of 4, so a 16-byte vector
+// never straddles two segments.
+// seg_find: the segment of float offset e, searched in [lo, n_seg): the first s with seg_end[s] > e.  Callers pass wave-uniform
+// arguments (the search runs on the scalar unit) and a lower bound that only grows as a grid-stride loop advances.
+__device__ __forceinline__ int seg_find(const long long* __restrict__ seg_end, int n_seg, int lo, long long e) {
+    int hi = n_seg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (seg_end[mid] > e) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// The walk over the range is adamw_kernel's (same grid, same stride: 28 B per element of HBM traffic either way).  A wave's 64
+// vectors of one iteration are 256 consecutive floats: their segment is resolved ONCE per wave and iteration; where all 256 lie in
+// one segment (every wave but the few that sit on a segment end) the rate lr * lr_scale[s], the step and the decay are computed
+// once, wave-uniform.  A wave that sits on an end lets each lane walk on from the wave's segment to its own.  Per element the
+// arithmetic is adamw_elem4 with lr = fp32(lr * lr_scale[s]) and wd = seg_wd[s]: bit for bit adamw_kernel launched on that
+// segment alone.  Elements of a frozen segment are neither loaded nor stored.
+// FROZEN = false (seg_frozen == NULL: the caller knows that no segment is frozen): the loads of p, g, m, v do not wait for the table --
+// with a frozen flag to honour, a wave must have read the table before it may touch its elements, one dependent round trip more than
+// adamw_kernel has and at a cache-resident size (a wave runs one or two iterations) about half a microsecond of a 28 us launch
+// (profiles/param_groups/adamw_groups_bench.txt and profiles/README.md).
+template <bool SCALED, bool FROZEN>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ v, long long start, long long n, const long long* __restrict__ seg_end,
+                             const float* __restrict__ seg_lr_scale, const float* __restrict__ seg_wd,
+                             const unsigned char* __restrict__ seg_frozen, int n_seg, float lr, float b1, float b2, float eps,
+                             float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
+#pragma clang fp contract(off)
+    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    const long long n4 = n >> 2;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    f32x4* p4 = (f32x4*)(p + start); const f32x4* g4 = (const f32x4*)(g + start);
+    f32x4* m4 = (f32x4*)(m + start); f32x4* v4 = (f32x4*)(v + start);
+    int s = 0;
+    for (long long w0 = blockIdx.x * (long long)blockDim.x + wave * 64; w0 < n4; w0 += (long long)gridDim.x * blockDim.x) {
+        const long long e0 = start + (w0 << 2);                                   // the wave's first float, from the buffers' base
+        long long e1 = e0 + 256;                                                  // one past its last
+        if (e1 > start + (n4 << 2)) e1 = start + (n4 << 2);
+        s = seg_find(seg_end, n_seg, s, e0);
+        const long long i = w0 + lane;
+        // the wave's segment: its four table entries in one round of scalar loads (nothing below waits for one after the other)
+        const long long end_s = seg_end[s];
+        unsigned char fz = 0;
+        if constexpr (FROZEN) fz = seg_frozen[s];
+        float sc = seg_lr_scale[s], wd = seg_wd[s];
+        if (end_s < e1 && s < n_seg - 1) {                                        // a segment ends inside the wave's 256 floats
+            const long long e = e0 + (lane << 2);
+            int ls = s;
+            while (ls < n_seg - 1 && seg_end[ls] <= e) ++ls;
+            if constexpr (FROZEN) fz = seg_frozen[ls];
+            sc = seg_lr_scale[ls]; wd = seg_wd[ls];
+        }
+        if (i >= n4 || fz) continue;
+        const float lr_s = lr * sc;
+        const float step = lr_s / bc1;
+        f32x4 pp = p4[i];
+        const f32x4 gg = adamw_grad4<SCALED>(g4[i], coef);
+        f32x4 mm = m4[i], vv = v4[i];
+        adamw_elem4(pp, gg, mm, vv, lr_s, b1, b2, eps, wd, step, bc2_sqrt);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+    }
+    // tail (n % 4): the last segment the range touches
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long long i = start + (n4 << 2) + threadIdx.x;
+        const int ls = seg_find(seg_end, n_seg, 0, start + n - 1);
+        if (!FROZEN || !seg_frozen[ls]) {
+            const float lr_s = lr * seg_lr_scale[ls];
+            const float step = lr_s / bc1;
+            f32x4 pp = {p[i], 0.f, 0.f, 0.f}, mm = {m[i], 0.f, 0.f, 0.f}, vv = {v[i], 0.f, 0.f, 0.f};
+            adamw_elem4(pp, adamw_grad4<SCALED>(f32x4{g[i], 0.f, 0.f, 0.f}, coef), mm, vv, lr_s, b1, b2, eps, seg_wd[ls], step, bc2_sqrt);
+            p[i] = pp.x; m[i] = mm.x; v[i] = vv.x;
+        }
+    }
+}
+
 // AdamW of an id-embedding table in two passes (segmm_adamw_table): the arithmetic of adamw_kernel, element for element
+// (lr_scale: the rate is fp32(lr * lr_scale), lr being the argument or the device state's -- segmm_adamw_table_lrs; 1 elsewhere,
+// which leaves every bit of lr as it is)
 __global__ __launch_bounds__(256) void table_mark_kernel(const long long* __restrict__ ids, int n, long long n_rows, unsigned int* __restrict__ flags) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) {
@@ -733,8 +814,11 @@ __global__ __launch_bounds__(256) void table_mark_kernel(const long long* __rest
 // every row WITHOUT a mark, g = 0
 __global__ __launch_bounds__(256) void adamw_table_rest_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long n_rows,
                                                                int w4, const unsigned int* __restrict__ flags, float lr, float b1, float b2,
-                                                               float eps, float wd, float bc1, float bc2_sqrt, const StepState* live) {
+                                                               float eps, float wd, float bc1, float bc2_sqrt, const StepState* live,
+                                                               float lr_scale) {
+#pragma clang fp contract(off)
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    lr = lr * lr_scale;
     const float step = lr / bc1;
     const long long n4 = n_rows * w4;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -751,8 +835,10 @@ __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict
                                                                float* __restrict__ v, long long n_rows, int w4, const long long* __restrict__ ids,
                                                                int n_ids, unsigned int* __restrict__ flags, float lr, float b1, float b2, float eps,
                                                                float wd, float bc1, float bc2_sqrt, const StepState* live,
-                                                               const float* __restrict__ coef) {
+                                                               const float* __restrict__ coef, float lr_scale) {
+#pragma clang fp contract(off)
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    lr = lr * lr_scale;
     const float step = lr / bc1;
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -805,6 +891,39 @@ __global__ __launch_bounds__(256) void sumsq_parts_kernel(const float* __restric
             const float x = g[lead + (n4 << 2) + threadIdx.x];
             acc += (double)x * x;
         }
+    }
+    acc = block_sum256(acc, red);
+    if (threadIdx.x == 0) parts[blockIdx.x] = acc;
+}
+// segmm_grad_norm_groups: the partials of g[0, n) WITHOUT the frozen segments (the table of adamw_groups_kernel; g is the buffers'
+// base, 16-byte aligned).  A wave resolves the segment of its 256 consecutive floats once per iteration, as adamw_groups_kernel does;
+// a frozen element is not loaded, so whatever it holds (NaN, inf) cannot reach a partial.  Fixed order: same gradient, same bits.
+__global__ __launch_bounds__(256) void sumsq_parts_groups_kernel(const float* __restrict__ g, long long n, const long long* __restrict__ seg_end,
+                                                                 const unsigned char* __restrict__ seg_frozen, int n_seg,
+                                                                 double* __restrict__ parts) {
+    __shared__ double red[4];
+    const f32x4* g4 = (const f32x4*)g;
+    const long long n4 = n >> 2;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0;
+    int s = 0;
+    for (long long w0 = blockIdx.x * (long long)blockDim.x + wave * 64; w0 < n4; w0 += (long long)gridDim.x * blockDim.x) {
+        const long long e0 = w0 << 2;
+        long long e1 = e0 + 256;
+        if (e1 > (n4 << 2)) e1 = n4 << 2;
+        s = seg_find(seg_end, n_seg, s, e0);
+        const long long i = w0 + lane;
+        int ls = s;
+        if (seg_end[s] < e1 && s < n_seg - 1) {
+            const long long e = e0 + (lane << 2);
+            while (ls < n_seg - 1 && seg_end[ls] <= e) ++ls;
+        }
+        if (i < n4 && !seg_frozen[ls]) acc += sq4(g4[i]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3) && !seg_frozen[seg_find(seg_end, n_seg, 0, n - 1)]) {
+        const float x = g[(n4 << 2) + threadIdx.x];
+        acc += (double)x * x;
     }
     acc = block_sum256(acc, red);
     if (threadIdx.x == 0) parts[blockIdx.x] = acc;

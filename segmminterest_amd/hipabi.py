@@ -1045,7 +1045,56 @@ def _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0, co
         _check(lib().segmm_adamw_scaled(*args, coef.data_ptr(), _stream()), "segmm_adamw_scaled")
 
 
+def _segs(segs):
+    """The segment table of a grouped optimizer, (ends int64, lr_scale float32, weight_decay float32, frozen uint8): equally long,
+    contiguous device tensors -> their pointers and the segment count.  ``frozen`` may be None: no segment is frozen."""
+    ends, scale, wd, frozen = segs
+    n_seg = ends.numel()
+    given = [t for t in segs if t is not None]
+    if (ends.dtype, scale.dtype, wd.dtype) != (torch.int64, torch.float32, torch.float32) or (frozen is not None and frozen.dtype != torch.uint8) \
+            or n_seg < 1 or not all(t.numel() == n_seg and t.is_contiguous() for t in given):
+        raise RuntimeError("segment table: int64 ends, float32 lr_scale, float32 weight_decay, uint8 frozen (or None), one entry per segment")
+    _dev(*given)
+    return ends.data_ptr(), scale.data_ptr(), wd.data_ptr(), _ptr(frozen), n_seg
+
+
+def adamw_groups(p, g, m, v, start, n, segs, lr, beta1, beta2, eps, step, coef=None):
+    """segmm_adamw_groups over [start, start + n) of the flat buffers, ``segs`` = (ends, lr_scale, weight_decay, frozen) the
+    segment table (:func:`_segs`; ends counted from the buffers' first element); ``coef`` as in :func:`adamw`."""
+    start, n = int(start), int(n)
+    if start < 0 or start % 4 or n < 0 or start + n > min(p.numel(), g.numel(), m.numel(), v.numel()):
+        raise RuntimeError("adamw_groups: range [%d, %d) (start a multiple of 4) outside buffers of %d / %d / %d / %d elements"
+                           % (start, start + n, p.numel(), g.numel(), m.numel(), v.numel()))
+    e, s, w, f, n_seg = _segs(segs)
+    with _kprof("adamw", 28 * n):
+        _check(lib().segmm_adamw_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), start, n, e, s, w, f, n_seg, float(lr), float(beta1),
+                                        float(beta2), float(eps), int(step), _ptr(coef), _stream()), "segmm_adamw_groups")
+
+
+def adamw_table_lrs(p, g, m, v, off, n_rows, width, ids, flags, lr, lr_scale, beta1, beta2, eps, weight_decay, step, phase, coef=None):
+    """segmm_adamw_table_lrs: :func:`adamw_table` at the rate fp32(lr * lr_scale)."""
+    with _kprof("adamw", (24 if phase == 0 else 28) * int(n_rows if phase == 0 else ids.numel()) * int(width)):
+        _check(lib().segmm_adamw_table_lrs(p.data_ptr() + 4 * off, None if g is None else g.data_ptr() + 4 * off, m.data_ptr() + 4 * off,
+                                           v.data_ptr() + 4 * off, int(n_rows), int(width), ids.data_ptr(), ids.numel(), flags.data_ptr(), float(lr),
+                                           float(lr_scale), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), int(phase),
+                                           _ptr(coef), _stream()), "segmm_adamw_table_lrs")
+
+
 GRAD_NORM_SCRATCH = 1024          # fp64 partials segmm_grad_norm may write
+
+
+def grad_norm_groups(g, n, segs, max_norm, scratch, out2):
+    """segmm_grad_norm_groups: :func:`grad_norm` over g[0, n) without the elements of the frozen segments of ``segs``."""
+    if scratch.dtype != torch.float64 or scratch.numel() < GRAD_NORM_SCRATCH or out2.dtype != torch.float32 or out2.numel() < 2:
+        raise RuntimeError("grad_norm_groups: scratch must be %d float64, out2 two float32" % GRAD_NORM_SCRATCH)
+    if n < 0 or n > g.numel():
+        raise RuntimeError("grad_norm_groups: %d elements of a tensor of %d" % (n, g.numel()))
+    e, _, _, f, n_seg = _segs(segs)
+    if f is None:
+        raise RuntimeError("grad_norm_groups: no frozen flags (without a frozen segment call grad_norm)")
+    with _kprof("grad_norm", 4 * int(n)):
+        _check(lib().segmm_grad_norm_groups(g.data_ptr(), int(n), e, f, n_seg, float(max_norm), scratch.data_ptr(), out2.data_ptr(), _stream()),
+               "segmm_grad_norm_groups")
 
 
 def grad_norm(g, n, max_norm, scratch, out2, off=0):

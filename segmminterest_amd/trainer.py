@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import fnmatch
 import functools
 import math
 import struct
@@ -107,6 +108,101 @@ def _f32(x):
         return struct.unpack("f", struct.pack("f", float(x)))[0]
     except OverflowError:          # beyond the fp32 range
         return math.copysign(math.inf, x)
+
+
+# ---- parameter groups (FusedAdamW(param_groups=...)): pure functions of names, sizes and offsets -- no device, no ParamStore
+GROUP_KEYS = ("params", "lr_scale", "weight_decay", "frozen")
+
+
+def _group_value(gi, key, x):
+    """A group's ``lr_scale`` / ``weight_decay``: a finite float >= 0, as the fp32 number the device table holds."""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not (0.0 <= float(x) < math.inf) or _f32(x) == math.inf:
+        raise ValueError("%s%s must be a finite float >= 0, not %r" % ("param_groups[%d]: " % gi if gi >= 0 else "", key, x))
+    return _f32(x)
+
+
+def resolve_param_groups(named, param_groups, weight_decay):
+    """``param_groups`` (the list of dicts FusedAdamW takes) resolved over ``named`` = [(name, parameter)] in
+    ``model.named_parameters()`` order (the parameter is only handed to callables; it may be None) -> a list of
+    ``{"names", "lr_scale", "weight_decay", "frozen"}``: entry 0 is the DEFAULT group (every parameter no group selects: scale 1,
+    the optimizer's ``weight_decay``; possibly empty), entry k + 1 is ``param_groups[k]``.  Refused by name: a parameter two groups
+    select, a pattern or callable that selects nothing, an unknown key, a value out of range."""
+    if not isinstance(param_groups, (list, tuple)) or not all(isinstance(g, dict) for g in param_groups):
+        raise ValueError("param_groups must be a list of dicts, not %r" % (param_groups,))
+    names = [n for n, _ in named]
+    owner = {}
+    out = [dict(names=[], lr_scale=1.0, weight_decay=_group_value(-1, "weight_decay (with param_groups)", weight_decay), frozen=False)]
+    for gi, g in enumerate(param_groups):
+        unknown = [k for k in g if k not in GROUP_KEYS]
+        if unknown:
+            raise ValueError("param_groups[%d]: unknown key %r (a group takes %s; betas and eps are the optimizer's, one pair for "
+                             "every group)" % (gi, unknown[0], ", ".join(GROUP_KEYS)))
+        if "params" not in g:
+            raise ValueError("param_groups[%d]: no 'params' (a list of names / fnmatch patterns, or a callable (name, parameter) -> bool)" % gi)
+        sel = g["params"]
+        if callable(sel):
+            picked = [n for n, p in named if sel(n, p)]
+            if not picked:
+                raise ValueError("param_groups[%d]: the callable %r selects no parameter" % (gi, getattr(sel, "__name__", sel)))
+        else:
+            if isinstance(sel, str):
+                sel = [sel]
+            picked, seen = [], set()
+            for pat in sel:
+                if not isinstance(pat, str):
+                    raise ValueError("param_groups[%d]: 'params' holds %r; names / fnmatch patterns are strings" % (gi, pat))
+                hit = [n for n in names if n == pat or fnmatch.fnmatchcase(n, pat)]
+                if not hit:
+                    raise ValueError("param_groups[%d]: the pattern %r selects no parameter" % (gi, pat))
+                picked += [n for n in hit if n not in seen]
+                seen.update(hit)
+        frozen = g.get("frozen", False)
+        if not isinstance(frozen, bool):
+            raise ValueError("param_groups[%d]: frozen must be a bool, not %r" % (gi, frozen))
+        for n in picked:
+            if n in owner:
+                raise ValueError("param_groups[%d] and param_groups[%d] both select the parameter %s" % (owner[n], gi, n))
+            owner[n] = gi
+        order = {n: i for i, n in enumerate(names)}
+        out.append(dict(names=sorted(picked, key=order.__getitem__), lr_scale=_group_value(gi, "lr_scale", g.get("lr_scale", 1.0)),
+                        weight_decay=_group_value(gi, "weight_decay", g.get("weight_decay", out[0]["weight_decay"])), frozen=frozen))
+    out[0]["names"] = [n for n in names if n not in owner]
+    return out
+
+
+def group_segments(order, n_live, hyper_of):
+    """The live range [0, n_live) cut into segments: ``order`` = [(name, offset, numel)] of the live parameters by ascending offset,
+    ``hyper_of(name)`` = (lr_scale, weight_decay, frozen) -> [(end, lr_scale, weight_decay, frozen)], maximal runs of consecutive
+    floats with equal values.  An alignment gap goes with the parameter in front of it (it holds zeros, and zeros stay zero under
+    any update), so a segment ends where the next parameter with other values STARTS: at a multiple of 4 floats (ParamStore lays
+    groups out at multiples of 32 and fused-group members have numel % 4 == 0) -- the 16-byte vectors of the kernels never
+    straddle two segments.  Only the last end, n_live itself, may be anything."""
+    segs = []
+    for name, off, _ in order:
+        h = tuple(hyper_of(name))
+        if segs and segs[-1][1:] == h:
+            continue
+        if segs:
+            if off % 4:
+                raise AssertionError("parameter %s starts at float %d, not a multiple of 4: a segment cannot end there" % (name, off))
+            segs[-1] = (off,) + segs[-1][1:]
+        segs.append((None,) + h)
+    if not segs:
+        return [(n_live, 1.0, 0.0, False)]
+    segs[-1] = (n_live,) + segs[-1][1:]
+    assert all(a[0] < b[0] for a, b in zip(segs, segs[1:])), segs
+    return segs
+
+
+def no_decay_groups(model):
+    """The usual AdamW recipe as a ``param_groups`` list: every bias, every LayerNorm weight and every positional table
+    (the ``*_pe`` embeddings) at weight decay 0; everything else stays in the default group."""
+    names = []
+    for mname, mod in model.named_modules():
+        for pname, _ in mod.named_parameters(recurse=False):
+            if pname == "bias" or isinstance(mod, nn.LayerNorm) or (isinstance(mod, nn.Embedding) and mname.endswith("_pe")):
+                names.append((mname + "." if mname else "") + pname)
+    return [{"params": names, "weight_decay": 0.0}]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -260,10 +356,30 @@ class FusedAdamW:
     rate of every step is evaluated on the DEVICE from ``lr`` (the base rate) and the schedule, inside the launch that advances
     the step state, and the AdamW kernels read it there -- so it may move under a recorded step.  Needs the device step state
     (``Trainer(device_state=True)``).  ``set_base_lr`` moves the base rate between two steps, ``current_lr`` is the host's value
-    of the coming step's rate, ``device_lr`` reads the device's (a sync)."""
+    of the coming step's rate, ``device_lr`` reads the device's (a sync).
 
-    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None):
+    ``param_groups`` (None = one rate and one decay for the whole live range, today's launches and bits): a list of dicts
+    ``{"params": ..., "lr_scale": 1.0, "weight_decay": <the optimizer's>, "frozen": False}``.  ``params`` is a list of exact names
+    or fnmatch patterns over ``model.named_parameters()``, or a callable ``(name, parameter) -> bool``; a parameter two groups
+    select, a pattern that selects nothing and any other key (``betas`` and ``eps`` included: one pair for every group, the device
+    step state's contract) are refused by name.  What no group selects is the default group (scale 1, the optimizer's decay).  A
+    group steps at fp32(rate x lr_scale), the rate being ``lr`` or, under ``lr_schedule``, the device's rate of that step: every
+    schedule, ``set_base_lr`` and PlateauLR move all groups at once.  The step stays ONE launch per range (segmm_adamw_groups): the
+    groups become segments of the live range (``group_segments``), a small table in device memory that is rebuilt only with the
+    flat buffer, so a recorded step replays with unchanged arguments; element for element the result is that of segmm_adamw on the
+    element's segment alone.  A FROZEN parameter is neither read nor written by the step (no p, m, v), its gradient stays out of
+    the clipping norm (torch: ``grad=None``) and ``state_dict()["state"]`` has no entry for it; its ``.grad`` is still what the
+    backward delivers -- the backward's work for frozen parameters is NOT skipped, freezing saves optimizer traffic only.  Dead
+    parameters may be listed; they stay untouched as ever.  ``no_decay_groups(model)`` is the usual no-decay recipe,
+    ``group_of(name)`` a parameter's resolved values."""
+
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None,
+                 param_groups=None):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
+        # resolved groups (resolve_param_groups; entry 0 = the default group) or None; _segs: their segment table on the device
+        self.groups = None if param_groups is None else resolve_param_groups(list(model.named_parameters()), param_groups, weight_decay)
+        self._group_idx = None if self.groups is None else {n: gi for gi, G in enumerate(self.groups) for n in G["names"]}
+        self._segs = self._segs_host = None
         self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
         self.schedule = LRSchedule.parse(lr_schedule, lr)
         self.step_count = 0
@@ -278,7 +394,48 @@ class FusedAdamW:
             self.m = torch.zeros(st.n_live, device=st.flat.device)
             self.v = torch.zeros(st.n_live, device=st.flat.device)
             self._flat_id = st.flat.data_ptr()
+            self._segs = None
+        if self.groups is not None and self._segs is None:
+            self._build_segments(st)
         return st
+
+    # ---- parameter groups
+    def group_of(self, name):
+        """``(lr_scale, weight_decay, frozen)`` of the parameter ``name`` as the step applies them (fp32 values)."""
+        if self.groups is None:
+            if name not in dict(self.model.named_parameters()):
+                raise KeyError("group_of: the model has no parameter %s" % name)
+            return 1.0, _f32(self.wd), False
+        if name not in self._group_idx:
+            raise KeyError("group_of: the model has no parameter %s" % name)
+        G = self.groups[self._group_idx[name]]
+        return G["lr_scale"], G["weight_decay"], G["frozen"]
+
+    def group_table(self):
+        """The resolved groups as a hashable value (Trainer._hyper: a recorded step is refused once it differs)."""
+        return None if self.groups is None else tuple((tuple(G["names"]), G["lr_scale"], G["weight_decay"], G["frozen"]) for G in self.groups)
+
+    def _build_segments(self, st):
+        """The groups as segments of the store's live range, in persistent device tensors (ends int64, lr_scale and weight_decay
+        float32, frozen bytes).  An existing table of the same length is rewritten in place: the launches of a recorded step name
+        these tensors.  ``_segs_arg`` is what the AdamW launches get: without a frozen segment no flags at all, which lets the
+        kernel load its elements without waiting for the table."""
+        order = sorted((st.index[n] + (n,) for n in st.live_names))
+        segs = group_segments([(n, o, k) for o, k, n in order], st.n_live, self.group_of)
+        cols = list(zip(*segs))
+        dev = st.flat.device
+        new = tuple(torch.tensor(c, dtype=dt) for c, dt in zip(cols, (torch.int64, torch.float32, torch.float32, torch.uint8)))
+        if self._segs is not None and self._segs[0].numel() == len(segs) and self._segs[0].device == dev:
+            for old, t in zip(self._segs, new):
+                old.copy_(t)
+        else:
+            self._segs = tuple(t.to(dev) for t in new)
+        self._segs_host = segs
+        self._any_frozen = any(s[3] for s in segs)
+        self._segs_arg = self._segs if self._any_frozen else self._segs[:3] + (None,)
+
+    def _frozen(self, name):
+        return self.groups is not None and self.groups[self._group_idx[name]]["frozen"]
 
     def zero_grad(self, set_to_none=True):
         plist = self.__dict__.get("_plist")
@@ -341,11 +498,15 @@ class FusedAdamW:
         pos = 0
         # id tables whose rows without a gradient were already stepped at the head of the step (table_early): the listed rows
         # now, with their gradients; everything else as contiguous ranges around them
-        for o, n, rows, width, ids, flags in sorted(self.__dict__.pop("_early", []), key=lambda e: e[0]):
+        for o, n, rows, width, ids, flags, hyper in sorted(self.__dict__.pop("_early", []), key=lambda e: e[0]):
             self.step_range(pos, o, gbuf)
-            H.adamw_table(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0],
-                          self.betas[1], self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, 1,
-                          coef=self._coef())
+            step = -1 if self.__dict__.get("device_state", False) else self.step_count
+            if hyper is None:
+                H.adamw_table(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0],
+                              self.betas[1], self.eps, self.wd, step, 1, coef=self._coef())
+            else:          # (an id table lies in one group by construction: it is one parameter)
+                H.adamw_table_lrs(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), hyper[0],
+                                  self.betas[0], self.betas[1], self.eps, hyper[1], step, 1, coef=self._coef())
             pos = o + n
         self.step_range(pos, st.n_live, gbuf)
         self.end_step()
@@ -357,15 +518,23 @@ class FusedAdamW:
         only read the listed rows).  ``step()`` then updates the listed rows and skips the table's range.  Element for element
         the arithmetic of the one-launch dense update."""
         st = self._state()
+        if self._frozen(name):          # nothing to step, now or later: step() walks over the table's range, which the kernel skips
+            return
+        hyper = None if self.groups is None else self.group_of(name)[:2]
         o, n = st.index[name]
         rows, width = st._params[name].shape
         fl = self.__dict__.setdefault("_table_flags", {})
         flags = fl.get(name)
         if flags is None or flags.numel() != rows or flags.device != st.flat.device:
             flags = fl[name] = torch.zeros((rows,), dtype=torch.int32, device=st.flat.device)
-        H.adamw_table(st.flat, None, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0], self.betas[1], self.eps, self.wd,
-                      -1 if self.__dict__.get("device_state", False) else self.step_count + 1, 0)
-        self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, flags))
+        step = -1 if self.__dict__.get("device_state", False) else self.step_count + 1
+        if hyper is None:
+            H.adamw_table(st.flat, None, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0], self.betas[1], self.eps, self.wd,
+                          step, 0)
+        else:
+            H.adamw_table_lrs(st.flat, None, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), hyper[0], self.betas[0], self.betas[1],
+                              self.eps, hyper[1], step, 0)
+        self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, flags, hyper))
 
     # one optimizer step as several launches over disjoint ranges that together cover the live range: the data-parallel
     # trainer steps each gradient bucket as soon as ITS all-reduce has completed (begin_step, step_range ..., end_step)
@@ -380,7 +549,10 @@ class FusedAdamW:
             if self._clip_out is None or self._clip_out.device != st.flat.device:
                 self._clip_out = torch.zeros(2, dtype=torch.float32, device=st.flat.device)
                 self._clip_scratch = torch.zeros(H.GRAD_NORM_SCRATCH, dtype=torch.float64, device=st.flat.device)
-            H.grad_norm(st.gflat if gbuf is None else gbuf, st.n_live, self.max_grad_norm, self._clip_scratch, self._clip_out)
+            if self.groups is not None and self._any_frozen:          # frozen gradients stay out of the norm (torch: grad = None)
+                H.grad_norm_groups(st.gflat if gbuf is None else gbuf, st.n_live, self._segs, self.max_grad_norm, self._clip_scratch, self._clip_out)
+            else:
+                H.grad_norm(st.gflat if gbuf is None else gbuf, st.n_live, self.max_grad_norm, self._clip_scratch, self._clip_out)
 
     def _sync_grads(self, st):
         """The kernel reads the FLAT gradient buffer.  After Trainer.train_step the parameters' ``.grad`` ARE views of it
@@ -401,10 +573,14 @@ class FusedAdamW:
             # the bound step state is a process-global host pointer read when a launch is MADE; a direct opt.step() /
             # step_range() between two trainers' steps must not pick up the other trainer's seed words and bias corrections
             H.step_bind(self._step_state)
-        if end > start:
+        step = -1 if self.__dict__.get("device_state", False) else self.step_count
+        if end > start and self.groups is not None:
+            H.adamw_groups(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, start, end - start, self._segs_arg, self._lr_arg(), self.betas[0],
+                           self.betas[1], self.eps, step, coef=self._coef())
+        elif end > start:
             # device_state: the bias corrections come from the device-side step count (segmm_step_advance), step = -1
             H.adamw(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, end - start, self._lr_arg(), self.betas[0], self.betas[1],
-                    self.eps, self.wd, -1 if self.__dict__.get("device_state", False) else self.step_count, p_off=start, coef=self._coef())
+                    self.eps, self.wd, step, p_off=start, coef=self._coef())
 
     def end_step(self):
         self.model._store.fused_version += 1          # the pre-split weight planes of the GEMM engines are now stale
@@ -416,7 +592,7 @@ class FusedAdamW:
         names = [n for n, _ in self.model.named_parameters()]
         state = {}
         for i, n in enumerate(names):
-            if n in st.live_names:
+            if n in st.live_names and not self._frozen(n):
                 o, k = st.index[n]
                 shape = st._params[n].shape
                 state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.m[o:o + k].view(shape).clone(),
@@ -428,19 +604,60 @@ class FusedAdamW:
             # torch's schedulers keep the base rate in "initial_lr" and the running one in "lr"; the descriptor is an extra key
             # torch.optim.AdamW.load_state_dict carries along untouched
             group.update(lr=self.current_lr(), initial_lr=self.lr, segmm_lr_schedule=dataclasses.asdict(self.schedule))
-        return {"state": state, "param_groups": [group]}
+        if self.groups is None:
+            return {"state": state, "param_groups": [group]}
+        # one torch-format entry per group, the default group first (scale 1: its "lr" / "initial_lr" are the optimizer's own, as in
+        # a one-group checkpoint).  "params" leaves the frozen parameters out, as a torch optimizer built without them would;
+        # "segmm_frozen_params" names them, so that load_state_dict can tell a grouping from another.
+        out = []
+        for gi, G in enumerate(self.groups):
+            idx = [i for i, n in enumerate(names) if self._group_idx[n] == gi]
+            e = dict(group, weight_decay=G["weight_decay"] if gi else self.wd, segmm_lr_scale=G["lr_scale"], params=[] if G["frozen"] else idx)
+            if G["lr_scale"] != 1.0:
+                e["lr"] = _f32(_f32(group["lr"]) * G["lr_scale"])
+                if "initial_lr" in e:
+                    e["initial_lr"] = _f32(_f32(self.lr) * G["lr_scale"])
+            if G["frozen"]:
+                e["segmm_frozen_params"] = idx
+            out.append(e)
+        return {"state": state, "param_groups": out}
+
+    def _check_grouping(self, sd, names):
+        """Refuses, by the name of the first parameter that differs, a checkpoint whose grouping is not this optimizer's."""
+        mine = [self._group_idx[n] for n in names] if self.groups is not None else [0] * len(names)
+        theirs = {}
+        for gi, g in enumerate(sd["param_groups"]):
+            for i in list(g["params"]) + list(g.get("segmm_frozen_params", ())):
+                theirs[int(i)] = gi
+        for i, n in enumerate(names):
+            if theirs.get(i) != mine[i]:
+                raise ValueError("load_state_dict: the checkpoint has the parameter %s in %s, this optimizer in param group %d%s -- build "
+                                 "the optimizer with the checkpoint's param_groups"
+                                 % (n, "no param group" if i not in theirs else "param group %d" % theirs[i], mine[i],
+                                    " (the default group)" if mine[i] == 0 else ""))
+        n_mine = len(self.groups) if self.groups is not None else 1
+        if len(sd["param_groups"]) != n_mine:
+            raise ValueError("load_state_dict: the checkpoint has %d param groups, this optimizer %d" % (len(sd["param_groups"]), n_mine))
+        for gi, g in enumerate(sd["param_groups"]):
+            frozen = "segmm_frozen_params" in g
+            if frozen != (self.groups is not None and self.groups[gi]["frozen"]):
+                raise ValueError("load_state_dict: param group %d (%s ...) is %s in the checkpoint and %s in this optimizer"
+                                 % (gi, names[int((list(g["params"]) + list(g.get("segmm_frozen_params", ())) + [0])[0])],
+                                    "frozen" if frozen else "trained", "trained" if frozen else "frozen"))
 
     def load_state_dict(self, sd):
         if "segmm_lr_schedule" in sd["param_groups"][0]:          # (refused before anything is overwritten)
             self._bound_state("load_state_dict of a checkpoint written under an lr_schedule")
-        st = self._state()
         names = [n for n, _ in self.model.named_parameters()]
+        if self.groups is not None or len(sd["param_groups"]) > 1:
+            self._check_grouping(sd, names)
+        st = self._state()
         self.m.zero_()
         self.v.zero_()
         steps = set()
         for i, s in sd["state"].items():
             n = names[int(i)]
-            if n in st.live_names:
+            if n in st.live_names and not self._frozen(n):
                 o, k = st.index[n]
                 self.m[o:o + k].copy_(s["exp_avg"].reshape(-1))
                 self.v[o:o + k].copy_(s["exp_avg_sq"].reshape(-1))
@@ -448,6 +665,11 @@ class FusedAdamW:
         self.step_count = max(steps) if steps else 0
         g = sd["param_groups"][0]
         self.lr, self.wd, self.betas, self.eps = g["lr"], g["weight_decay"], tuple(g["betas"]), g["eps"]
+        if self.groups is not None:          # the groups' own values (entry 0, the default group, follows the optimizer's decay)
+            for G, e in zip(self.groups, sd["param_groups"]):
+                G["lr_scale"] = _group_value(-1, "load_state_dict: segmm_lr_scale", e.get("segmm_lr_scale", 1.0))
+                G["weight_decay"] = _group_value(-1, "load_state_dict: weight_decay", e["weight_decay"])
+            self._build_segments(st)
         if "segmm_lr_schedule" in g:          # written under a schedule: "lr" is the rate of the next step, "initial_lr" the base
             self.lr = g["initial_lr"]
             self.schedule = LRSchedule.parse(g["segmm_lr_schedule"], self.lr)
@@ -680,7 +902,8 @@ class Trainer:
 
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
-                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None):
+                 feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None,
+                 param_groups=None):
         self.model = model
         # micro_batch=m: a batch of more than m rows is stepped in ceil(B / m) micro-batches with ONE optimizer step on the whole
         # batch's gradient (train_step / _train_step_micro); None, or m >= the batch's rows: the plain step, launch for launch
@@ -700,7 +923,8 @@ class Trainer:
         # HBM-bound kernel (segmm_gather_l1) and the 573 KB/row host->device copy disappears
         self.feature_table = feature_table
         self.dropout = dropout      # False: run the step in eval mode (deterministic; used by the DP equivalence tests)
-        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
+        self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
+                              param_groups=param_groups)          # per-group rate scale, decay and freezing: see FusedAdamW
         self.comm = comm if comm is not None else DPComm()
         self.overlap = overlap
         st = model._store
@@ -863,7 +1087,7 @@ class Trainer:
         stale = self.opt.__dict__.pop("_early", None)
         if stale:
             E.join_aux(self.model._store)
-            for _, _, _, _, _, flags in stale:
+            for _, _, _, _, _, flags, _ in stale:
                 flags.zero_()
             #  the failed step had already advanced the DEVICE step count (segmm_step_advance at its head) while
             # opt.step_count never moved, and THIS step has advanced it once more: put it back to step_count + 1, the number of the
@@ -1414,7 +1638,7 @@ class Trainer:
     def _hyper(self):
         # under an lr_schedule the recorded commands carry the sentinel, not a rate: the rate may move, the schedule's presence not
         lr = self.opt.lr if self.opt.schedule is None else H.LIVE_LR
-        return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm)
+        return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm, self.opt.group_table())
 
     def _timed_plan(self, r):
         """The recorded phases cut at every GEMM / attention command (bench.py's timed replay): [("host", fn) | ("run", Phase) |
