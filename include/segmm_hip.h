@@ -715,6 +715,16 @@ int segmm_copy_bytes(void* dst, const void* src, int64_t bytes, segmm_stream_t s
 /* test hook: multiplier (0 or 1/(1-p)) of elements [0,n) of a dropout site */
 int segmm_dropout_mult(float* out, int64_t n, float p, uint64_t seed, uint32_t site, segmm_stream_t stream);
 
+/* The weight average of Trainer(ema=...), placed in front of segmm_vec_add; added under ABI version 30: nothing that existed changed.
+ * segmm_ema_update: shadow[i] = shadow[i] + (p[i] - shadow[i]) * w for i < n, three IEEE fp32 operations, nothing contracted, in place.
+ *   w = weight (0 < weight <= 1), or with warmup != 0: w = max(weight, (float)(9.0 / (10.0 + (double)t))) -- decay_t = min(decay,
+ *   (1 + t) / (10 + t)), written as its complement -- t = step (>= 1, by value) or, with step == -1, the step count of the bound
+ *   device step state (the count segmm_step_advance left: that of the step just taken).  shadow and p 16-byte aligned and
+ *   disjoint, any n >= 0 (n % 4 tail included); anything else is refused by name.  (Knob EMA_NT: the shadow's traffic nontemporal; same bits.)
+ * segmm_vec_swap: a[i] <-> b[i] for i < n; 16-byte aligned, disjoint (an overlap is refused by name), any n >= 0. */
+int segmm_ema_update(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream);
+int segmm_vec_swap(float* a, float* b, int64_t n, segmm_stream_t stream);
+
 /* out[i] = a[i] + b[i] (one IEEE fp32 add, nothing contracted), i < n; n >= 0; out may be exactly a or exactly b; any other overlap
  * of out with an operand is refused (nothing is written).  The gradient sum of a micro-batched step (Trainer(micro_batch=m)): 16-byte
  * accesses where the three pointers share their offset from a 16-byte boundary (scalar head and tail), one dword per lane otherwise;

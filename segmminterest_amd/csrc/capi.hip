@@ -110,7 +110,7 @@ static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, 
 // in by -DSEGMM_ATT_PROBE / -DSEGMM_GEMM_PROBE only.
 enum {
     K_ATTN, K_ATT_FWD_PL, K_ATT_FWD_LDS, K_ATT_FWD_KSPLIT, K_ATT_FWD_LDS_PAD, K_ATT_STREAM, K_ATT_FUSED_LAUNCH, K_ATT_MERGE, K_ATT_LDS_PAD, K_ATT_WAVES, K_ATT_WAVES_PL, K_ATT_REPAIR_WALK,
-    K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_DPRE_PLANES_ONLY, K_COUNT
+    K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_DPRE_PLANES_ONLY, K_EMA_NT, K_COUNT
 };
 struct Knob { const char* name; int value; const char* doc; };
 static Knob g_knobs[K_COUNT] = {
@@ -136,6 +136,7 @@ static Knob g_knobs[K_COUNT] = {
     {"TN_VAR", 8, "plane TN GEMM: 8 gemm_pl_tn4 (round 6: 128 x 256 tiles, two workgroups per CU) for few-tile and 128-row matrices, gemm_pl_tn8 (round 3) otherwise; 4 gemm_pl_tn4 wherever it fits; 88 gemm_pl_tn8 wherever it fits; 0: the round-2 fallback kernel for every launch"},
     {"LN_BWD_PARTS", 0, "LayerNorm backward: most workgroups (= partial rows of its column sums) per launch; 0: as many four-wave workgroups as are resident at the row width (768 at d = 768: one full round, no under-occupied tail)"},
     {"DPRE_PLANES_ONLY", 1, "embedding LayerNorm gradients as planes only + repair launch (no fp32 copy): 0 never, 1 for sites on the per-position grid today (rows * d >= 2^23), 2 wherever segmm_layernorm_bwd_pos_parts gives a grid (tests at small shapes), 3 as 1 for the user side only (A/B per site)"},
+    {"EMA_NT", 0, "segmm_ema_update: 0 everything with the default cache policy, 1 the shadow loaded and stored nontemporally (p with the default policy); same bits (A/B: profiles/ema/)"},
 };
 static bool g_knobs_ready = false;
 static void knobs_init() {
@@ -2174,6 +2175,47 @@ int segmm_vec_add(float* out, const float* a, const float* b, int64_t n, segmm_s
         blocks = blocks > cap ? cap : blocks;
         hipLaunchKernelGGL(vec_add_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, a, b, 0, (long long)n, 0);
     }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// shared checks of the two flat two-range kernels below (`who`: the entry point's name in the messages)
+static int flat_pair_check(const char* who, const void* a, const void* b, int64_t n) {
+    SEGMM_REQUIRE(a && b, "%s: null pointer", who);
+    SEGMM_REQUIRE(n >= 0 && n <= (int64_t)1 << 40, "%s: n=%lld (0 .. 2^40)", who, (long long)n);
+    SEGMM_REQUIRE(aligned16(a) && aligned16(b), "%s: pointers must be 16-byte aligned", who);
+    const uintptr_t nb = (uintptr_t)n * 4u, pa = (uintptr_t)a, pb = (uintptr_t)b;
+    SEGMM_REQUIRE(pa + nb <= pb || pb + nb <= pa, "%s: the two ranges overlap (they must be disjoint)", who);
+    return 0;
+}
+static unsigned flat_pair_blocks(long long n4) {
+    const long long cap = (long long)num_cus() * VEC_ADD_WG_PER_CU;          // one round of resident workgroups
+    const long long blocks = (n4 + 255) / 256;
+    return (unsigned)(blocks > cap ? cap : blocks < 1 ? 1 : blocks);
+}
+
+int segmm_ema_update(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream) {
+    if (const int rc = flat_pair_check("ema_update", shadow, p, n)) return rc;
+    SEGMM_REQUIRE(weight > 0.f && weight <= 1.f, "ema_update: weight=%g (0 < weight <= 1; weight = 1 - decay)", (double)weight);
+    SEGMM_REQUIRE(step >= 1 || step == -1, "ema_update: step=%d (>= 1, or -1: the device-side step state)", step);
+    if (n == 0) return 0;
+    const StepState* live = (warmup && step < 0) ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    SEGMM_REQUIRE(!(warmup && step < 0) || live, "ema_update: no device-side step state");
+    const long long n4 = n >> 2;
+    const int tail = (int)(n & 3);
+    if (knob(K_EMA_NT) != 0)
+        hipLaunchKernelGGL(ema_update_kernel<true>, dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
+    else
+        hipLaunchKernelGGL(ema_update_kernel<false>, dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_vec_swap(float* a, float* b, int64_t n, segmm_stream_t stream) {
+    if (const int rc = flat_pair_check("vec_swap", a, b, n)) return rc;
+    if (n == 0) return 0;
+    const long long n4 = n >> 2;
+    hipLaunchKernelGGL(vec_swap_kernel, dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, a, b, n4, (int)(n & 3));
     LAUNCH_CHECK();
     return 0;
 }

@@ -995,6 +995,91 @@ __global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void vec_add_kernel(float* 
     }
 }
 
+// ---------------------------------------------------------------- shadow += (p - shadow) w over a flat range (segmm_ema_update)
+// The weight average of Trainer(ema=...): three IEEE fp32 operations per element (subtract, multiply, add; nothing contracted), 12
+// bytes of traffic per element -- vec_add_kernel's `acc <- acc + g` form, and its shape: one round of resident workgroups, four
+// 16-byte loads of each operand in flight before the first store, then single vectors, the n % 4 tail by workgroup 0.  Both pointers
+// are 16-byte aligned and the ranges disjoint (the entry point refuses anything else), so there is no scalar head and no dword form.
+// w is wave-uniform: the weight, or under warm-up max(weight, fp32(9 / (10 + t))) with t the step by value or `live->step` -- one
+// double division per lane, issued beside the first loads.
+// NT (knob EMA_NT, off by default): the shadow loaded and stored nontemporally, p with the default policy.  The shadow is touched once
+// per step and by nothing else, which is what made nontemporal traffic pay for the row kernels that run BESIDE the GEMMs; this launch
+// runs alone at the end of the step's tail, and measured in the recorded config-2 step the two policies tie within the step's spread,
+// while alone at 4 x the config-2 size the nontemporal form is 6-8 % slower (profiles/ema/): the default policy stays.
+__device__ __forceinline__ float ema_weight(float weight, int warmup, int step, const StepState* live) {
+#pragma clang fp contract(off)
+    if (!warmup) return weight;
+    const int t = live ? live->step : step;
+    const float wt = (float)(9.0 / (10.0 + (double)t));
+    return wt > weight ? wt : weight;
+}
+template <bool NT>
+__device__ __forceinline__ f32x4 ema_ld(const f32x4* q) {
+    if constexpr (NT) return __builtin_nontemporal_load(q);
+    else return *q;
+}
+template <bool NT>
+__device__ __forceinline__ void ema_st(f32x4* q, f32x4 v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, q);
+    else *q = v;
+}
+__device__ __forceinline__ f32x4 ema_lerp(f32x4 s, f32x4 p, float w) {
+#pragma clang fp contract(off)
+    const f32x4 d = p - s;
+    const f32x4 dw = d * w;
+    return s + dw;
+}
+template <bool NT>
+__global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void ema_update_kernel(float* __restrict__ shadow, const float* __restrict__ p, long long n4, int tail,
+                                                                            float weight, int warmup, int step, const StepState* live) {
+#pragma clang fp contract(off)
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    f32x4* s4 = (f32x4*)shadow;
+    const f32x4* p4 = (const f32x4*)p;
+    const float w = ema_weight(weight, warmup, step, live);
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f32x4 s0 = ema_ld<NT>(s4 + i), s1 = ema_ld<NT>(s4 + i + stride), s2 = ema_ld<NT>(s4 + i + 2 * stride), s3 = ema_ld<NT>(s4 + i + 3 * stride);
+        const f32x4 p0 = p4[i], p1 = p4[i + stride], p2 = p4[i + 2 * stride], p3 = p4[i + 3 * stride];
+        ema_st<NT>(s4 + i, ema_lerp(s0, p0, w)); ema_st<NT>(s4 + i + stride, ema_lerp(s1, p1, w));
+        ema_st<NT>(s4 + i + 2 * stride, ema_lerp(s2, p2, w)); ema_st<NT>(s4 + i + 3 * stride, ema_lerp(s3, p3, w));
+    }
+    for (; i < n4; i += stride) ema_st<NT>(s4 + i, ema_lerp(ema_ld<NT>(s4 + i), p4[i], w));
+    if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
+        const long long k = (n4 << 2) + threadIdx.x;
+        const float s = shadow[k];
+        const float d = p[k] - s;
+        const float dw = d * w;
+        shadow[k] = s + dw;
+    }
+}
+
+// ---------------------------------------------------------------- a <-> b over a flat range (segmm_vec_swap)
+// WeightEMA.applied(): the shadow goes into the live range of the flat parameter buffer and back.  16 bytes of traffic per element;
+// the shape of the two kernels above (a lane reads the elements it owns from both ranges before it writes them).
+__global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void vec_swap_kernel(float* __restrict__ a, float* __restrict__ b, long long n4, int tail) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    f32x4 *a4 = (f32x4*)a, *b4 = (f32x4*)b;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f32x4 a0 = a4[i], a1 = a4[i + stride], a2 = a4[i + 2 * stride], a3 = a4[i + 3 * stride];
+        const f32x4 b0 = b4[i], b1 = b4[i + stride], b2 = b4[i + 2 * stride], b3 = b4[i + 3 * stride];
+        a4[i] = b0; a4[i + stride] = b1; a4[i + 2 * stride] = b2; a4[i + 3 * stride] = b3;
+        b4[i] = a0; b4[i + stride] = a1; b4[i + 2 * stride] = a2; b4[i + 3 * stride] = a3;
+    }
+    for (; i < n4; i += stride) {
+        const f32x4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < tail) {
+        const long long k = (n4 << 2) + threadIdx.x;
+        const float x = a[k], y = b[k];
+        a[k] = y;
+        b[k] = x;
+    }
+}
+
 // ---------------------------------------------------------------- CrossMLP ablation: AdaptiveAvgPool1d over tokens
 // out[b, i, :] = mean over t in [floor(i T / bins), ceil((i+1) T / bins)) of cat(U[b], V[b])[t, :], T = Lu + Lv
 // (encoder.py:396,503-506: nn.AdaptiveAvgPool1d(40) over the token axis of the concatenated user and video tokens;

@@ -295,6 +295,34 @@ def vec_add(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor, n=None, out_off
         _check(lib().segmm_vec_add(out.data_ptr() + 4 * out_off, a.data_ptr() + 4 * a_off, b.data_ptr() + 4 * b_off, n, _stream()), "segmm_vec_add")
 
 
+def ema_update(shadow: torch.Tensor, p: torch.Tensor, n, weight, warmup, step, shadow_off=0, p_off=0):
+    """segmm_ema_update: ``shadow[i] += (p[i] - shadow[i]) * w`` for i < n over contiguous float32 tensors (offsets in floats), three
+    rounded fp32 operations per element.  ``w`` = ``weight`` or, with ``warmup``, max(weight, fp32(9 / (10 + t))), t = ``step`` (>= 1)
+    or, with step = -1, the bound device step state's count.  16-byte aligned, disjoint ranges.  A recordable command."""
+    _f32c(shadow, "ema_update: shadow")
+    _f32c(p, "ema_update: p")
+    _dev(shadow, p)
+    n = int(n)
+    if n < 0 or min(shadow_off, p_off) < 0 or shadow_off + n > shadow.numel() or p_off + n > p.numel():
+        raise RuntimeError("ema_update: %d elements from offsets %d / %d do not fit tensors of %d / %d" % (n, shadow_off, p_off, shadow.numel(), p.numel()))
+    with _kprof("ema_update", 12 * n):
+        _check(lib().segmm_ema_update(shadow.data_ptr() + 4 * shadow_off, p.data_ptr() + 4 * p_off, n, float(weight), int(bool(warmup)), int(step),
+                                      _stream()), "segmm_ema_update")
+
+
+def vec_swap(a: torch.Tensor, b: torch.Tensor, n=None, a_off=0, b_off=0):
+    """segmm_vec_swap: ``a[a_off + i] <-> b[b_off + i]`` for i < n (default: all of ``a``) over contiguous float32 tensors; 16-byte
+    aligned, disjoint ranges.  A recordable command."""
+    _f32c(a, "vec_swap: a")
+    _f32c(b, "vec_swap: b")
+    _dev(a, b)
+    n = a.numel() - a_off if n is None else int(n)
+    if n < 0 or min(a_off, b_off) < 0 or a_off + n > a.numel() or b_off + n > b.numel():
+        raise RuntimeError("vec_swap: %d elements from offsets %d / %d do not fit tensors of %d / %d" % (n, a_off, b_off, a.numel(), b.numel()))
+    with _kprof("vec_swap", 16 * n):
+        _check(lib().segmm_vec_swap(a.data_ptr() + 4 * a_off, b.data_ptr() + 4 * b_off, n, _stream()), "segmm_vec_swap")
+
+
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError("%s failed (%d): %s" % (what, rc, _lib_real().segmm_last_error().decode()))

@@ -18,6 +18,7 @@ data parallelism is what this build adds:
 from __future__ import annotations
 
 import argparse
+import contextlib
 import dataclasses
 import fnmatch
 import functools
@@ -339,6 +340,175 @@ class PlateauLR:
         return None
 
 
+EMA_KEYS = ("decay", "warmup")
+
+
+def parse_ema(spec):
+    """``ema=`` of FusedAdamW / Trainer -> ``(decay, warmup)`` or None.  ``spec``: None, a float (the decay) or a dict
+    ``dict(decay=0.999, warmup=True)``; an unknown key, a decay outside 0 <= decay < 1 and a non-bool warmup are refused by name."""
+    if spec is None:
+        return None
+    if isinstance(spec, dict):
+        unknown = [k for k in spec if k not in EMA_KEYS]
+        if unknown:
+            raise ValueError("ema: unknown key %r (an EMA takes %s)" % (unknown[0], ", ".join(EMA_KEYS)))
+        decay, warmup = spec.get("decay", 0.999), spec.get("warmup", True)
+    else:
+        decay, warmup = spec, True
+    if not isinstance(warmup, bool):
+        raise ValueError("ema: warmup must be a bool, not %r" % (warmup,))
+    return _check_ema_decay(decay), warmup
+
+
+def _check_ema_decay(decay):
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:          # (also NaN)
+        raise ValueError("ema: decay must be a float with 0 <= decay < 1, not %r" % (decay,))
+    return float(decay)
+
+
+class WeightEMA:
+    """An exponential moving average of the live parameters, kept on the device and owned by :class:`FusedAdamW`
+    (``Trainer(ema=...)``; ``trainer.ema`` / ``opt.ema``): ``shadow <- shadow + (p - shadow) w`` after every optimizer step, one
+    segmm_ema_update launch over the live range of the flat buffer, issued by ``FusedAdamW.end_step`` -- behind every AdamW launch
+    of the step, whichever path took it (plain, clipped, two-pass id tables, data-parallel buckets, micro-batches: one update per
+    OPTIMIZER step), and part of a recorded step's tail.  w = fp32(1 - decay) (host double); with ``warmup`` the step t runs at
+    max(w, fp32(9 / (10 + t))), i.e. decay_t = min(decay, (1 + t) / (10 + t)), t = the optimizer's step count (the device step
+    state's under ``device_state``: a resumed run continues its warm-up).
+
+    ``shadow``: one float32 tensor of ``n_live`` floats beside ``opt.m`` / ``opt.v``; dead parameters never move and have none,
+    frozen ones keep shadow = p.  It is made with the optimizer's state and SEEDED with the parameters at the head of the first
+    optimizer step, before any of its AdamW launches (the id tables' early pass included) -- not lazily at the first update; read
+    earlier (``applied()``, ``state_dict()`` before any step) it holds the parameters of that moment.  It is RE-SEEDED in the same way
+    from the parameters of the moment whenever the store rebuilds its flat buffer, exactly where ``m`` and ``v`` are zeroed;
+    ``load_state_dict`` replaces the seed.
+    Data parallel: every rank computes the same shadow from its identical parameters, no collective.
+
+    ``applied()``: a context manager that swaps the shadow INTO the live range (segmm_vec_swap) and back out on exit, bumping
+    ``store.fused_version`` both times so that the weight planes are re-split for the averaged weights and again for the trained
+    ones.  While applied, ``train_step`` / ``record`` / ``run_recorded`` are refused, and so is a nested ``applied()``.
+    ``decay`` may be assigned between steps (a recorded step is then refused like after any hyperparameter change)."""
+
+    def __init__(self, opt, decay=0.999, warmup=True):
+        self.opt, self.warmup = opt, bool(warmup)
+        self.decay = decay
+        self.shadow = None
+        self.is_applied = False
+
+    @property
+    def decay(self):
+        return self._decay
+
+    @decay.setter
+    def decay(self, d):
+        self._decay = _check_ema_decay(d)
+
+    @property
+    def weight(self):
+        """The kernel's ``weight``: fp32(1 - decay), the subtraction in double."""
+        return _f32(1.0 - self._decay)
+
+    def hyper(self):
+        return self.weight, self.warmup
+
+    def weight_at(self, t):
+        """w of optimizer step ``t`` as the kernel forms it (a Python float holding an fp32 value)."""
+        return max(self.weight, _f32(9.0 / (10.0 + t))) if self.warmup else self.weight
+
+    def _seed(self, st):
+        """(FusedAdamW._state, where m and v are made) a fresh shadow for the store's live range.  It is FILLED with the parameters at the
+        head of the next optimizer step (:meth:`step_head`) -- and, should anything read it before (``applied()``, ``state_dict()``),
+        with the parameters of that moment, the step head then filling it again: weights loaded into the model between the
+        construction of the optimizer's state and the first step are the ones averaged."""
+        if self.is_applied:
+            raise RuntimeError("ema: the flat parameter buffer was rebuilt inside ema.applied()")
+        self.shadow = torch.empty(st.n_live, dtype=torch.float32, device=st.flat.device)
+        self._pending = True
+
+    def _fill(self, st):
+        H.torch_fallback("seeding the EMA shadow (a step is recorded after the optimizer's first step)")
+        self.shadow.copy_(st.flat[:st.n_live].detach())
+
+    def step_head(self, st):
+        """Head of an optimizer step (FusedAdamW.begin_step, or table_early when the id tables' early pass comes first): a shadow
+        that is still to be seeded takes the parameters as they stand now, before any AdamW launch of the step."""
+        if self.__dict__.get("_pending", False):
+            self._fill(st)
+            self._pending = False
+
+    def _store(self):
+        """The store, with the optimizer's state and a seeded shadow in place."""
+        st = self.opt._state()
+        if self.shadow is None or self.shadow.numel() != st.n_live:
+            raise AssertionError("ema: no shadow for the live range")
+        if self.__dict__.get("_pending", False):
+            self._fill(st)          # (stays pending: the head of the first step seeds it again)
+        return st
+
+    def update(self):
+        """The step's update (FusedAdamW.end_step): one launch on the current stream."""
+        if self.is_applied:
+            raise RuntimeError("ema: an optimizer step inside ema.applied() (the live range holds the averaged weights)")
+        opt = self.opt
+        st = self._store()
+        live = opt.__dict__.get("device_state", False)
+        if live and opt.__dict__.get("_step_state") is not None:
+            H.step_bind(opt._step_state)
+        H.ema_update(self.shadow, st.flat, st.n_live, self.weight, self.warmup, -1 if live else opt.step_count)
+
+    def _swap(self, st):
+        H.vec_swap(st.flat, self.shadow, st.n_live)
+        st.fused_version += 1          # the weight planes follow the live range: ParamStore.ensure() re-splits them
+
+    @contextlib.contextmanager
+    def applied(self):
+        if self.is_applied:
+            raise RuntimeError("ema.applied() is already active (nested applied() is refused)")
+        if H.RECORDER is not None:
+            raise RuntimeError("ema.applied() inside a recorded step")
+        st = self._store()
+        self._swap(st)
+        self.is_applied = True
+        flat_id = st.flat.data_ptr()
+        try:
+            yield self
+        finally:
+            self.is_applied = False
+            if st.flat is None or st.flat.data_ptr() != flat_id:
+                raise RuntimeError("ema.applied(): the flat parameter buffer was rebuilt while the averaged weights were applied; the "
+                                   "trained weights are in ema.shadow")
+            self._swap(st)
+
+    def _refuse_applied(self, who):
+        if self.is_applied:
+            raise RuntimeError("%s inside ema.applied(): the live range holds the averaged weights; leave the context first" % who)
+
+    def state_dict(self):
+        """The model's ``state_dict`` keys and shapes (host tensors): the live parameters from the shadow, everything else (dead
+        parameters, buffers) copied from the model -- what the reference's model loads directly."""
+        self._refuse_applied("ema.state_dict()")
+        st = self._store()
+        out = {k: v.detach().cpu().clone() for k, v in self.opt.model.state_dict().items()}
+        for n in st.live_names:
+            o, k = st.index[n]
+            out[n] = self.shadow[o:o + k].view(st._params[n].shape).cpu().clone()
+        return out
+
+    def load_state_dict(self, sd):
+        """The inverse of :meth:`state_dict`: the live parameters' entries become the shadow (the seed is replaced)."""
+        self._refuse_applied("ema.load_state_dict()")
+        st = self._store()
+        for n in st.live_names:
+            if n not in sd:
+                raise KeyError("ema.load_state_dict: no entry for the parameter %s" % n)
+            if tuple(sd[n].shape) != tuple(st._params[n].shape):
+                raise ValueError("ema.load_state_dict: %s has shape %s, the model's parameter %s"
+                                 % (n, tuple(sd[n].shape), tuple(st._params[n].shape)))
+        for n in st.live_names:
+            o, k = st.index[n]
+            self.shadow[o:o + k].copy_(sd[n].reshape(-1).to(torch.float32))
+        self._pending = False          # the loaded average replaces the seed
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics (lr 1e-3, wd 1e-4, betas (.9,.999), eps 1e-8 at
     main_for_seq_leave_earlystop_SegMM.py:226) as ONE kernel over the contiguous live range of the
@@ -371,11 +541,16 @@ class FusedAdamW:
     the clipping norm (torch: ``grad=None``) and ``state_dict()["state"]`` has no entry for it; its ``.grad`` is still what the
     backward delivers -- the backward's work for frozen parameters is NOT skipped, freezing saves optimizer traffic only.  Dead
     parameters may be listed; they stay untouched as ever.  ``no_decay_groups(model)`` is the usual no-decay recipe,
-    ``group_of(name)`` a parameter's resolved values."""
+    ``group_of(name)`` a parameter's resolved values.
+
+    ``ema`` (None = nothing is launched or allocated; a decay, or ``dict(decay=0.999, warmup=True)``): a :class:`WeightEMA` of the
+    live parameters, ``opt.ema``, updated by ``end_step`` with one launch behind the step's last AdamW launch."""
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None,
-                 param_groups=None):
+                 param_groups=None, ema=None):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
+        ema = parse_ema(ema)
+        self.ema = None if ema is None else WeightEMA(self, *ema)
         # resolved groups (resolve_param_groups; entry 0 = the default group) or None; _segs: their segment table on the device
         self.groups = None if param_groups is None else resolve_param_groups(list(model.named_parameters()), param_groups, weight_decay)
         self._group_idx = None if self.groups is None else {n: gi for gi, G in enumerate(self.groups) for n in G["names"]}
@@ -395,6 +570,8 @@ class FusedAdamW:
             self.v = torch.zeros(st.n_live, device=st.flat.device)
             self._flat_id = st.flat.data_ptr()
             self._segs = None
+            if self.ema is not None:          # (re-)seeded where m and v are zeroed: from the parameters of the moment
+                self.ema._seed(st)
         if self.groups is not None and self._segs is None:
             self._build_segments(st)
         return st
@@ -518,6 +695,8 @@ class FusedAdamW:
         only read the listed rows).  ``step()`` then updates the listed rows and skips the table's range.  Element for element
         the arithmetic of the one-launch dense update."""
         st = self._state()
+        if self.ema is not None:
+            self.ema.step_head(st)          # this pass is the step's first parameter write
         if self._frozen(name):          # nothing to step, now or later: step() walks over the table's range, which the kernel skips
             return
         hyper = None if self.groups is None else self.group_of(name)[:2]
@@ -540,6 +719,8 @@ class FusedAdamW:
     # trainer steps each gradient bucket as soon as ITS all-reduce has completed (begin_step, step_range ..., end_step)
     def begin_step(self, gbuf=None):
         st = self._state()
+        if self.ema is not None:
+            self.ema.step_head(st)
         self.step_count += 1
         if not st.__dict__.get("direct_grads", False):
             self._sync_grads(st)
@@ -583,6 +764,10 @@ class FusedAdamW:
                     self.eps, self.wd, step, p_off=start, coef=self._coef())
 
     def end_step(self):
+        if self.ema is not None:
+            # behind every AdamW launch of this step on this stream; the next step's first parameter write -- phase 0 of a two-pass
+            # id table on the auxiliary stream -- is enqueued behind engine.aux_work's fork from this stream
+            self.ema.update()
         self.model._store.fused_version += 1          # the pre-split weight planes of the GEMM engines are now stale
 
     def state_dict(self):
@@ -903,7 +1088,7 @@ class Trainer:
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
                  feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None,
-                 param_groups=None):
+                 param_groups=None, ema=None):
         self.model = model
         # micro_batch=m: a batch of more than m rows is stepped in ceil(B / m) micro-batches with ONE optimizer step on the whole
         # batch's gradient (train_step / _train_step_micro); None, or m >= the batch's rows: the plain step, launch for launch
@@ -924,7 +1109,9 @@ class Trainer:
         self.feature_table = feature_table
         self.dropout = dropout      # False: run the step in eval mode (deterministic; used by the DP equivalence tests)
         self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
-                              param_groups=param_groups)          # per-group rate scale, decay and freezing: see FusedAdamW
+                              param_groups=param_groups, ema=ema)          # per-group rate scale, decay and freezing: see FusedAdamW
+        # ema=None | decay | dict(decay=0.999, warmup=True): a device-side moving average of the weights (WeightEMA), or None
+        self.ema = self.opt.ema
         self.comm = comm if comm is not None else DPComm()
         self.overlap = overlap
         st = model._store
@@ -1109,6 +1296,8 @@ class Trainer:
             name = pre + "vid_proj.weight"
             if name not in st.index or name not in st.live_names or st._params[name].shape[1] % 4:
                 continue
+            if self.opt.ema is not None:          # the shadow is made and seeded on the main stream, before the early pass moves the table's rows
+                self.opt.ema.step_head(self.opt._state())
             with E.aux_work(st):
                 self.opt.table_early(name, ids.reshape(-1))
 
@@ -1241,6 +1430,8 @@ class Trainer:
         enqueued on a side stream right away (:meth:`prefetch`) and overlaps this step's backward.
         ``Trainer(micro_batch=m)`` and a batch of more than m rows: the step runs in micro-batches (:meth:`_train_step_micro`; nothing
         is prefetched then)."""
+        if self.ema is not None:
+            self.ema._refuse_applied("train_step()")
         if self.micro_batch is not None and batch_rows(batch) > self.micro_batch:
             return self._train_step_micro(batch, self.micro_batch)
         model, st = self.model, self.model._store
@@ -1535,6 +1726,8 @@ class Trainer:
         takes is the recorded one, on ``batch``: what an epoch loop needs (:func:`fit` with ``recorded=True``)."""
         if not self.device_state:
             raise RuntimeError("record() needs Trainer(device_state=True): the per-step state must live on the device")
+        if self.ema is not None:
+            self.ema._refuse_applied("record()")
         model, st = self.model, self.model._store
         if self._param_hooks():
             raise RuntimeError("record(): parameter hooks only fire when the gradients travel through autograd; use train_step")
@@ -1638,7 +1831,9 @@ class Trainer:
     def _hyper(self):
         # under an lr_schedule the recorded commands carry the sentinel, not a rate: the rate may move, the schedule's presence not
         lr = self.opt.lr if self.opt.schedule is None else H.LIVE_LR
-        return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm, self.opt.group_table())
+        # (the recorded segmm_ema_update carries the EMA's weight and warm-up flag by value)
+        return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm, self.opt.group_table(),
+                None if self.ema is None else self.ema.hyper())
 
     def _timed_plan(self, r):
         """The recorded phases cut at every GEMM / attention command (bench.py's timed replay): [("host", fn) | ("run", Phase) |
@@ -1692,6 +1887,8 @@ class Trainer:
         r = self.__dict__.get("_recorded")
         if r is None:
             raise RuntimeError("run_recorded() before record()")
+        if self.ema is not None:
+            self.ema._refuse_applied("run_recorded()")
         H.step_bind(self._step_state)
         if self._hyper() != r["hyper"]:
             # the recorded segmm_adamw / segmm_adamw_table / segmm_grad_norm commands carry lr (without an lr_schedule), weight
@@ -1758,10 +1955,18 @@ class Trainer:
             pos = e
         return pos == st.n_live
 
+    def _ema_scope(self, ema, who):
+        """The context an evaluation entry point runs in: ``ema.applied()`` for ``ema=True`` (refused by name without an EMA)."""
+        if not ema:
+            return contextlib.nullcontext()
+        if self.ema is None:
+            raise ValueError("%s(ema=True) needs Trainer(ema=...): this trainer keeps no weight average" % who)
+        return self.ema.applied()
+
     @torch.no_grad()
     def test_model(self, test_batches, eval_type_list, ckpt: Optional["CheckPointer"] = None, threshold: float = 0.5, top_k_mask: int = 0,
                    top_k_permutation: int = 1, save_logits: bool = False, train_videos: Optional[set] = None, draw_case: int = 0,
-                   device_metrics: bool = False):
+                   device_metrics: bool = False, ema: bool = False):
         """The test phase of the reference trainer (main_for_seq_leave_earlystop_SegMM.py:365-459): reload the BEST checkpoint
         (``ckpt.load_checkpoint(model, optimizer, mode='best')``, :366-367), eval mode, ``mode="inference"`` over the test split,
         interests = sigmoid(logits) * exposure_prob (:402-403), pred_label = interests > threshold (:404), every batch through
@@ -1771,13 +1976,22 @@ class Trainer:
         "cold_count_inter", "hot_count_inter"][, "saved_logits"]}.
         ``device_metrics=True``: the per-row metrics (JaccardSim, LeaveMSE, LeaveCTR, LeaveCTR_view) and the cold / hot split are
         computed and summed on the device (:meth:`_test_model_device`) instead of in the host row loop of ``main_eval_batch``;
-        same keys, plus "extras"."""
+        same keys, plus "extras".
+        ``ema=True`` (needs ``Trainer(ema=...)``): the pass runs on the averaged weights (``ema.applied()``); a checkpoint's
+        ``"model_ema"`` entry is restored into the EMA first."""
+        scope = self._ema_scope(ema, "test_model")
+        if ckpt is not None:
+            load_dict = ckpt.load_checkpoint(self.model, self.opt, mode="best", **({"ema": self.ema} if ema else {}))
+            self.model.load_state_dict(load_dict["model"])
+        with scope:
+            return self._test_model(test_batches, eval_type_list, threshold, top_k_mask, top_k_permutation, save_logits, train_videos, draw_case,
+                                    device_metrics)
+
+    def _test_model(self, test_batches, eval_type_list, threshold, top_k_mask, top_k_permutation, save_logits, train_videos, draw_case,
+                    device_metrics):
         import argparse
         from .my_evaluation import main_eval_batch
         model = self.model
-        if ckpt is not None:
-            load_dict = ckpt.load_checkpoint(model, self.opt, mode="best")
-            model.load_state_dict(load_dict["model"])
         model.eval()
         margs = argparse.Namespace(TOP_K_mask=top_k_mask, TOP_K_permutation=top_k_permutation, draw_case=draw_case)
         if device_metrics:
@@ -1906,31 +2120,38 @@ class Trainer:
                      vid_id=batch["photo_identity_id"], vid_mask=vm, gt=batch["label"], mode=mode)
 
     @torch.no_grad()
-    def dump_logits(self, splits, store=None):
+    def dump_logits(self, splits, store=None, ema: bool = False):
         """The dump loop of the reference's inference script (inference/save_logits_for_all_leave_SegMM.py:105-146): eval mode,
         ``mode="inference"`` over every batch of every split in order, ``test_logits["<user_id>-<photo_id>-<time_ms>"] = logits`` --
         into a :class:`bridge.DeviceLogitStore`, so the logits stay on the device and no batch synchronises with the host.  ``splits``:
-        an iterable of batch iterables (train, valid, test; ``DeviceBatches`` yields the three key columns on the device)."""
+        an iterable of batch iterables (train, valid, test; ``DeviceBatches`` yields the three key columns on the device).
+        ``ema=True`` (needs ``Trainer(ema=...)``): the logits of the averaged weights (``ema.applied()``)."""
         from .bridge import DeviceLogitStore
-        for batches in splits:
-            for batch in batches:
-                logits = self.eval_step(batch, mode="inference")["logits"]
-                if store is None:
-                    store = DeviceLogitStore(S=logits.shape[1], device=logits.device)
-                store.add_batch(batch["user_id"], batch["photo_id"], batch["time_ms"], logits)
+        with self._ema_scope(ema, "dump_logits"):
+            for batches in splits:
+                for batch in batches:
+                    logits = self.eval_step(batch, mode="inference")["logits"]
+                    if store is None:
+                        store = DeviceLogitStore(S=logits.shape[1], device=logits.device)
+                    store.add_batch(batch["user_id"], batch["photo_id"], batch["time_ms"], logits)
         if store is None:
             store = DeviceLogitStore(device=next(self.model.parameters()).device)
         return store
 
     @torch.no_grad()
     def valid_model(self, batches, metrics=("valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"),
-                    permutation=1, top_k_mask=False, recorded=False, seed=None):
+                    permutation=1, top_k_mask=False, recorded=False, seed=None, ema=False):
         """``valid_model`` of the reference trainer (main_for_seq_leave_earlystop_SegMM.py:132-186): eval-mode forward
         with ``mode="train"`` (loss + logits), interests = sigmoid(logits) * exposure_prob, leave-rank metrics per batch,
         mean over batches.  The ranks are computed on the device (csrc/evalops.h); only B integers per batch reach the
         host instead of the [B, S] interests, labels and masks.
         ``recorded=True`` (opt-in; single process): the pass never waits for the host between batches -- :meth:`valid_enqueue`
-        followed by ``finish()`` of the accumulator it returns; ``seed``: the seed of the pass's candidate shuffles (see there)."""
+        followed by ``finish()`` of the accumulator it returns; ``seed``: the seed of the pass's candidate shuffles (see there).
+        ``ema=True`` (needs ``Trainer(ema=...)``): the pass, eager or recorded, runs on the averaged weights (``ema.applied()``: the
+        weight planes are re-split for them at the head of the pass and for the trained weights at the next step)."""
+        if ema:
+            with self._ema_scope(ema, "valid_model"):
+                return self.valid_model(batches, metrics=metrics, permutation=permutation, top_k_mask=top_k_mask, recorded=recorded, seed=seed)
         if recorded:
             return self.valid_enqueue(batches, metrics=metrics, permutation=permutation, top_k_mask=top_k_mask, seed=seed).finish()
         from .my_evaluation import TOP_K_leave_device
@@ -2164,7 +2385,7 @@ def compute_final_result(results_list):
 def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_step: int = 30, early_stop: int = 0,
         main_metric: str = "NDCG@5", ckpt: Optional["CheckPointer"] = None, logging_step: int = 0, log=None,
         permutation: int = 1, top_k_mask: bool = False, metrics=None, recorded: bool = False, eager_steps: int = 3,
-        lr_plateau: Optional[dict] = None, recorded_valid: bool = False):
+        lr_plateau: Optional[dict] = None, recorded_valid: bool = False, ema_valid: bool = False):
     """The train / validate / checkpoint / early-stop loop of the reference trainer around ``Trainer.train_step``
     (main_for_seq_leave_earlystop_SegMM.py:247-354): one validation over ``valid_batches`` BEFORE training, then per epoch every
     ``valid_step`` local steps a validation whose ``main_metric`` (mean over the validation batches, :179-181) drives
@@ -2183,6 +2404,9 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
     ``recorded_valid=True`` (independent of ``recorded``; single process): every validation of the loop goes through
     ``Trainer.valid_model(recorded=True)`` -- no host round trip between its batches, one read-back per validation; with
     ``permutation=0`` the history equals the eager validations' exactly, with ``permutation=1`` the shuffles come from the device.
+    ``ema_valid=True`` (needs ``Trainer(ema=...)``): every validation of the loop runs on the averaged weights
+    (``valid_model(ema=True)``), so the best checkpoint, early stopping and ``lr_plateau`` follow them.  With an EMA every checkpoint
+    carries the average as ``"model_ema"`` (beside ``"model"``, the trained weights), whatever ``ema_valid`` says.
     Returns the history dict the reference calls ``total_valid_loss_metrics`` (+ "stopped_epoch", "global_step")."""
     metrics = list(metrics) if metrics is not None else ["valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"]
     hist: Dict[str, list] = {"train_loss": [0.0]}
@@ -2191,13 +2415,15 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
 
     def validate():
         vm = trainer.valid_model(valid_batches, metrics=tuple(metrics), permutation=permutation, top_k_mask=top_k_mask,
-                                 **({"recorded": True} if recorded_valid else {}))
+                                 **({"recorded": True} if recorded_valid else {}), **({"ema": True} if ema_valid else {}))
         for k in metrics:
             hist[k].append(vm[k])
         return vm
 
     if recorded and not trainer.device_state:
         raise RuntimeError("fit(recorded=True) needs Trainer(device_state=True)")
+    if ema_valid and trainer.ema is None:
+        raise ValueError("fit(ema_valid=True) needs Trainer(ema=...): this trainer keeps no weight average")
     plateau = None
     if lr_plateau is not None:
         if not isinstance(lr_plateau, dict):
@@ -2250,7 +2476,8 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
                 if log is not None:
                     log("Valid_loss: %s, %s: %s, Global_step: %d" % (hist["valid_loss"][-1] if "valid_loss" in hist else None, main_metric, avg, global_step))
                 if ckpt is not None and trainer.comm.rank == 0:
-                    ckpt.save_checkpoint(model=trainer.model, optimizer=trainer.opt, num_epochs=epoch, metric_vals={"main_metric": avg})
+                    ckpt.save_checkpoint(model=trainer.model, optimizer=trainer.opt, num_epochs=epoch, metric_vals={"main_metric": avg},
+                                         **({"ema": trainer.ema} if trainer.ema is not None else {}))
                 if early_stop_reached(hist[main_metric], early_stop):
                     stop, stopped_epoch = True, epoch
                     break
@@ -2277,11 +2504,14 @@ class CheckPointer:
             return True
         return new < orig if self.mode == "min" else new > orig
 
-    def save_checkpoint(self, model, optimizer, num_epochs, metric_vals=None, **_):
+    def save_checkpoint(self, model, optimizer, num_epochs, metric_vals=None, ema=None, **_):
+        """``ema`` (a :class:`WeightEMA`): one more key, ``"model_ema"`` = ``ema.state_dict()`` -- the model's own keys and shapes."""
         import glob
         import os
         sd = dict(model={k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
                   optimizer=optimizer.state_dict(), num_epochs=num_epochs, metrics=metric_vals)
+        if ema is not None:
+            sd["model_ema"] = ema.state_dict()
         torch.save(sd, self.ckpt_latest)
         if metric_vals and self.better(metric_vals[self.monitor], self.best_metric):
             self.best_metric = metric_vals[self.monitor]
@@ -2291,11 +2521,17 @@ class CheckPointer:
             return True
         return False
 
-    def load_checkpoint(self, model, optimizer, mode="latest", **_):
+    def load_checkpoint(self, model, optimizer, mode="latest", ema=None, **_):
+        """``ema`` (a :class:`WeightEMA`): restored from the file's ``"model_ema"``; a file without that key is refused by name
+        (before anything is loaded).  Without ``ema`` the key is ignored and any file loads as ever."""
         import glob
         fn = self.ckpt_latest if mode == "latest" else glob.glob(self.ckpt_best.format("*", "*"))[0]
         sd = torch.load(fn, map_location="cpu", weights_only=False)
+        if ema is not None and "model_ema" not in sd:
+            raise KeyError("load_checkpoint(ema=...): %s has no \"model_ema\" entry (it was written without an EMA)" % fn)
         model.load_state_dict(sd["model"])
         if optimizer is not None:
             optimizer.load_state_dict(sd["optimizer"])
+        if ema is not None:
+            ema.load_state_dict(sd["model_ema"])          # (after the optimizer: its state, and with it the shadow, exists now)
         return sd
