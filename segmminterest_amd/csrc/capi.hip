@@ -110,7 +110,7 @@ static int attn_fill(AttnArgs& a, int B, int H, int dh, int Lq, int La, int Lb, 
 // in by -DSEGMM_ATT_PROBE / -DSEGMM_GEMM_PROBE only.
 enum {
     K_ATTN, K_ATT_FWD_PL, K_ATT_FWD_LDS, K_ATT_FWD_KSPLIT, K_ATT_FWD_LDS_PAD, K_ATT_STREAM, K_ATT_FUSED_LAUNCH, K_ATT_MERGE, K_ATT_LDS_PAD, K_ATT_WAVES, K_ATT_WAVES_PL, K_ATT_REPAIR_WALK,
-    K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_DPRE_PLANES_ONLY, K_EMA_NT, K_COUNT
+    K_ATT_HPB_FWD, K_ATT_HPB_DQ, K_ATT_HPB_DKV, K_L1NORM_REG, K_GEMM_BN, K_PL_VAR, K_PL_NJ, K_TN_VAR, K_LN_BWD_PARTS, K_DPRE_PLANES_ONLY, K_EMA_NT, K_LN_FWD_PARTS, K_COUNT
 };
 struct Knob { const char* name; int value; const char* doc; };
 static Knob g_knobs[K_COUNT] = {
@@ -137,6 +137,7 @@ static Knob g_knobs[K_COUNT] = {
     {"LN_BWD_PARTS", 0, "LayerNorm backward: most workgroups (= partial rows of its column sums) per launch; 0: as many four-wave workgroups as are resident at the row width (768 at d = 768: one full round, no under-occupied tail)"},
     {"DPRE_PLANES_ONLY", 1, "embedding LayerNorm gradients as planes only + repair launch (no fp32 copy): 0 never, 1 for sites on the per-position grid today (rows * d >= 2^23), 2 wherever segmm_layernorm_bwd_pos_parts gives a grid (tests at small shapes), 3 as 1 for the user side only (A/B per site)"},
     {"EMA_NT", 0, "segmm_ema_update: 0 everything with the default cache policy, 1 the shadow loaded and stored nontemporally (p with the default policy); same bits (A/B: profiles/ema/)"},
+    {"LN_FWD_PARTS", 0, "LayerNorm forward (d <= 1024): 0 one round of resident workgroups whose waves walk rows, grid by row width; 1 the one-wave-per-row form; 2 and up: that many workgroups in the walking form, clamped to 64..4096; same bits (A/B: profiles/row_stream/)"},
 };
 static bool g_knobs_ready = false;
 static void knobs_init() {
@@ -1091,6 +1092,21 @@ int segmm_split3_transpose(const float* x, int R, int Cc, int ld, uint16_t* plan
     return 0;
 }
 
+// Workgroups of a LayerNorm-forward launch in the row-walking form (layernorm_fwd_walk_kernel<V, DOT>): ONE round of the four-wave
+// workgroups that are resident at the row width -- 256 CUs x the waves per SIMD the instance's registers allow (the compiler's
+// report, profiles/row_stream/resource_usage.txt: 8 / 6 / 5 / 4 for V = 1 / 2 / 3 / 4, and 8 / 5 / 4 / 4 for the DOT instances, which
+// hold the head weight as well; tests/test_row_stream_cpu.py holds this table against that file).  0: the one-wave-per-row form
+// (layernorm_fwd_kernel<V>) -- rows wider than 1024 (V = 8 keeps it: with a second row of 32 registers beside gamma and beta the
+// instance needs all 256 VGPRs and spills into the AGPRs, one wave per SIMD), or knob LN_FWD_PARTS = 1.
+// The knob is clamped, and no caller sizes a buffer by this grid (the maxima slots are keyed by row, as before).
+static int ln_fwd_cap(int d, bool dot) {
+    const int k = knob(K_LN_FWD_PARTS);
+    if (k == 1 || d > 1024) return 0;
+    if (k >= 2) return k < 64 ? 64 : k > 4096 ? 4096 : k;
+    if (dot) return d <= 256 ? 2048 : d <= 512 ? 1280 : 1024;
+    return d <= 256 ? 2048 : d <= 512 ? 1536 : d <= 768 ? 1280 : 1024;
+}
+
 static int ln_fwd_launch(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                          int64_t rows, int d, float eps, float drop_p, uint64_t seed, uint32_t site, float* amax,
                          uint16_t* planes, int ld2, float* hdr, const float* scale_in, const float* dot_w, const float* dot_b, float* dot_out,
@@ -1101,11 +1117,25 @@ static int ln_fwd_launch(const float* x, const float* gamma, const float* beta, 
     SEGMM_REQUIRE(d > 0 && d % 4 == 0 && d <= 256 * ROW_MAXV, "layernorm_fwd: d=%d unsupported", d);
     SEGMM_REQUIRE(aligned16(x) && (!y || aligned16(y)) && aligned16(gamma) && aligned16(beta), "layernorm_fwd: alignment");
     if (rows <= 0) return 0;
-    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    const int64_t per_row = (rows + 3) / 4;          // workgroups of the one-wave-per-row form
+    const int cap = ln_fwd_cap(d, dot_w != nullptr);
+    const dim3 block(256);
     const DropCfg dc = make_drop(drop_p, seed, site);
-#define LNF(V) hipLaunchKernelGGL((layernorm_fwd_kernel<V>), grid, block, 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, (long long)rows, d, eps, dc, amax, plane_out(planes, ld2, hdr, scale_in), dot_w, dot_b, dot_out)
-    if (d <= 256) LNF(1); else if (d <= 512) LNF(2); else if (d <= 768) LNF(3); else if (d <= 1024) LNF(4); else LNF(8);
+#define LNF_ARGS x, gamma, beta, y, mean, rstd, (long long)rows, d, eps, dc, amax, plane_out(planes, ld2, hdr, scale_in), dot_w, dot_b, dot_out
+    if (cap == 0) {          // one wave per row, then exit: d > 1024, or knob LN_FWD_PARTS = 1
+        const dim3 grid((unsigned)per_row);
+#define LNF(V) hipLaunchKernelGGL((layernorm_fwd_kernel<V>), grid, block, 0, (hipStream_t)stream, LNF_ARGS)
+        if (d <= 256) LNF(1); else if (d <= 512) LNF(2); else if (d <= 768) LNF(3); else if (d <= 1024) LNF(4); else LNF(8);
 #undef LNF
+    } else {                 // one round of resident workgroups whose waves walk rows
+        const dim3 grid((unsigned)(per_row < cap ? per_row : cap));
+#define LNW_(V, DOT) hipLaunchKernelGGL((layernorm_fwd_walk_kernel<V, DOT>), grid, block, 0, (hipStream_t)stream, LNF_ARGS)
+#define LNW(V) do { if (dot_w) LNW_(V, true); else LNW_(V, false); } while (0)
+        if (d <= 256) LNW(1); else if (d <= 512) LNW(2); else if (d <= 768) LNW(3); else LNW(4);
+#undef LNW
+#undef LNW_
+    }
+#undef LNF_ARGS
     LAUNCH_CHECK();
     return 0;
 }

@@ -216,6 +216,113 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     plane_finish(po, amax, am, (unsigned)row, ps, row == 0 && lane == 0);
 }
 
+// The same as ONE ROUND of resident workgroups whose waves WALK rows (wave w of W takes rows w, w + W, ...: the launch form of
+// layernorm_bwd_kernel).  The loads of a wave's NEXT row are issued before the two reductions of the current one (one more row of
+// registers), so a wave always has a row in flight while it reduces and stores; gamma, beta, the head weight (DOT) and the planes-only
+// scale are the same for every row and are fetched once per wave.  Per row the arithmetic is layernorm_fwd_kernel's, expression for
+// expression: the lane-to-column map, the summation orders, o, the dropout index, the plane stores, and the maxima in the slots
+// that one plane_finish per row with the row as key leaves them in (see one_slot) -- every output is bit for bit that kernel's.
+template <int V, bool DOT>
+__global__ __launch_bounds__(256) void layernorm_fwd_walk_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                     const float* __restrict__ beta, float* __restrict__ y, float* mean_out,
+                                     float* rstd_out, long long rows, int d, float eps, DropCfg drop, float* amax, PlaneOut po,
+                                     const float* __restrict__ dot_w, const float* __restrict__ dot_b, float* __restrict__ dot_out) {
+    drop = drop_live(drop);
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * (blockDim.x >> 6);
+    long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    f32x4 nx[V];                      // the next row of this wave, in flight
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const int c = lane * 4 + i * 256;
+        nx[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < d) nx[i] = ld_row4(x + row * d + c);
+    }
+    f32x4 gmv[V], btv[V], dw[DOT ? V : 1];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const int c = lane * 4 + i * 256;
+        gmv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; btv[i] = gmv[i];
+        if (DOT) dw[i] = gmv[i];
+        if (c < d) {
+            gmv[i] = *(const f32x4*)(gamma + c); btv[i] = *(const f32x4*)(beta + c);
+            if (DOT) dw[i] = *(const f32x4*)(dot_w + c);
+        }
+    }
+    float ps = plane_scale(po);
+    if (y == nullptr) {               // planes only: the scale of the output's bound (layernorm_fwd_kernel), the same for every row
+        float gm = 0.f, bm = 0.f;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const int c = lane * 4 + i * 256;
+            if (c < d) { gm = absmax4(gm, gmv[i]); bm = absmax4(bm, btv[i]); }
+        }
+        ps = f16_scale_of((wave_max(gm) * sqrtf((float)d) + wave_max(bm)) * drop.scale);
+    }
+    float db = 0.f;
+    if (DOT && dot_b) db = dot_b[0];
+    // The maxima: a row's maximum goes to slot row % AMAX_SLOTS.  Where the wave stride is a multiple of AMAX_SLOTS (every default
+    // grid is a multiple of 64 workgroups) all rows of a wave share ONE slot, and the wave keeps a running maximum and commits it once,
+    // keyed by its first row: max is exact and order-free, the overflow flag is monotone in it, and the wave of row 0 still writes the
+    // scale -- the header and the slots end up with the bits of one commit per row, at one atomic per wave instead of one per row.
+    const bool one_slot = (stride & (AMAX_SLOTS - 1)) == 0 || row + stride >= rows;          // (wave-uniform)
+    const long long row0 = row;
+    float am = 0.f;
+    for (; row < rows; row += stride) {
+        f32x4 v[V];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const int c = lane * 4 + i * 256;
+            v[i] = nx[i];
+            if (c < d) s += v[i].x + v[i].y + v[i].z + v[i].w;
+        }
+        if (row + stride < rows) {          // (wave-uniform) the next row's loads go out before this row's reductions
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const int c = lane * 4 + i * 256;
+                if (c < d) nx[i] = ld_row4(x + (row + stride) * d + c);
+            }
+        }
+        const float mean = wave_sum(s) / d;
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const int c = lane * 4 + i * 256;
+            if (c < d) {
+                const f32x4 t = v[i] - mean;
+                q += t.x * t.x + t.y * t.y + t.z * t.z + t.w * t.w;
+            }
+        }
+        const float rstd = rsqrtf(wave_sum(q) / d + eps);
+        if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+        float dsum = 0.f;
+        if (!one_slot) am = 0.f;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const int c = lane * 4 + i * 256;
+            if (c < d) {
+                f32x4 o = (v[i] - mean) * rstd * gmv[i] + btv[i];
+                if (drop.p > 0.f) o = drop_apply4(drop, ((uint64_t)row * d + c) >> 2, o);
+                if (y) st_row4(y + row * d + c, o);
+                if (ps > 0.f) plane_store4_pair(po.p, po.ld2, row, c, o, ps);
+                am = absmax4(am, o);
+                if (DOT) {
+                    const f32x4 b = dw[i];
+                    dsum += o.x * b.x + o.y * b.y + o.z * b.z + o.w * b.w;
+                }
+            }
+        }
+        if (DOT) {
+            dsum = wave_sum(dsum);
+            if (lane == 0) dot_out[row] = dot_b ? dsum + db : dsum;
+        }
+        if (!one_slot) plane_finish(po, amax, am, (unsigned)row, ps, row == 0 && lane == 0);
+    }
+    if (one_slot) plane_finish(po, amax, am, (unsigned)row0, ps, row0 == 0 && lane == 0);
+}
+
 // ---------------------------------------------------------------- LayerNorm backward
 // dy_eff = dy (.) dropmask (if the forward dropped y);  dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)).
 // Outputs: dx; optionally dx_drop = dx (.) dropmask2 (the gradient that continues through the
@@ -327,6 +434,39 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- column sums (bias grads, head weight grad)
+// One thread's walk of the column sums below: acc += p[r * pitch] for r = r, r + step, ... < r1 (w: each row times w[r] first), added in
+// ROW ORDER into the one accumulator.  Only the loads are batched: COLSUM_INFLIGHT of them are issued before the dependent adds (one
+// dependent load per add left a thread waiting a full memory round trip per row: 1.3 TB/s on the head's weight gradient), then a
+// remainder loop.  Contraction is off: the product with w[r] is rounded before the add, whatever the unrolled body would let the
+// compiler fuse -- bit for bit the plain loop "v = load; v *= w[r]; acc += v".
+constexpr int COLSUM_INFLIGHT = 8;
+template <bool NT>
+__device__ __forceinline__ f32x4 colsum_ld(const float* p) { return NT ? ld_row4b(p) : *(const f32x4*)p; }
+template <bool NT>
+__device__ __forceinline__ f32x4 colsum_walk(const float* __restrict__ p, size_t pitch, const float* __restrict__ w, long long r, long long r1,
+                                             long long step, f32x4 acc) {
+#pragma clang fp contract(off)
+    for (; r + (COLSUM_INFLIGHT - 1) * step < r1; r += COLSUM_INFLIGHT * step) {
+        f32x4 v[COLSUM_INFLIGHT];
+#pragma unroll
+        for (int k = 0; k < COLSUM_INFLIGHT; ++k) v[k] = colsum_ld<NT>(p + (size_t)(r + k * step) * pitch);
+        if (w) {
+            float wk[COLSUM_INFLIGHT];
+#pragma unroll
+            for (int k = 0; k < COLSUM_INFLIGHT; ++k) wk[k] = w[r + k * step];
+#pragma unroll
+            for (int k = 0; k < COLSUM_INFLIGHT; ++k) v[k] *= wk[k];
+        }
+#pragma unroll
+        for (int k = 0; k < COLSUM_INFLIGHT; ++k) acc += v[k];
+    }
+    for (; r < r1; r += step) {
+        f32x4 v = colsum_ld<NT>(p + (size_t)r * pitch);
+        if (w) v *= w[r];
+        acc += v;
+    }
+    return acc;
+}
 // partial[chunk][n] = sum over the chunk's rows of w[m] * X[m][n]   (w optional)
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ X, int ld, const float* __restrict__ w, long long M,
                                       int N, float* __restrict__ partial, int rows_per_chunk) {
@@ -336,13 +476,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     const long long r0 = (long long)blockIdx.y * rows_per_chunk;
     const long long r1 = min(M, r0 + rows_per_chunk);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (n < N) {
-        for (long long r = r0 + ty; r < r1; r += 4) {
-            f32x4 v = ld_row4b(X + r * ld + n);
-            if (w) v *= w[r];
-            acc += v;
-        }
-    }
+    if (n < N) acc = colsum_walk<true>(X + n, (size_t)ld, w, r0 + ty, r1, 4, acc);
     red[ty][tx] = acc;
     __syncthreads();
     if (ty == 0 && n < N) {
@@ -358,8 +492,7 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int n = (blockIdx.x * 64 + tx) * 4;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (n < N)
-        for (int p = ty; p < P; p += 4) acc += *(const f32x4*)(partial + (size_t)p * N + n);
+    if (n < N) acc = colsum_walk<false>(partial + n, (size_t)N, nullptr, ty, P, 4, acc);
     red[ty][tx] = acc;
     __syncthreads();
     if (ty == 0 && n < N) {
@@ -382,8 +515,7 @@ __global__ __launch_bounds__(256) void colsum_partial3_kernel(Colsum3 a, int ld,
     const long long r0 = (long long)blockIdx.y * rows_per_chunk;
     const long long r1 = min(M, r0 + rows_per_chunk);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (n < N)
-        for (long long r = r0 + ty; r < r1; r += 4) acc += ld_row4b(X + r * ld + n);
+    if (n < N) acc = colsum_walk<true>(X + n, (size_t)ld, nullptr, r0 + ty, r1, 4, acc);
     red[ty][tx] = acc;
     __syncthreads();
     if (ty == 0 && n < N)
@@ -395,8 +527,7 @@ __global__ __launch_bounds__(256) void colsum_final3_kernel(const float* __restr
     const int n = (blockIdx.x * 64 + tx) * 4;
     const float* part = partial + (size_t)blockIdx.z * P * N;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (n < N)
-        for (int p = ty; p < P; p += 4) acc += *(const f32x4*)(part + (size_t)p * N + n);
+    if (n < N) acc = colsum_walk<false>(part + n, (size_t)N, nullptr, ty, P, 4, acc);
     red[ty][tx] = acc;
     __syncthreads();
     if (ty == 0 && n < N) *(f32x4*)(a.out[blockIdx.z] + n) = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
@@ -411,8 +542,7 @@ __global__ __launch_bounds__(256) void colsum_pos_kernel(const float* __restrict
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int n = (blockIdx.x * 16 + tx) * 4, s_ = blockIdx.y;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (n < N)
-        for (long long p_ = s_ + (long long)period * ty; p_ < P; p_ += 16ll * period) acc += *(const f32x4*)(part + (size_t)p_ * N + n);
+    if (n < N) acc = colsum_walk<false>(part + n, (size_t)N, nullptr, s_ + (long long)period * ty, P, 16ll * period, acc);
     red[ty][tx] = acc;
     __syncthreads();
     if (ty == 0 && n < N) {
