@@ -536,7 +536,7 @@ def test_recorded_step_equals_eager_device_state_step(kind, N, B, S, Lt, D, h):
 
 @pytest.mark.gpu
 def test_timed_replay_labels_the_launches_like_the_eager_step():
-    """bench.py's roofline pass labels a launch of the timed replay from the recorded command's arguments (Trainer._timed_plan:
+    """bench.py's roofline pass labels a launch of the timed replay from the recorded command's arguments (recording.timed_plan:
     found by the header's parameter names), the eager step from the wrapper's own (hipabi.GEMM_PROFILE / ATTN_PROFILE).  The
     recording IS an eager step and both skip the GEMM repair launches, so the two label lists are equal, in order."""
     import torch

@@ -210,6 +210,7 @@ def test_fit_recorded_chooses_the_step_mode_per_batch():
     """fit(recorded=True): eager for the first ``eager_steps`` batches, ONE recording step (with the previous batch, so that no extra
     optimisation step is taken), replays for batches of the recorded shapes, the eager step for a batch of another shape -- and every
     batch exactly once, in order.  (Host logic only: a stand-in trainer notes what is called.)"""
+    from segmminterest_amd.recording import batch_shapes
     from segmminterest_amd.trainer import fit
 
     class _Comm:
@@ -233,7 +234,7 @@ def test_fit_recorded_chooses_the_step_mode_per_batch():
 
         def record(self, b, prev_batch=None):
             assert prev_batch is not None and prev_batch is not b
-            self._recorded = {"spans": {k: (tuple(v.shape), v.dtype) for k, v in b.items()}}
+            self._recorded = {"spans": batch_shapes(b)}
             return self._out("record", b)
 
         def run_recorded(self, b):
