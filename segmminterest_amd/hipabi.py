@@ -622,8 +622,16 @@ def step_state_bytes():
 
 def step_bind(state):
     """``segmm_step_bind``: the device-side step state (a caller-owned device tensor of step_state_bytes() bytes, or None: the
-    library's own default state) that the launches which follow use -- the pointer travels in their arguments."""
+    library's own default state) that the launches which follow use -- the pointer travels in their arguments.
+    The library holds the bare pointer, so the tensor is kept alive here for as long as it is bound: an owner that goes away
+    without unbinding (a trainer that is dropped) must not hand the block back to the allocator, where the next tensor of that
+    size would take it and ``step_set`` / a live dropout seed of a later caller would write and read somebody else's data."""
+    global _STEP_BOUND
     _check(_lib_real().segmm_step_bind(None if state is None else state.data_ptr()), "segmm_step_bind")
+    _STEP_BOUND = state
+
+
+_STEP_BOUND = None          # the tensor behind the library's bound step-state pointer (None: the library's default state)
 
 
 def step_set(seed, step, beta1=0.9, beta2=0.999):

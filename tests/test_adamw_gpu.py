@@ -297,6 +297,31 @@ def test_step_state_bias_corrections(own_step_state, betas):
         assert step == step2 == t + 7 and bc == bc2, (t, bc, bc2)
 
 
+def test_a_bound_step_state_outlives_its_owner():
+    """The library holds the bare pointer of the bound state.  An owner that is dropped while its state is still bound (a trainer
+    at the end of a test) must not hand the block back to the allocator: the next tensors of that size would take it, and a later
+    caller's step_set / live dropout seed would write and read their data -- wrong dropout masks in whatever runs next with a live
+    seed.  hipabi.step_bind keeps the tensor alive until something else is bound."""
+    H = _H()
+    n = (H.step_state_bytes() + 3) // 4
+    seed = 0x0BAD_C0DE_F00D_FACE
+    state = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ptr = state.data_ptr()
+    H.step_bind(state)
+    try:
+        H.step_set(seed, 5)
+        torch.cuda.synchronize()
+        del state
+        junk = [torch.full((n,), -1, dtype=torch.int32, device=DEV) for _ in range(8)]      # (a freed block of this size would be reused at once)
+        assert all(j.data_ptr() != ptr for j in junk)
+        torch.cuda.synchronize()
+        got, step, _ = H.step_get()
+        assert (got, step) == (seed, 5)
+    finally:
+        H.step_bind(None)
+    assert H._STEP_BOUND is None
+
+
 @pytest.mark.parametrize("t", [1, 2, 10, 1000])
 def test_adamw_with_device_step_state(own_step_state, t):
     """segmm_adamw(step = -1) after step_set(t) against segmm_adamw(step = t): bit-identical whenever step_get returned the host's

@@ -719,14 +719,20 @@ def test_attention_bwd_on_input_planes_is_independent_of_the_wave_count(request)
         assert torch.equal(dYv, outs[0][0]) and torch.equal(dYu, outs[0][1])
 
 
-def _attn_bwd_repair_protocol(H, B, H_, dh, Lq, La, Lb, bad, seed, with_pin):
+def _attn_bwd_repair_protocol(H, B, H_, dh, Lq, La, Lb, bad, seed, with_pin, carry=None):
     """The planes-only protocol of a fused attention backward at the op level: an fp32 run, a planes-only run whose delayed scales
     are ``bad`` times the fitting ones, segmm_site_fixup, the REPAIR launch.  bad != 1 (overflow / below the fp16 window): the
     repair must leave exactly the planes of the fp32 gradients under the exact scale of their maxima, and that scale in the
     headers.  bad == 1: site_fixup finds nothing and the repair launch changes nothing -- shown on planes overwritten with a
     pattern in between, which a repair pass that ran would replace.  The fp32 buffers handed to the planes-only launches stay zero.
     ``with_pin``: Q / K / V as input planes and no fp32 views in the planes-only launches (the planes-in kernel); Lq != La: the
-    queries are a tensor, a plane buffer and a site of their own."""
+    queries are a tensor, a plane buffer and a site of their own.
+    ``carry`` ('a' or 'b'): the key block the wide kernel takes in two passes (more than 8 tiles).  Its fp32 dQ slice -- rows
+    [0, B Lq), the d columns of dQa or dQb -- is the one place of the fp32 buffers such a launch may write: the first pass leaves a
+    chunk's partial sum there for the second, and the last pass stores planes and maxima only (csrc/attention_wide.h).  What the
+    slice holds afterwards is the sum over the FIRST pass's 8 tiles in the kernel's own order, and it is held to that exactly:
+    against an fp32 phase 5 / 6 run of the same kernel on the same saved O and lse whose key mask ends after 128 keys -- a masked key
+    has dS = 0 exactly, so that run's second pass adds zeros to the same first-pass sum.  Every other fp32 word stays zero."""
     p = 0.1
     d = H_ * dh
     g = torch.Generator().manual_seed(seed)
@@ -797,6 +803,19 @@ def _attn_bwd_repair_protocol(H, B, H_, dh, Lq, La, Lb, bad, seed, with_pin):
         bwd(*zeros, planes=pln)
         assert [float(h_[0]) for h_ in hdrs] == fit
         assert all(torch.equal(o[0], e) for o, e in zip(outs, exact))
+    if carry is not None:
+        c0 = 0 if carry == "a" else d
+        zq = zeros[0] if own_q else zeros[1]
+        got = zq[:B * Lq, c0:c0 + d].clone()
+        zq[:B * Lq, c0:c0 + d] = 0.0
+        mk = (mka if carry == "a" else mkb).clone()
+        mk[:, 16 * 8:] = False                                 # the keys of the first pass: ATT_WIDE_MAXW tiles
+        first = [torch.zeros_like(Qs) if own_q else None, torch.zeros_like(Yv), torch.zeros_like(Yu)]
+        fq = first[0] if own_q else first[1]
+        H.attn_bwd(B, H_, dh, Lq, La, Lb, *views, mq, mk if carry == "a" else mka, mkb if carry == "a" else mk, lse, O, d, dO, d, Dv,
+                   (fq, 0), (fq, d), nv * d, (first[1], 2 * d), (first[1], 3 * d), nv * d, (first[2], 0), (first[2], d), nu * d,
+                   drop_p=p, seed=11, site=3, phase=5 if carry == "a" else 6)
+        assert float(got.abs().max()) > 0.0 and torch.equal(got, fq[:B * Lq, c0:c0 + d])
     assert all(float(z.abs().max()) == 0.0 for z in zeros if z is not None)
 
 
@@ -825,13 +844,26 @@ def test_attention_bwd_repair_of_the_fp32_view_kernels(request, kernel, dh, mode
     through whichever of them a shape selects.  B = 3, H = 2.  (40, 40, 100): one chunk, 3 and 7 key tiles, the repair pass as
     ONE launch for both blocks with surplus waves.  (20, 20, 1): the merged short-head form (one workgroup per head for both
     blocks, its verdict over both blocks' sites) at dh = 64 and 96; the per-block fp16x3 form at dh = 48.  (100, 40, 100): several
-    query chunks, the queries a site of their own.  No block has more than 8 tiles, so the wide kernel's multi-pass carry does not
-    write the fp32 buffers.  bad = 1: a fitting scale, the repair launch leaves everything alone."""
+    query chunks, the queries a site of their own.  No block here has more than 8 tiles, so the wide kernel runs one pass per block
+    and writes no fp32 word; its multi-pass launches, which carry dQ partial sums through the fp32 dQ buffer, are the cases of
+    test_attention_bwd_repair_of_the_wide_kernel_in_two_passes below.  bad = 1: a fitting scale, the repair launch leaves everything alone."""
     H = _abi()
     if mode is not None:
         prev = H.attn_mode(mode)
         request.addfinalizer(lambda: H.attn_mode(prev))
     _attn_bwd_repair_protocol(H, 3, 2, dh, Lq, La, Lb, bad, 8 + Lq + Lb, False)
+
+
+@pytest.mark.parametrize("bad", [2.0 ** 30, 2.0 ** -30, 1.0])
+@pytest.mark.parametrize("dh", [96, 128])
+def test_attention_bwd_repair_of_the_wide_kernel_in_two_passes(dh, bad):
+    """The protocol through attn_bwd_fused_wide_kernel at (Lq, La, Lb) = (40, 176, 16): block a has 11 key tiles and is taken in two
+    passes of 8 + 3 -- by the planes-only launch (one launch per block) and by the repair launch (one launch for both blocks: block
+    b's workgroups run 8 waves of which one has a tile).  The three waves without a tile in the last pass still stage and store.
+    The planes and headers are exactly those of the single-scale reference; of the fp32 buffers only the dQa slice is written, and it
+    holds the first pass's sum (``carry`` in _attn_bwd_repair_protocol).  B = 3, H = 2, the queries a site of their own."""
+    H = _abi()
+    _attn_bwd_repair_protocol(H, 3, 2, dh, 40, 176, 16, bad, 8 + 40 + 16, False, carry="a")
 
 
 def test_scales_update():
