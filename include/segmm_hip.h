@@ -424,6 +424,34 @@ int segmm_grad_norm_groups(const float* g, int64_t n, const int64_t* seg_end, co
 int segmm_adamw_table_lrs(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                           uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step,
                           int phase, const float* coef, segmm_stream_t stream);
+/* Lazy exact AdamW of an id-embedding table: only the batch's rows are touched per step.  The step of a row WITHOUT a gradient is
+ * a function of the row's own (p, m, v) and that step's scalars, so it is taken later, in order, with the same fp32 operations:
+ * after a flush the table holds the bits of the dense update (segmm_adamw_table phase 0 + 1 every step).  Three pieces of state,
+ * all caller-owned device memory:
+ *   stamps  n_rows int32: the number of optimizer steps already applied to each row;
+ *   hist    a ring of cap entries of four floats {rate, bc1, bc2_sqrt, 0} (16-byte aligned), the entry of step t in slot t % cap:
+ *           what moves from step to step.  The rate is the one the step used BEFORE any lr_scale;
+ *   the other hyperparameters (betas, eps, decay, lr_scale) are arguments of the replay: the caller flushes before it changes one.
+ * segmm_adamw_hist_push: one thread writes the entry of `step` (>= 1: bias corrections computed as in segmm_adamw; -1: count,
+ *   corrections and -- with lr = SEGMM_LIVE_LR -- the rate of the bound device step state), so it can sit in a recorded step.
+ * segmm_adamw_table_catchup: every listed row (ids, n_ids; duplicates allowed, ids outside [0, n_rows) ignored, as in
+ *   segmm_adamw_table) whose stamp is below the target replays the steps stamp + 1 .. target with g = 0 from the ring and is
+ *   written once; its stamp becomes the target (an atomic max claims the row: a duplicate, or a row already at the target, is
+ *   neither read nor written).  target - stamp <= cap must hold for every row reached.  ids == NULL: the FLUSH, every row of the
+ *   table.  flags != NULL (listed rows only): every valid listed row is marked for a following phase 1 of segmm_adamw_table,
+ *   which a lazy step runs without a phase 0.  target: by value (relative == 0, target >= 0), or the bound device step count plus
+ *   target (relative != 0, target 0 or -1: -1 at the head of a step, behind segmm_step_advance, is "every step before this one").
+ * segmm_adamw_table_stamp: the listed rows' stamps become at least the target (after phase 1 has stepped them); ids == NULL:
+ *   all n_rows stamps are SET to the target (a loaded checkpoint, a rebuilt buffer).
+ * One lazy step T: catchup(ids, target T - 1, flags) ahead of the forward; hist_push(T); phase 1 of segmm_adamw_table on the same
+ * ids; stamp(ids, T).  With cap = F the caller flushes (catchup with ids == NULL to the step count) whenever F steps have passed
+ * since the last flush, before the next step begins. */
+int segmm_adamw_hist_push(float* hist, int cap, float lr, float beta1, float beta2, int step, segmm_stream_t stream);
+int segmm_adamw_table_catchup(float* p, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids, int32_t* stamps,
+                              uint32_t* flags, const float* hist, int cap, int target, int relative, float lr_scale, float beta1,
+                              float beta2, float eps, float weight_decay, segmm_stream_t stream);
+int segmm_adamw_table_stamp(const int64_t* ids, int n_ids, int64_t n_rows, int32_t* stamps, int target, int relative,
+                            segmm_stream_t stream);
 /* Device-side step state, so that a whole training step (main_for_seq_leave_earlystop_SegMM.py:265-300) can be replayed from its
  * recorded launch sequences with unchanged kernel arguments: two dropout seed words and the optimizer's step count with its bias
  * corrections live in device memory -- a struct of segmm_step_state_bytes() bytes in CALLER-OWNED, 16-byte aligned device memory

@@ -1702,6 +1702,59 @@ int segmm_adamw_table_lrs(float* p, const float* g, float* m, float* v, int64_t 
                             coef, stream);
 }
 
+int segmm_adamw_hist_push(float* hist, int cap, float lr, float beta1, float beta2, int step, segmm_stream_t stream) {
+    SEGMM_REQUIRE(hist && aligned16(hist) && cap >= 1, "adamw_hist_push: ring pointer/alignment, cap=%d (>= 1)", cap);
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_hist_push: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_hist_push: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    hipLaunchKernelGGL(adamw_hist_push_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamwHist*)hist, cap, step, lr, (float)bc1, (float)sqrt(bc2),
+                       live);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// target of the two launches below: the step count itself (relative == 0, target >= 0), or the bound device step count plus
+// target (relative != 0, target 0 or -1)
+#define SEGMM_LAZY_TARGET_CHECK(who)                                                                                                     \
+    SEGMM_REQUIRE(relative ? (target == 0 || target == -1) : target >= 0,                                                                \
+                  who ": target=%d (relative=%d: >= 0 by value; 0 or -1 from the device-side step count)", target, relative)
+
+int segmm_adamw_table_stamp(const int64_t* ids, int n_ids, int64_t n_rows, int32_t* stamps, int target, int relative, segmm_stream_t stream) {
+    SEGMM_REQUIRE(stamps && n_rows >= 0 && n_ids >= 0, "adamw_table_stamp: arguments");
+    SEGMM_LAZY_TARGET_CHECK("adamw_table_stamp");
+    const long long n = ids ? (long long)n_ids : (long long)n_rows;
+    if (n == 0) return 0;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const StepState* live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    hipLaunchKernelGGL(table_stamp_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, n, (long long)n_rows,
+                       (int*)stamps, target, live);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_adamw_table_catchup(float* p, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids, int32_t* stamps,
+                              uint32_t* flags, const float* hist, int cap, int target, int relative, float lr_scale, float beta1, float beta2,
+                              float eps, float weight_decay, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && m && v && stamps && hist && aligned16(p) && aligned16(m) && aligned16(v) && aligned16(hist), "adamw_table_catchup: pointer/alignment");
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_catchup: width %% 4, sizes, cap >= 1");
+    SEGMM_REQUIRE(!flags || ids, "adamw_table_catchup: flags mark LISTED rows (the flush, ids == NULL, takes none)");
+    SEGMM_LAZY_TARGET_CHECK("adamw_table_catchup");
+    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_catchup: lr_scale=%g (finite, >= 0)", (double)lr_scale);
+    const long long n = ids ? (long long)n_ids : (long long)n_rows;
+    if (n == 0 || n_rows == 0) return 0;
+    const StepState* live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    long long blocks = (n + 3) / 4;          // one wave per row; the flush strides over a capped grid like adamw_table_rest_kernel's
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(adamw_table_catchup_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, m, v, (long long)n_rows, width,
+                       (const long long*)ids, n, (int*)stamps, (unsigned int*)flags, (const AdamwHist*)hist, cap, target, live, lr_scale, beta1,
+                       beta2, eps, weight_decay);
+    LAUNCH_CHECK();
+    return 0;
+}
+#undef SEGMM_LAZY_TARGET_CHECK
+
 int segmm_adamw_groups(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end, const float* seg_lr_scale,
                        const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1, float beta2, float eps, int step,
                        const float* coef, segmm_stream_t stream) {

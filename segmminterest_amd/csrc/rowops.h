@@ -987,6 +987,71 @@ __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict
     }
 }
 
+// ---------------------------------------------------------------- lazy exact AdamW of an id table (segmm_adamw_table_catchup)
+// A row without a gradient takes a step that depends on nothing but its own (p, m, v) and the step's scalars, so the step can be
+// taken LATER, in order, with the same fp32 operations: bit for bit adamw_table_rest_kernel's update of that row.  Each row carries
+// a stamp (int32: the optimizer steps already applied to it); the scalars of step t that move from step to step -- the rate
+// before lr_scale, bc1, bc2_sqrt -- sit in slot t % cap of a device ring, one 16-byte entry per step (hist_push_kernel).
+struct AdamwHist { float lr, bc1, bc2_sqrt, pad_; };
+__global__ void adamw_hist_push_kernel(AdamwHist* __restrict__ hist, int cap, int t, float lr, float bc1, float bc2_sqrt, const StepState* live) {
+    if (live) { t = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    if (t < 0) return;          // (a step state that was never set)
+    hist[t % cap] =AdamwHist{lr, bc1, bc2_sqrt, 0.f};
+}
+// the stamps of the listed rows become at least `target` (the rows phase 1 has just stepped); ids == NULL: every stamp IS target
+__global__ __launch_bounds__(256) void table_stamp_kernel(const long long* __restrict__ ids, long long n, long long n_rows, int* __restrict__ stamps,
+                                                          int target, const StepState* live) {
+    if (live) target += live->step;
+    for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
+        if (!ids) { stamps[k] = target; continue; }
+        const long long id = ids[k];
+        if (id >= 0 && id < n_rows) atomicMax(stamps + id, target);
+    }
+}
+// Rows behind `target` replay their missed steps stamp + 1 .. target with g = 0 from the ring and are written once.  One wave per
+// row, four rows per workgroup, four floats per lane (adamw_table_rows_kernel's shape); lane 0 claims the row with an atomic max of
+// its stamp: a second list entry with the same id, or a row already at target, finds old >= target and leaves the row alone (no
+// load, no store).  ids == NULL: the rows 0 .. n_items - 1 themselves (the flush; the grid is capped and strides).  flags != NULL:
+// every valid listed row is marked for phase 1 of segmm_adamw_table, which the lazy step runs without a phase 0.  target - stamp
+// <= cap is the caller's rule (a slot is overwritten cap steps later).  The replay is a dependent chain of sqrt and divide per
+// element and step; four independent elements per lane keep the VALU busy from one wave: a whole workgroup per row with one float
+// per thread (four waves per row at width 256) measured 2.7-2.9x SLOWER per row-step at every gap from 32 to 1024 and 3.9x in the
+// flush (profiles/lazy_tables/), and was dropped.
+__global__ __launch_bounds__(256) void adamw_table_catchup_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long n_rows,
+                                                                  int width, const long long* __restrict__ ids, long long n_items,
+                                                                  int* __restrict__ stamps, unsigned int* __restrict__ flags,
+                                                                  const AdamwHist* __restrict__ hist, int cap, int target, const StepState* live,
+                                                                  float lr_scale, float b1, float b2, float eps, float wd) {
+#pragma clang fp contract(off)
+    if (live) target += live->step;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int w4 = width >> 2;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (long long k = blockIdx.x * 4LL + wave; k < n_items; k += gridDim.x * 4LL) {
+        const long long id = ids ? ids[k] : k;
+        int old = target;
+        if (lane == 0 && id >= 0 && id < n_rows) {
+            old = atomicMax(stamps + id, target);
+            if (flags) flags[id] = 1u;
+        }
+        old = __builtin_amdgcn_readfirstlane(old);
+        if (old >= target) continue;
+        for (int c = lane; c < w4; c += 64) {
+            const long long i = id * w4 + c;
+            f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+            int slot = (int)((unsigned)(old + 1) % (unsigned)cap);          // (a stamp is never negative; whatever it holds, the slot is in the ring)
+            for (int s = old + 1; s <= target; ++s) {
+                const AdamwHist h = hist[slot];
+                slot = slot + 1 == cap ? 0 : slot + 1;
+                const float lr = h.lr * lr_scale;
+                const float step = lr / h.bc1;
+                adamw_elem4(pp, zero, mm, vv, lr, b1, b2, eps, wd, step, h.bc2_sqrt);
+            }
+            ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- global 2-norm of a flat gradient range (segmm_grad_norm)
 // torch.nn.utils.clip_grad_norm_(params, max_norm) without a host sync: sum of squares in fp64 (the square of an fp32 value is
 // exact in fp64, so fp32 gradients near 1e-20 or 1e19 neither underflow nor overflow), one partial per workgroup into caller-owned

@@ -42,6 +42,7 @@ class EvalPasses:
         ``ema=True`` (needs ``Trainer(ema=...)``): the pass runs on the averaged weights (``ema.applied()``); a checkpoint's
         ``"model_ema"`` entry is restored into the EMA first."""
         scope = self._ema_scope(ema, "test_model")
+        self.opt.flush_tables()          # lazy tables: every row current before weights are read (or replaced by the checkpoint's)
         if ckpt is not None:
             load_dict = ckpt.load_checkpoint(self.model, self.opt, mode="best", **({"ema": self.ema} if ema else {}))
             self.model.load_state_dict(load_dict["model"])
@@ -173,6 +174,7 @@ class EvalPasses:
     def eval_step(self, batch, mode="inference"):
         model = self.model
         model.eval()
+        self.opt.flush_tables()          # lazy tables: the forward reads every listed row as the dense run holds it (nothing pending: no launch)
         usr, um, vid, vm = self._features(batch)
         return model(usr_image=usr, usr_id=batch["user_identity_id"], usr_mask=um, vid_image=vid,
                      vid_id=batch["photo_identity_id"], vid_mask=vm, gt=batch["label"], mode=mode)
@@ -186,6 +188,7 @@ class EvalPasses:
         ``ema=True`` (needs ``Trainer(ema=...)``): the logits of the averaged weights (``ema.applied()``)."""
         from .bridge import DeviceLogitStore
         with self._ema_scope(ema, "dump_logits"):
+            self.opt.flush_tables()          # lazy tables: every row current before the forward reads them
             for batches in splits:
                 for batch in batches:
                     logits = self.eval_step(batch, mode="inference")["logits"]
@@ -210,6 +213,7 @@ class EvalPasses:
         if ema:
             with self._ema_scope(ema, "valid_model"):
                 return self.valid_model(batches, metrics=metrics, permutation=permutation, top_k_mask=top_k_mask, recorded=recorded, seed=seed)
+        self.opt.flush_tables()          # lazy tables: every row current before the forward reads them (nothing pending: no launch)
         if recorded:
             return self.valid_enqueue(batches, metrics=metrics, permutation=permutation, top_k_mask=top_k_mask, seed=seed).finish()
         from .my_evaluation import TOP_K_leave_device
@@ -302,6 +306,7 @@ class EvalPasses:
         if self.comm.active:
             raise RuntimeError("valid_model(recorded=True) is not supported under data parallelism (an active DPComm): the per-batch "
                                "rank gather and loss all-reduce are host-driven collectives; use recorded=False")
+        self.opt.flush_tables()          # lazy tables: flushed ahead of the pass, never inside its recording
         batches = list(batches)
         for b in batches:
             self._refuse_unrecordable(b, "valid_model(recorded=True)", "validation batch")

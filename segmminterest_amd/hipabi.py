@@ -1116,6 +1116,58 @@ def adamw_table_lrs(p, g, m, v, off, n_rows, width, ids, flags, lr, lr_scale, be
                                            _ptr(coef), _stream()), "segmm_adamw_table_lrs")
 
 
+# ---- lazy exact AdamW of an id table (include/segmm_hip.h "Lazy exact AdamW"): stamps int32 [n_rows], hist float32 [cap, 4]
+def _lazy_state(stamps, hist, n_rows):
+    if stamps.dtype != torch.int32 or not stamps.is_contiguous() or stamps.numel() != int(n_rows):
+        raise RuntimeError("lazy table: stamps must be %d contiguous int32 (got %s x %d)" % (n_rows, stamps.dtype, stamps.numel()))
+    if hist is not None and (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 2 or hist.shape[1] != 4 or hist.shape[0] < 1):
+        raise RuntimeError("lazy table: the history ring must be contiguous float32 [cap, 4]")
+    _dev(stamps, hist)
+
+
+def adamw_hist_push(hist, lr, beta1, beta2, step):
+    """segmm_adamw_hist_push: the entry of ``step`` (>= 1, or -1: the bound device step state's count, with ``lr`` = LIVE_LR its rate
+    too) into slot step % cap of the ring ``hist`` (float32 [cap, 4])."""
+    if hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 2 or hist.shape[1] != 4:
+        raise RuntimeError("adamw_hist_push: the history ring must be contiguous float32 [cap, 4]")
+    _dev(hist)
+    _check(lib().segmm_adamw_hist_push(hist.data_ptr(), hist.shape[0], float(lr), float(beta1), float(beta2), int(step), _stream()),
+           "segmm_adamw_hist_push")
+
+
+def adamw_table_catchup(p, m, v, off, n_rows, width, ids, stamps, hist, target, lr_scale, beta1, beta2, eps, weight_decay, relative=False,
+                        flags=None):
+    """segmm_adamw_table_catchup on the table that starts ``off`` floats into the flat buffers: the rows listed in ``ids`` (None: every
+    row, the flush) replay their missed g = 0 steps up to ``target`` (``relative``: the bound device step count plus ``target``, 0 or
+    -1); ``flags``: the listed rows are marked for the phase 1 that follows."""
+    n_rows, width = int(n_rows), int(width)
+    _lazy_state(stamps, hist, n_rows)
+    if off < 0 or off + n_rows * width > min(p.numel(), m.numel(), v.numel()):
+        raise RuntimeError("adamw_table_catchup: a table of %d x %d at float %d does not fit buffers of %d / %d / %d elements"
+                           % (n_rows, width, off, p.numel(), m.numel(), v.numel()))
+    if flags is not None and (ids is None or flags.numel() != n_rows or flags.dtype != torch.int32):
+        raise RuntimeError("adamw_table_catchup: flags are %d int32 and go with an id list" % n_rows)
+    if ids is not None and (ids.dtype != torch.int64 or not ids.is_contiguous()):
+        raise RuntimeError("adamw_table_catchup: ids must be contiguous int64")
+    if ids is not None and ids.numel() == 0:          # an empty list (torch hands out a null pointer for it, the C ABI's flush) lists nothing
+        return
+    _check(lib().segmm_adamw_table_catchup(p.data_ptr() + 4 * off, m.data_ptr() + 4 * off, v.data_ptr() + 4 * off, n_rows, width, _ptr(ids),
+                                           0 if ids is None else ids.numel(), stamps.data_ptr(), _ptr(flags), hist.data_ptr(), hist.shape[0],
+                                           int(target), int(bool(relative)), float(lr_scale), float(beta1), float(beta2), float(eps),
+                                           float(weight_decay), _stream()), "segmm_adamw_table_catchup")
+
+
+def adamw_table_stamp(ids, n_rows, stamps, target, relative=False):
+    """segmm_adamw_table_stamp: the listed rows' stamps become at least ``target``; ``ids`` None: every stamp is set to it."""
+    _lazy_state(stamps, None, n_rows)
+    if ids is not None and (ids.dtype != torch.int64 or not ids.is_contiguous()):
+        raise RuntimeError("adamw_table_stamp: ids must be contiguous int64")
+    if ids is not None and ids.numel() == 0:          # (a null pointer in the C ABI means every row)
+        return
+    _check(lib().segmm_adamw_table_stamp(_ptr(ids), 0 if ids is None else ids.numel(), int(n_rows), stamps.data_ptr(), int(target),
+                                         int(bool(relative)), _stream()), "segmm_adamw_table_stamp")
+
+
 GRAD_NORM_SCRATCH = 1024          # fp64 partials segmm_grad_norm may write
 
 

@@ -163,6 +163,8 @@ class CheckPointer:
         """``ema`` (a :class:`WeightEMA`): one more key, ``"model_ema"`` = ``ema.state_dict()`` -- the model's own keys and shapes."""
         import glob
         import os
+        if hasattr(optimizer, "flush_tables"):
+            optimizer.flush_tables()          # lazy id tables: the weights saved below are the dense run's
         sd = dict(model={k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
                   optimizer=optimizer.state_dict(), num_epochs=num_epochs, metrics=metric_vals)
         if ema is not None:

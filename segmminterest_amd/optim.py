@@ -292,6 +292,28 @@ def _check_ema_decay(decay):
     return float(decay)
 
 
+LAZY_KEYS = ("flush_every",)
+LAZY_FLUSH_EVERY = 64          # lazy_tables=True (profiles/lazy_tables/)
+
+
+def parse_lazy_tables(spec):
+    """``lazy_tables=`` of FusedAdamW / Trainer -> ``flush_every`` (the history ring's capacity) or None.  ``spec``: None (dense, as
+    ever), True (the default capacity) or ``dict(flush_every=int)``; an unknown key and a flush_every < 1 are refused by name."""
+    if spec is None:
+        return None
+    if spec is True:
+        return LAZY_FLUSH_EVERY
+    if not isinstance(spec, dict):
+        raise ValueError("lazy_tables must be None, True or dict(flush_every=int), not %r" % (spec,))
+    unknown = [k for k in spec if k not in LAZY_KEYS]
+    if unknown:
+        raise ValueError("lazy_tables: unknown key %r (lazy tables take %s)" % (unknown[0], ", ".join(LAZY_KEYS)))
+    fe = spec.get("flush_every", LAZY_FLUSH_EVERY)
+    if isinstance(fe, bool) or not isinstance(fe, int) or fe < 1:
+        raise ValueError("lazy_tables: flush_every must be an int >= 1, not %r" % (fe,))
+    return fe
+
+
 class WeightEMA:
     """An exponential moving average of the live parameters, kept on the device and owned by :class:`FusedAdamW`
     (``Trainer(ema=...)``; ``trainer.ema`` / ``opt.ema``): ``shadow <- shadow + (p - shadow) w`` after every optimizer step, one
@@ -470,13 +492,33 @@ class FusedAdamW:
     ``group_of(name)`` a parameter's resolved values.
 
     ``ema`` (None = nothing is launched or allocated; a decay, or ``dict(decay=0.999, warmup=True)``): a :class:`WeightEMA` of the
-    live parameters, ``opt.ema``, updated by ``end_step`` with one launch behind the step's last AdamW launch."""
+    live parameters, ``opt.ema``, updated by ``end_step`` with one launch behind the step's last AdamW launch.
+
+    ``lazy_tables`` (None = every launch as ever; True, or ``dict(flush_every=F)``): LAZY EXACT AdamW of the id-embedding tables
+    the trainer hands to :meth:`table_lazy`.  A step touches only the batch's rows: at its head they replay the g = 0 steps they
+    missed (segmm_adamw_table_catchup, from a ring of the last F steps' rate and bias corrections and a per-row step stamp), at its
+    tail they take today's phase-1 launch and the stamp of the step; no other row is read or written.  Nothing is dropped or
+    approximated: after :meth:`flush_tables` the table, both moments included, holds the bits of the dense update.  The host
+    flushes between steps once F steps have passed since the last flush (the ring's capacity), and before a step whose betas, eps,
+    decay or group scale differ from the pending steps' (the ring holds only what a schedule moves).  ``state_dict()`` flushes
+    first: a checkpoint is byte for byte the dense one, with no new keys; ``load_state_dict`` and a rebuild of the flat buffer
+    discard what is pending and set every stamp to ``step_count`` -- flush before loading weights into a model with pending rows
+    (``CheckPointer`` and the trainer's evaluation passes do).  A rebuild of the flat buffer with rows pending LOSES their pending
+    decay and momentum steps (the moments are zeroed there as ever): from then on the run is not the dense run's; call
+    ``flush_tables()`` before anything that rebuilds the buffer.  ``tables_pending``: the steps since the last flush.  Refused by
+    name: an EMA (its shadow would average stale rows), unknown keys, flush_every < 1, :meth:`table_lazy` with ``flush_every`` steps
+    pending (the trainer calls :meth:`lazy_step_head` first).  A forward of the caller's own (not ``Trainer.train_step``) reads the
+    table as it stands: call ``flush_tables()`` before it.  ``step()`` for a lazy table that did not come through
+    :meth:`table_lazy` steps it densely and sets every stamp; with steps pending it raises, because that forward read stale rows."""
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None,
-                 param_groups=None, ema=None):
+                 param_groups=None, ema=None, lazy_tables=None):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
         ema = parse_ema(ema)
         self.ema = None if ema is None else WeightEMA(self, *ema)
+        # flush_every (= the ring's capacity) or None; _lazy: name -> dict(stamps, flags, o, rows, width) of the tables stepped lazily
+        self.lazy_flush_every = parse_lazy_tables(lazy_tables)
+        self._lazy, self._lazy_hist, self._lazy_flushed, self._lazy_snap = {}, None, 0, None
         # resolved groups (resolve_param_groups; entry 0 = the default group) or None; _segs: their segment table on the device
         self.groups = None if param_groups is None else resolve_param_groups(list(model.named_parameters()), param_groups, weight_decay)
         self._group_idx = None if self.groups is None else {n: gi for gi, G in enumerate(self.groups) for n in G["names"]}
@@ -496,6 +538,7 @@ class FusedAdamW:
             self.v = torch.zeros(st.n_live, device=st.flat.device)
             self._flat_id = st.flat.data_ptr()
             self._segs = None
+            self._lazy = {}          # (what was pending went with the old moments: the next table_lazy stamps every row step_count)
             if self.ema is not None:          # (re-)seeded where m and v are zeroed: from the parameters of the moment
                 self.ema._seed(st)
         if self.groups is not None and self._segs is None:
@@ -596,23 +639,126 @@ class FusedAdamW:
         return H.step_get_lr()[0]
 
     def step(self, gbuf=None):
+        # a lazy table that did not come through table_lazy this step (a forward and backward of the caller's own): it is stepped
+        # densely, with the rest of the live range -- which is the dense run's step only if every row was current when the forward
+        # read the table.  Flushing here would be too late: the gradients are already those of stale rows
+        dense_lazy = bool(self._lazy) and any(name not in {e[7] for e in self.__dict__.get("_early", [])} for name in self._lazy)
+        if dense_lazy and self.tables_pending:
+            raise RuntimeError("lazy_tables: step() without table_lazy() for %s while %d steps are pending -- the forward read rows that "
+                               "were behind; call flush_tables() BEFORE a forward that does not go through Trainer.train_step"
+                               % (", ".join(sorted(self._lazy)), self.tables_pending))
+        early = self.__dict__.pop("_early", [])
+        if dense_lazy:
+            for e in early:
+                if e[7] is not None:
+                    H.fill_zero(e[5])
+            early = [e for e in early if e[7] is None]
         self.begin_step(gbuf)
         st = self._state()
         pos = 0
-        # id tables whose rows without a gradient were already stepped at the head of the step (table_early): the listed rows
-        # now, with their gradients; everything else as contiguous ranges around them
-        for o, n, rows, width, ids, flags, hyper in sorted(self.__dict__.pop("_early", []), key=lambda e: e[0]):
+        live = self.__dict__.get("device_state", False)
+        pushed = False
+        # id tables whose rows without a gradient were already stepped at the head of the step (table_early) or are stepped
+        # lazily (table_lazy): the listed rows now, with their gradients; everything else as contiguous ranges around them
+        for o, n, rows, width, ids, flags, hyper, lazy in sorted(early, key=lambda e: e[0]):
             self.step_range(pos, o, gbuf)
-            step = -1 if self.__dict__.get("device_state", False) else self.step_count
+            step = -1 if live else self.step_count
+            if lazy is not None and not pushed:          # this step's entry of the ring: the rate and bias corrections phase 1 uses
+                H.adamw_hist_push(self._lazy_hist, self._lr_arg(), self.betas[0], self.betas[1], step)
+                pushed = True
             if hyper is None:
                 H.adamw_table(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), self.betas[0],
                               self.betas[1], self.eps, self.wd, step, 1, coef=self._coef())
             else:          # (an id table lies in one group by construction: it is one parameter)
                 H.adamw_table_lrs(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), hyper[0],
                                   self.betas[0], self.betas[1], self.eps, hyper[1], step, 1, coef=self._coef())
+            if lazy is not None:
+                H.adamw_table_stamp(ids, rows, self._lazy[lazy]["stamps"], 0 if live else self.step_count, relative=live)
             pos = o + n
         self.step_range(pos, st.n_live, gbuf)
+        if dense_lazy:
+            self._lazy_restamp()
         self.end_step()
+
+    # ---- lazy exact AdamW of the id tables (lazy_tables=...)
+    @property
+    def tables_pending(self):
+        """The optimizer steps since the last flush of the lazy tables (0: every row is current)."""
+        return self.step_count - self._lazy_flushed if self._lazy else 0
+
+    def _lazy_hyper_now(self):
+        """What a replayed step takes from the launch arguments, not from the ring: betas, eps and each lazy table's (scale, decay)."""
+        tabs = tuple((n,) + ((1.0, self.wd) if self.groups is None else tuple(self.group_of(n)[:2])) for n in sorted(self._lazy))
+        return (tuple(self.betas), self.eps, tabs)
+
+    def _lazy_restamp(self):
+        """Every row of every lazy table has taken ``step_count`` steps (a dense step, a loaded checkpoint)."""
+        for e in self._lazy.values():
+            H.adamw_table_stamp(None, e["rows"], e["stamps"], self.step_count)
+        self._lazy_flushed = self.step_count
+
+    def flush_tables(self):
+        """Brings every row of the lazy tables to ``step_count`` (segmm_adamw_table_catchup over all rows, with the hyperparameters of
+        the pending steps); nothing is launched when nothing is pending.  Never part of a recorded step."""
+        if self.tables_pending == 0:
+            return
+        if H.RECORDER is not None:
+            raise RuntimeError("flush_tables() inside a recorded step: the flush of the lazy tables is a host decision between steps")
+        st = self._state()
+        if self.tables_pending == 0:          # (the flat buffer was rebuilt: nothing is pending any more)
+            return
+        betas, eps, tabs = self._lazy_snap
+        for name, scale, wd in tabs:
+            e = self._lazy[name]
+            H.adamw_table_catchup(st.flat, self.m, self.v, e["o"], e["rows"], e["width"], None, e["stamps"], self._lazy_hist, self.step_count,
+                                  scale, betas[0], betas[1], eps, wd)
+        self._lazy_flushed = self.step_count
+
+    def lazy_step_head(self):
+        """Between two steps, before the next one begins (the trainer calls it; never inside a recording): the periodic flush, once
+        ``flush_every`` steps are pending -- the ring holds no more -- and the flush ahead of a changed hyperparameter."""
+        pending = self.tables_pending
+        if pending and (pending >= self.lazy_flush_every or self._lazy_snap != self._lazy_hyper_now()):
+            self.flush_tables()
+
+    def table_lazy(self, name, ids):
+        """Head of a lazy step of the id-embedding table ``name``, on the current stream and AHEAD of the forward that reads the rows:
+        the rows in ``ids`` replay the steps they missed, up to the one before this (segmm_adamw_table_catchup), and are marked for
+        this step's phase 1, which ``step()`` runs with the ring's new entry and the rows' new stamp.  Correct whether or not the
+        step then happens: a row caught up to step T - 1 holds what the dense run holds after T - 1."""
+        if self.lazy_flush_every is None:
+            raise RuntimeError("table_lazy needs FusedAdamW(lazy_tables=...)")
+        if self.ema is not None:
+            raise RuntimeError("lazy_tables with ema: the shadow would average the stale rows of the lazy table %s; use one of the two" % name)
+        st = self._state()
+        if self.tables_pending >= self.lazy_flush_every:          # the ring rule: target - stamp <= cap, or a replay reads an overwritten slot
+            raise RuntimeError("table_lazy: %d steps are pending and the ring holds %d -- call lazy_step_head() (or flush_tables()) "
+                               "between steps, before the step begins" % (self.tables_pending, self.lazy_flush_every))
+        if self._frozen(name):          # nothing to step, now or later
+            return
+        hyper = None if self.groups is None else self.group_of(name)[:2]
+        o, n = st.index[name]
+        rows, width = st._params[name].shape
+        dev = st.flat.device
+        e = self._lazy.get(name)
+        if e is None:
+            H.torch_fallback("the first lazy step of the table %s (its stamps are made; record() after one eager step)" % name)
+            if not self._lazy:
+                self._lazy_flushed = self.step_count
+            e = self._lazy[name] = dict(o=o, rows=rows, width=width, flags=torch.zeros((rows,), dtype=torch.int32, device=dev),
+                                        stamps=torch.full((rows,), self.step_count, dtype=torch.int32, device=dev))
+        if self._lazy_hist is None or self._lazy_hist.device != dev:
+            self._lazy_hist = torch.zeros((self.lazy_flush_every, 4), dtype=torch.float32, device=dev)
+        live = self.__dict__.get("device_state", False)
+        scale, wd = (1.0, self.wd) if hyper is None else hyper
+        H.adamw_table_catchup(st.flat, self.m, self.v, o, rows, width, ids, e["stamps"], self._lazy_hist, -1 if live else self.step_count, scale,
+                              self.betas[0], self.betas[1], self.eps, wd, relative=live, flags=e["flags"])
+        self._lazy_snap = self._lazy_hyper_now()
+        self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, e["flags"], hyper, name))
+
+    def early_on_aux(self):
+        """True while a two-pass table's phase 0 of this step is queued (on the auxiliary stream: join it before ``step()``)."""
+        return any(e[7] is None for e in self.__dict__.get("_early") or ())
 
     def table_early(self, name, ids):
         """First pass of the two-pass update of the id-embedding table ``name`` (segmm_adamw_table): every row that is NOT in
@@ -639,7 +785,7 @@ class FusedAdamW:
         else:
             H.adamw_table_lrs(st.flat, None, self.m, self.v, o, rows, width, ids, flags, self._lr_arg(), hyper[0], self.betas[0], self.betas[1],
                               self.eps, hyper[1], step, 0)
-        self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, flags, hyper))
+        self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, flags, hyper, None))
 
     # one optimizer step as several launches over disjoint ranges that together cover the live range: the data-parallel
     # trainer steps each gradient bucket as soon as ITS all-reduce has completed (begin_step, step_range ..., end_step)
@@ -699,6 +845,7 @@ class FusedAdamW:
     def state_dict(self):
         """torch.optim.AdamW-format state (keyed by the index of the parameter in model.parameters()),
         so a checkpoint written here resumes under the reference's optimizer and vice versa."""
+        self.flush_tables()          # lazy tables: the checkpoint is the dense one
         st = self._state()
         names = [n for n, _ in self.model.named_parameters()]
         state = {}
@@ -774,6 +921,7 @@ class FusedAdamW:
                 self.v[o:o + k].copy_(s["exp_avg_sq"].reshape(-1))
                 steps.add(int(float(s["step"])))
         self.step_count = max(steps) if steps else 0
+        self._lazy_restamp()          # lazy tables: the loaded moments are every row's, at the loaded count; nothing stays pending
         g = sd["param_groups"][0]
         self.lr, self.wd, self.betas, self.eps = g["lr"], g["weight_decay"], tuple(g["betas"]), g["eps"]
         if self.groups is not None:          # the groups' own values (entry 0, the default group, follows the optimizer's decay)

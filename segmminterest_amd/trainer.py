@@ -121,8 +121,18 @@ class Trainer(EvalPasses):
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
                  feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None,
-                 param_groups=None, ema=None):
+                 param_groups=None, ema=None, lazy_tables=None):
         self.model = model
+        # lazy_tables=None | True | dict(flush_every=F): lazy exact AdamW of the item-id tables (FusedAdamW; _tables_early) -- a step
+        # reads and writes only the batch's rows of the table.  Single process only: under data parallelism the rows touched are
+        # those of ALL ranks, known only after the row exchange
+        if lazy_tables is not None and comm is not None and comm.active:
+            raise ValueError("Trainer(lazy_tables=...) is not supported with an active DPComm (data parallel): the rows a step touches "
+                             "are all ranks' rows, known only after the row exchange; the dense table update stays there")
+        if lazy_tables is not None and ema is not None and any(
+                bb is not None and bb.id_vid for bb in (model.backbone1, getattr(model, "backbone2", None))):
+            raise ValueError("Trainer(lazy_tables=...) with ema: the EMA shadow would average the stale rows of the lazy item-id table; "
+                             "use one of the two")
         # micro_batch=m: a batch of more than m rows is stepped in ceil(B / m) micro-batches with ONE optimizer step on the whole
         # batch's gradient (train_step / _train_step_micro); None, or m >= the batch's rows: the plain step, launch for launch
         if micro_batch is not None and (isinstance(micro_batch, bool) or not isinstance(micro_batch, int) or micro_batch < 1):
@@ -142,7 +152,7 @@ class Trainer(EvalPasses):
         self.feature_table = feature_table
         self.dropout = dropout      # False: run the step in eval mode (deterministic; used by the DP equivalence tests)
         self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
-                              param_groups=param_groups, ema=ema)          # per-group rate scale, decay and freezing: see FusedAdamW
+                              param_groups=param_groups, ema=ema, lazy_tables=lazy_tables)          # per-group rate scale, decay and freezing: see FusedAdamW
         # ema=None | decay | dict(decay=0.999, warmup=True): a device-side moving average of the weights (WeightEMA), or None
         self.ema = self.opt.ema
         self.comm = comm if comm is not None else DPComm()
@@ -306,9 +316,10 @@ class Trainer(EvalPasses):
         # skipped
         stale = self.opt.__dict__.pop("_early", None)
         if stale:
-            E.join_aux(self.model._store)
-            for _, _, _, _, _, flags, _ in stale:
-                flags.zero_()
+            if any(e[7] is None for e in stale):
+                E.join_aux(self.model._store)
+            for e in stale:
+                e[5].zero_()
             #  the failed step had already advanced the DEVICE step count (segmm_step_advance at its head) while
             # opt.step_count never moved, and THIS step has advanced it once more: put it back to step_count + 1, the number of the
             # step that is running, so its bias corrections are right again.  What cannot be taken back and is accepted: the failed step's early pass applied one g = 0 AdamW
@@ -317,10 +328,21 @@ class Trainer(EvalPasses):
                 H.step_bind(self._step_state)
                 seed, _, _ = H.step_get()
                 H.step_set(seed, self.opt.step_count + 1, *self.opt.betas)
-        if self.comm.active or not self.table_two_pass or self._param_hooks():
+        lazy = self.opt.lazy_flush_every is not None
+        if lazy and self._param_hooks():
+            raise RuntimeError("Trainer(lazy_tables=...) does not support parameter hooks: a hook may rewrite the gradient of table rows "
+                               "outside the batch, which a lazy step never reads")
+        if self.comm.active or not (self.table_two_pass or lazy) or self._param_hooks():
             return
         model, st = self.model, self.model._store
         ids = batch.get("photo_identity_id")
+        if lazy and torch.is_tensor(ids):
+            # the forward reads the batch's rows whatever the id list looks like (engine._as converts it there): a lazy step must
+            # bring those rows up to date first, so an int32 or strided list is converted here the same way, never skipped
+            ids = E._as(ids, torch.int64, "the item ids")
+        elif lazy:
+            self.opt.flush_tables()          # (no id list at all: every row current before anything reads the table)
+            return
         if ids is None or ids.dtype != torch.int64 or not ids.is_contiguous():
             return
         for pre, bb in (("backbone1.", model.backbone1), ("backbone2.", getattr(model, "backbone2", None))):
@@ -328,6 +350,12 @@ class Trainer(EvalPasses):
                 continue
             name = pre + "vid_proj.weight"
             if name not in st.index or name not in st.live_names or st._params[name].shape[1] % 4:
+                continue
+            if lazy:
+                # lazy exact AdamW takes the early pass's place: the batch's rows catch up to the step before this one, on the MAIN
+                # stream -- the id-embedding forward reads them.  No repair is needed if the step then fails: rows caught up to
+                # T - 1 are right whether or not step T happens
+                self.opt.table_lazy(name, ids.reshape(-1))
                 continue
             if self.opt.ema is not None:          # the shadow is made and seeded on the main stream, before the early pass moves the table's rows
                 self.opt.ema.step_head(self.opt._state())
@@ -491,6 +519,8 @@ class Trainer(EvalPasses):
         is prefetched then)."""
         if self.ema is not None:
             self.ema._refuse_applied("train_step()")
+        if self.opt.lazy_flush_every is not None:
+            self.opt.lazy_step_head()          # the periodic flush of the lazy tables: between steps, ahead of the step's first launch
         if self.micro_batch is not None and batch_rows(batch) > self.micro_batch:
             return self._train_step_micro(batch, self.micro_batch)
         st = self.model._store
@@ -613,7 +643,7 @@ class Trainer(EvalPasses):
             if self.comm.active:
                 H.host_action(self._micro_reduce)
             H.mark(H.PHASE_STEP_TAIL)
-            if self.opt.__dict__.get("_early"):
+            if self.opt.early_on_aux():
                 E.join_aux(st)          # the tables' first pass (aux stream) is complete before their listed rows are stepped
             self.opt.step()
             res = {}
@@ -733,7 +763,7 @@ class Trainer(EvalPasses):
                     w.wait()
             self.comm.finish()
         H.mark(H.PHASE_STEP_TAIL)
-        if self.opt.__dict__.get("_early"):
+        if self.opt.early_on_aux():
             E.join_aux(st)          # the tables' first pass (aux stream) is complete before their listed rows are stepped
         self.opt.step()
         return out
@@ -775,6 +805,7 @@ class Trainer(EvalPasses):
             for _ in range(max(warmup - 1, 0)):
                 self.train_step(batch)
             self.train_step(prev)
+        self.opt.flush_tables()          # lazy tables: a flush is never part of a recording -- the recorded step starts with none pending
         aux = st.__dict__.get("_aux_stream")
         with R.capture(st, st.side_stream().cuda_stream, aux.cuda_stream if aux is not None else 0) as cap:
             # The recorded step must carry the per-step weight split (segmm_wsplit_p32): ParamStore.refresh_planes skips it when the planes
@@ -850,6 +881,8 @@ class Trainer(EvalPasses):
             v = batch[k]
             if tuple(v.shape) != sh or v.dtype != dt or not v.is_contiguous():
                 raise RuntimeError("run_recorded(): batch[%r] is %s %s, the step was recorded for %s %s" % (k, tuple(v.shape), v.dtype, sh, dt))
+        if self.opt.lazy_flush_every is not None:
+            self.opt.lazy_step_head()          # the host's periodic flush, between two replays
         # (a wrong current stream is refused before a slot is patched: a refused call leaves the recording as it found it)
         R.replay(r, "run_recorded()", "step", batch, r["prev_batch"], timed)
         r["prev_batch"] = batch          # (also keeps the tensors a lag-1 pointer names alive until the next step has run)

@@ -1,0 +1,223 @@
+#!/usr/bin/env python
+"""What lazy exact AdamW of the item-id table costs and saves (Trainer(lazy_tables=...)), measured on the GPU; prints its report and,
+with ``--out FILE``, writes the same text there (profiles/lazy_tables/lazy_tables_bench.txt is this tool's output, see
+profiles/README.md).
+
+``--what step``: the recorded BASELINE config-3 step (id / id, B = 1024, S = 20, d = 512, N = 4, 352 494 items), lazy against the
+dense two-pass trainer of the SAME build, in one process, in alternating windows of ``--steps`` replays (a host clock around replays
+that end in a device synchronise).  Every leg walks the same pool of ``--pool`` id batches, so the gap between two visits of a row is
+the workload's, not that of three rotating batches.  Two draws of the item ids: uniform over the catalogue, and skewed (id =
+1 + floor(n_items u^4), u uniform: a quarter of the draws fall on 0.4 % of the items).  Lazy legs: flush_every 64, 256, 1024; their
+windows hold the periodic flushes that fall into them (windows x steps is a multiple of 1024: the mean over the windows carries each
+leg's flushes at their true share).  Before the timed windows every leg runs ``--settle`` steps, more than the largest flush_every:
+the stamps are in their steady state.  Reported per leg: median and mean window, the dense leg's window spread, and whether the lazy
+mean is slower than the dense mean by more than that spread.
+
+``--what kernel``: segmm_adamw_table_catchup alone on a 352 494 x W table (W the model's table width): 1024 listed rows that are ``gap``
+steps behind (the stamps are put back before every launch by a copy whose own time is measured and subtracted): at the batch's mean
+gap in each of the step part's pools and for each flush_every, then for a sweep of gaps; and ONE flush of the whole table after flush_every untouched steps.
+
+    python tools/lazy_tables_bench.py [--what step,kernel] [--windows 8] [--steps 256] [--pool 512] [--settle 1100] [--out FILE]
+
+Needs the GPU; there is no fallback."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HEADS, N_USERS, N_ITEMS = 16, 1903, 352494
+CFG3 = (20, 1, 512, 4, 1024)          # S, Lt, d, N, B of BASELINE config 3
+FLUSH = (64, 256, 1024)
+TABLE = "backbone1.vid_proj.weight"
+
+LINES = []
+
+
+def say(s):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def _model(torch, dev):
+    from segmminterest_amd.trainer import default_args, init_model
+    S, Lt, D, N, _ = CFG3
+    margs = default_args(num_layers_enc=N, d_model=D, nhead=HEADS, input_type={"user": "id", "photo": "id"}, exposure_prob=[1.0] * S)
+    torch.manual_seed(1234)
+    return init_model(margs, n_users=N_USERS, n_items=N_ITEMS, input_dim=D, max_vid_len=S, max_usr_len=Lt).to(dev)
+
+
+def _pool(torch, dev, n, skewed):
+    from segmminterest_amd.synth import make_batch
+    S, Lt, D, _, B = CFG3
+    g = torch.Generator().manual_seed(77)
+    out = []
+    for i in range(n):
+        b = make_batch(B, S, Lt, D, n_users=N_USERS, n_items=N_ITEMS, seed=1234 + 1000 * i, features=False)
+        if skewed:
+            b["photo_identity_id"] = (1 + (N_ITEMS * torch.rand(B, generator=g, dtype=torch.float64) ** 4).long()).clamp_(max=N_ITEMS)
+            b["photo_id"] = b["photo_identity_id"].clone()
+        out.append({k: v.to(dev) for k, v in b.items()})
+    return out
+
+
+def mean_gap(pool, cap):
+    """Mean over the pool's listed rows of min(steps since the row's last visit, cap) while the pool is walked round and round."""
+    last, tot, cnt = {}, 0, 0
+    for rnd in range(2):
+        for t, b in enumerate(pool):
+            for r in set(b["photo_identity_id"].tolist()):
+                if rnd:
+                    tot += min(len(pool) + t - last.get(r, -10 ** 9), cap)
+                    cnt += 1
+                last[r] = len(pool) * rnd + t
+    return tot / max(cnt, 1)
+
+
+def step(torch, steps, windows, n_pool, settle, dev):
+    from segmminterest_amd.trainer import Trainer
+    ok = True
+    for skewed in (False, True):
+        pool = _pool(torch, dev, n_pool, skewed)
+        legs = {}
+        for leg in ("dense",) + tuple("lazy %d" % f for f in FLUSH):
+            tr = Trainer(_model(torch, dev), device_state=True, lazy_tables=None if leg == "dense" else dict(flush_every=int(leg.split()[1])))
+            tr.train_step(pool[0])
+            tr.train_step(pool[1])
+            tr.record(pool[2], prev_batch=pool[1])
+            for i in range(settle):
+                tr.run_recorded(pool[(3 + i) % n_pool])
+            legs[leg] = [tr, 3 + settle]
+        torch.cuda.synchronize()
+        ms = {leg: [] for leg in legs}
+        for _ in range(windows):
+            for leg, e in legs.items():
+                tr = e[0]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    tr.run_recorded(pool[(e[1] + i) % n_pool])
+                torch.cuda.synchronize()
+                ms[leg].append(1e3 * (time.perf_counter() - t0) / steps)
+                e[1] += steps
+        d = ms["dense"]
+        spread, mean0 = max(d) - min(d), statistics.mean(d)
+        rows = [len(set(b["photo_identity_id"].tolist())) for b in pool]
+        say("recorded config-3 step (B = %d), item ids %s: pool of %d batches (%.0f distinct rows per batch), %d settling steps, %d alternating "
+            "windows of %d replays" % (CFG3[4], "SKEWED (1 + floor(n u^4))" if skewed else "uniform", n_pool, statistics.mean(rows), settle, windows, steps))
+        say("  dense two-pass    median %.4f ms  mean %.4f ms  (min %.4f max %.4f: spread %.4f ms = %.2f %%)"
+            % (statistics.median(d), mean0, min(d), max(d), spread, 100 * spread / mean0))
+        best = None
+        for f in FLUSH:
+            x = ms["lazy %d" % f]
+            mean = statistics.mean(x)
+            slower = mean - mean0 > spread
+            say("  lazy flush_every %-5d median %.4f ms  mean %.4f ms  (min %.4f max %.4f)  mean / dense %.4f  mean gap of a listed row %.1f steps  "
+                "slower than dense by more than its spread: %s" % (f, statistics.median(x), mean, min(x), max(x), mean / mean0, mean_gap(pool, f),
+                                                                   "YES" if slower else "no"))
+            if best is None or mean < best[1]:
+                best = (f, mean)
+        say("  smallest mean: flush_every = %d" % best[0])
+        ok = ok and best[1] - mean0 <= spread
+        del legs, pool
+        torch.cuda.empty_cache()
+    return ok
+
+
+def _timed(torch, fn, reps):
+    """us per call of ``fn``: ``reps`` calls between two device events."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / reps
+
+
+def kernel(torch, windows, n_pool, dev):
+    from segmminterest_amd import hipabi as H
+    model = _model(torch, dev)
+    width = model.get_parameter(TABLE).shape[1]
+    rows = model.get_parameter(TABLE).shape[0]
+    del model
+    n = rows * width
+    p, m = (torch.randn(n, device=dev) * 1e-2 for _ in range(2))
+    v = torch.rand(n, device=dev) * 1e-4
+    cap = 1024
+    hist = torch.zeros((cap, 4), device=dev)
+    for t in range(1, cap + 1):
+        H.adamw_hist_push(hist, 1e-3, 0.9, 0.999, 5000 + t)
+    target = 5000 + cap
+    stamps, behind = torch.zeros(rows, dtype=torch.int32, device=dev), torch.zeros(rows, dtype=torch.int32, device=dev)
+    ids = torch.randperm(rows, device=dev)[:1024].to(torch.int64).contiguous()
+    say("segmm_adamw_table_catchup alone: table %d x %d, 1024 distinct listed rows, each `gap` steps behind; us per launch (median of %d windows), "
+        "the copy that puts the stamps back subtracted" % (rows, width, windows))
+    hp = (1.0, 0.9, 0.999, 1e-8, 1e-2)
+    # the batch's MEAN gap in the step part's two pools, per flush_every (a listed row is never further behind than that), then a sweep
+    gaps = []
+    for skewed in (False, True):
+        pool = _pool(torch, "cpu", n_pool, skewed)
+        gaps += [(max(1, round(mean_gap(pool, f))), "the batch's mean gap, %s ids, flush_every %d" % ("skewed" if skewed else "uniform", f)) for f in FLUSH]
+    for gap, label in gaps + [(g, "") for g in (1, 8, 32, 64, 128, 344, 1024)]:
+        behind.fill_(target - gap)
+
+        def both():
+            H.copy_bytes(stamps, behind)
+            H.adamw_table_catchup(p, m, v, 0, rows, width, ids, stamps, hist, target, *hp)
+        both()
+        torch.cuda.synchronize()
+        reps = 50 if gap <= 128 else 10
+        full = statistics.median(_timed(torch, both, reps) for _ in range(windows))
+        copy = statistics.median(_timed(torch, lambda: H.copy_bytes(stamps, behind), reps) for _ in range(windows))
+        say("  gap %-5d %9.2f us (%.2f ns per row-step)%s" % (gap, full - copy, 1e3 * (full - copy) / (1024 * gap), "   " + label if label else ""))
+    say("ONE flush of the whole table (%d x %d = %.0f M floats, 24 B per float = %.2f GB of traffic) after flush_every untouched steps:"
+        % (rows, width, n / 1e6, 24.0 * n / 1e9))
+    for f in FLUSH:
+        behind.fill_(target - f)
+
+        def flush():
+            H.copy_bytes(stamps, behind)
+            H.adamw_table_catchup(p, m, v, 0, rows, width, None, stamps, hist, target, *hp)
+        flush()
+        torch.cuda.synchronize()
+        us = statistics.median(_timed(torch, flush, 2) for _ in range(3))
+        say("  flush_every %-5d %9.3f ms = %.1f us per step it covers" % (f, 1e-3 * us, us / f))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", default="step,kernel")
+    ap.add_argument("--windows", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--pool", type=int, default=512)
+    ap.add_argument("--settle", type=int, default=1100)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("lazy_tables_bench: no GPU (this tool measures the HIP path; there is no fallback)")
+    from segmminterest_amd import hipabi as H
+    H.lib()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    say("lazy_tables_bench: %s" % torch.cuda.get_device_name(0))
+    ok = True
+    what = args.what.split(",")
+    if "kernel" in what:
+        kernel(torch, min(args.windows, 5), args.pool, dev)
+    if "step" in what:
+        ok = step(torch, args.steps, args.windows, args.pool, args.settle, dev)
+    say("lazy (best flush_every) not slower than dense beyond the dense leg's window spread, both draws: %s" % ("yes" if ok else "NO"))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
