@@ -445,13 +445,24 @@ int segmm_adamw_table_lrs(float* p, const float* g, float* m, float* v, int64_t 
  *   all n_rows stamps are SET to the target (a loaded checkpoint, a rebuilt buffer).
  * One lazy step T: catchup(ids, target T - 1, flags) ahead of the forward; hist_push(T); phase 1 of segmm_adamw_table on the same
  * ids; stamp(ids, T).  With cap = F the caller flushes (catchup with ids == NULL to the step count) whenever F steps have passed
- * since the last flush, before the next step begins. */
+ * since the last flush, before the next step begins.
+ * Data parallel, a rank knows only its OWN ids at the head of a step; the rows the other ranks touch are known after the row
+ * exchange.  One lazy step T there: catchup(own ids, target T - 1) ahead of the forward (no flags); hist_push(T);
+ * segmm_adamw_table_lazy_rows(all ranks' ids, T).  lazy_rows claims every listed row with an atomic max of its stamp with T
+ * (T: step >= 1 by value, or step == -1: the bound device step state's count, with its bias corrections and -- lr = SEGMM_LIVE_LR --
+ * its rate); a row whose stamp was already T or more (a duplicate entry, a row stepped before) is neither read nor written, ids
+ * outside [0, n_rows) are ignored.  The winner replays old + 1 .. T - 1 with g = 0 from the ring, then takes step T with its row
+ * of g (times *coef when coef != NULL) and step T's own scalars, and writes p, m, v once: bit for bit catchup(ids, T - 1, flags),
+ * hist_push(T), phase 1 of segmm_adamw_table_lrs, stamp(ids, T) on the same list.  T - 1 - stamp <= cap is the caller's rule. */
 int segmm_adamw_hist_push(float* hist, int cap, float lr, float beta1, float beta2, int step, segmm_stream_t stream);
 int segmm_adamw_table_catchup(float* p, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids, int32_t* stamps,
                               uint32_t* flags, const float* hist, int cap, int target, int relative, float lr_scale, float beta1,
                               float beta2, float eps, float weight_decay, segmm_stream_t stream);
 int segmm_adamw_table_stamp(const int64_t* ids, int n_ids, int64_t n_rows, int32_t* stamps, int target, int relative,
                             segmm_stream_t stream);
+int segmm_adamw_table_lazy_rows(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2, float eps,
+                                float weight_decay, int step, const float* coef, segmm_stream_t stream);
 /* Device-side step state, so that a whole training step (main_for_seq_leave_earlystop_SegMM.py:265-300) can be replayed from its
  * recorded launch sequences with unchanged kernel arguments: two dropout seed words and the optimizer's step count with its bias
  * corrections live in device memory -- a struct of segmm_step_state_bytes() bytes in CALLER-OWNED, 16-byte aligned device memory

@@ -1755,6 +1755,32 @@ int segmm_adamw_table_catchup(float* p, float* m, float* v, int64_t n_rows, int 
 }
 #undef SEGMM_LAZY_TARGET_CHECK
 
+int segmm_adamw_table_lazy_rows(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2, float eps,
+                                float weight_decay, int step, const float* coef, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && g && m && v && stamps && hist && (ids || n_ids == 0) && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) &&
+                      aligned16(hist),
+                  "adamw_table_lazy_rows: pointer/alignment");
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_lazy_rows: width %% 4, sizes, cap >= 1");
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_lazy_rows: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table_lazy_rows: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_lazy_rows: lr_scale=%g (finite, >= 0)", (double)lr_scale);
+    if (n_rows == 0 || n_ids == 0) return 0;
+    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    const int w4 = width / 4;
+    if (coef)
+        hipLaunchKernelGGL(adamw_table_lazy_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, w4,
+                           (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps, weight_decay,
+                           (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
+    else
+        hipLaunchKernelGGL(adamw_table_lazy_rows_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, w4,
+                           (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps, weight_decay,
+                           (float)bc1, (float)sqrt(bc2), live, (const float*)nullptr, lr_scale);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int segmm_adamw_groups(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end, const float* seg_lr_scale,
                        const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1, float beta2, float eps, int step,
                        const float* coef, segmm_stream_t stream) {

@@ -1051,6 +1051,51 @@ __global__ __launch_bounds__(256) void adamw_table_catchup_kernel(float* __restr
         }
     }
 }
+// The data-parallel tail of a lazy step (segmm_adamw_table_lazy_rows): the listed rows -- those of ALL ranks, known only after the
+// row exchange -- replay the g = 0 steps old + 1 .. T - 1 from the ring (adamw_table_catchup_kernel's loop) and then take step T
+// with their gradient row and step T's own scalars (adamw_table_rows_kernel's: lr = lr * lr_scale, step = lr / bc1), in one pass
+// over the row: p, m, v are read once and written once, where catch-up + phase 1 + stamp read and write them twice in three
+// launches on the exposed end of the step.  The same shape, one wave per list entry and four floats per lane; the claim is the
+// atomic max of the stamp with T itself, so no flags are involved: a duplicate entry, or a row already at T, finds old >= T and
+// is neither loaded nor stored.  The gradient vector is loaded ahead of the replay: nothing needs it before the dependent sqrt /
+// divide chain of the replayed steps has run, which hides its latency (at a gap of 0 it travels with p, m, v in one round).
+template <bool SCALED>
+__global__ __launch_bounds__(256) void adamw_table_lazy_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                    float* __restrict__ v, long long n_rows, int w4,
+                                                                    const long long* __restrict__ ids, int n_ids, int* __restrict__ stamps,
+                                                                    const AdamwHist* __restrict__ hist, int cap, int T, float lr, float b1, float b2,
+                                                                    float eps, float wd, float bc1, float bc2_sqrt, const StepState* live,
+                                                                    const float* __restrict__ coef, float lr_scale) {
+#pragma clang fp contract(off)
+    if (live) { T = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    lr = lr * lr_scale;
+    const float step = lr / bc1;
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (k >= n_ids) return;
+    const long long id = ids[k];
+    if (id < 0 || id >= n_rows) return;
+    int old = T;
+    if (lane == 0) old = atomicMax(stamps + id, T);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (old >= T) return;          // another entry of the list holds the same id and has taken the row, or the row was stepped already
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int c = lane; c < w4; c += 64) {
+        const long long i = id * w4 + c;
+        const f32x4 graw = ((const f32x4*)g)[i];
+        f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+        int slot = (int)((unsigned)(old + 1) % (unsigned)cap);          // (as in the catch-up: whatever the stamp holds, the slot is in the ring)
+        for (int s = old + 1; s < T; ++s) {
+            const AdamwHist h = hist[slot];
+            slot = slot + 1 == cap ? 0 : slot + 1;
+            const float lr_s = h.lr * lr_scale;
+            const float step_s = lr_s / h.bc1;
+            adamw_elem4(pp, zero, mm, vv, lr_s, b1, b2, eps, wd, step_s, h.bc2_sqrt);
+        }
+        adamw_elem4(pp, adamw_grad4<SCALED>(graw, coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+    }
+}
 
 // ---------------------------------------------------------------- global 2-norm of a flat gradient range (segmm_grad_norm)
 // torch.nn.utils.clip_grad_norm_(params, max_norm) without a host sync: sum of squares in fp64 (the square of an fp32 value is

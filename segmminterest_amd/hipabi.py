@@ -1168,7 +1168,29 @@ def adamw_table_stamp(ids, n_rows, stamps, target, relative=False):
                                          int(bool(relative)), _stream()), "segmm_adamw_table_stamp")
 
 
-GRAD_NORM_SCRATCH = 1024          # fp64 partials segmm_grad_norm may write
+def adamw_table_lazy_rows(p, g, m, v, off, n_rows, width, ids, stamps, hist, lr, lr_scale, beta1, beta2, eps, weight_decay, step, coef=None):
+    """segmm_adamw_table_lazy_rows on the table that starts ``off`` floats into the flat buffers: every row listed in ``ids`` (all
+    ranks' ids of a data-parallel step) whose stamp is below T = ``step`` (>= 1, or -1: the bound device step state's count) replays
+    its missed g = 0 steps up to T - 1 from the ring, takes step T with its row of ``g`` (times ``coef[0]``) and is stamped T."""
+    n_rows, width = int(n_rows), int(width)
+    _lazy_state(stamps, hist, n_rows)
+    if hist is None:
+        raise RuntimeError("adamw_table_lazy_rows: needs the history ring")
+    if off < 0 or off + n_rows * width > min(p.numel(), g.numel(), m.numel(), v.numel()):
+        raise RuntimeError("adamw_table_lazy_rows: a table of %d x %d at float %d does not fit buffers of %d / %d / %d / %d elements"
+                           % (n_rows, width, off, p.numel(), g.numel(), m.numel(), v.numel()))
+    if ids is None or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise RuntimeError("adamw_table_lazy_rows: ids must be contiguous int64 (the gathered list of the step)")
+    _dev(p, g, m, v, ids, coef)
+    if ids.numel() == 0:
+        return
+    _check(lib().segmm_adamw_table_lazy_rows(p.data_ptr() + 4 * off, g.data_ptr() + 4 * off, m.data_ptr() + 4 * off, v.data_ptr() + 4 * off,
+                                             n_rows, width, ids.data_ptr(), ids.numel(), stamps.data_ptr(), hist.data_ptr(), hist.shape[0],
+                                             float(lr), float(lr_scale), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                             _ptr(coef), _stream()), "segmm_adamw_table_lazy_rows")
+
+
+GRAD_NORM_SCRATCH = 1024         # fp64 partials segmm_grad_norm may write
 
 
 def grad_norm_groups(g, n, segs, max_norm, scratch, out2):

@@ -292,13 +292,14 @@ def _check_ema_decay(decay):
     return float(decay)
 
 
-LAZY_KEYS = ("flush_every",)
+LAZY_KEYS = ("flush_every", "data_parallel")
 LAZY_FLUSH_EVERY = 64          # lazy_tables=True (profiles/lazy_tables/)
 
 
 def parse_lazy_tables(spec):
     """``lazy_tables=`` of FusedAdamW / Trainer -> ``flush_every`` (the history ring's capacity) or None.  ``spec``: None (dense, as
-    ever), True (the default capacity) or ``dict(flush_every=int)``; an unknown key and a flush_every < 1 are refused by name."""
+    ever), True (the default capacity) or ``dict(flush_every=int, data_parallel=bool)``; an unknown key, a flush_every < 1 and a
+    data_parallel that is no bool are refused by name (:func:`parse_lazy_data_parallel` returns that flag)."""
     if spec is None:
         return None
     if spec is True:
@@ -311,7 +312,17 @@ def parse_lazy_tables(spec):
     fe = spec.get("flush_every", LAZY_FLUSH_EVERY)
     if isinstance(fe, bool) or not isinstance(fe, int) or fe < 1:
         raise ValueError("lazy_tables: flush_every must be an int >= 1, not %r" % (fe,))
+    parse_lazy_data_parallel(spec)
     return fe
+
+
+def parse_lazy_data_parallel(spec):
+    """The ``data_parallel`` key of ``lazy_tables=`` (default False): the opt-in to lazy tables under an active DPComm, where the
+    rows a step touches are all ranks' rows and are stepped by segmm_adamw_table_lazy_rows behind the row exchange."""
+    dp = spec.get("data_parallel", False) if isinstance(spec, dict) else False
+    if not isinstance(dp, bool):
+        raise ValueError("lazy_tables: data_parallel must be a bool, not %r" % (dp,))
+    return dp
 
 
 class WeightEMA:
@@ -509,7 +520,13 @@ class FusedAdamW:
     name: an EMA (its shadow would average stale rows), unknown keys, flush_every < 1, :meth:`table_lazy` with ``flush_every`` steps
     pending (the trainer calls :meth:`lazy_step_head` first).  A forward of the caller's own (not ``Trainer.train_step``) reads the
     table as it stands: call ``flush_tables()`` before it.  ``step()`` for a lazy table that did not come through
-    :meth:`table_lazy` steps it densely and sets every stamp; with steps pending it raises, because that forward read stale rows."""
+    :meth:`table_lazy` steps it densely and sets every stamp; with steps pending it raises, because that forward read stale rows.
+    ``dict(data_parallel=True)`` (a bool, default False; combinable with ``flush_every``; ``opt.lazy_data_parallel``): the opt-in to
+    lazy tables under an active DPComm.  The rows a step touches there are all ranks' rows, known after the row exchange: the head is
+    ``table_lazy(name, own_ids, mark=False)`` -- the rank's own rows catch up, nothing is marked or queued -- and the tail
+    :meth:`table_lazy_rows` on the gathered list (segmm_adamw_table_lazy_rows: replay, this step and the stamp in one launch), while
+    the dense launches walk around the table (:meth:`step_ranges`).  Stamps, ring and flush rule depend on the step count only:
+    every rank flushes at the same step and holds the same bits, without a collective.  Without an active comm the key changes nothing."""
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None,
                  param_groups=None, ema=None, lazy_tables=None):
@@ -519,6 +536,11 @@ class FusedAdamW:
         # flush_every (= the ring's capacity) or None; _lazy: name -> dict(stamps, flags, o, rows, width) of the tables stepped lazily
         self.lazy_flush_every = parse_lazy_tables(lazy_tables)
         self._lazy, self._lazy_hist, self._lazy_flushed, self._lazy_snap = {}, None, 0, None
+        # lazy_tables=dict(data_parallel=True): the trainer may step the tables lazily under an active DPComm (table_lazy with
+        # mark=False at the head, table_lazy_rows at the tail).  _lazy_tail: name -> (o, n) of the tables whose head has run that
+        # way -- the ranges the dense launches of the step walk around (step_ranges); _lazy_pushed: the step whose ring entry is in
+        self.lazy_data_parallel = parse_lazy_data_parallel(lazy_tables)
+        self._lazy_tail, self._lazy_pushed = {}, 0
         # resolved groups (resolve_param_groups; entry 0 = the default group) or None; _segs: their segment table on the device
         self.groups = None if param_groups is None else resolve_param_groups(list(model.named_parameters()), param_groups, weight_decay)
         self._group_idx = None if self.groups is None else {n: gi for gi, G in enumerate(self.groups) for n in G["names"]}
@@ -539,6 +561,7 @@ class FusedAdamW:
             self._flat_id = st.flat.data_ptr()
             self._segs = None
             self._lazy = {}          # (what was pending went with the old moments: the next table_lazy stamps every row step_count)
+            self._lazy_tail = {}
             if self.ema is not None:          # (re-)seeded where m and v are zeroed: from the parameters of the moment
                 self.ema._seed(st)
         if self.groups is not None and self._segs is None:
@@ -638,11 +661,20 @@ class FusedAdamW:
         self._bound_state("device_lr")
         return H.step_get_lr()[0]
 
-    def step(self, gbuf=None):
+    def step(self, gbuf=None, lazy_rows=None):
+        """``lazy_rows`` (data parallel, ``lazy_tables=dict(data_parallel=True)``): name -> the gathered id list of all ranks, for
+        every table whose head ran as ``table_lazy(name, own_ids, mark=False)``; those tables take :meth:`table_lazy_rows` behind the
+        dense ranges, which walk around them."""
+        lazy_rows = lazy_rows or {}
+        missing = sorted(n for n in self._lazy_tail if n not in lazy_rows)
+        if missing:
+            raise RuntimeError("lazy_tables: step() after table_lazy(..., mark=False) for %s needs the step's gathered id list "
+                               "(step(lazy_rows={name: ids_all})): the dense ranges skip these tables" % ", ".join(missing))
         # a lazy table that did not come through table_lazy this step (a forward and backward of the caller's own): it is stepped
         # densely, with the rest of the live range -- which is the dense run's step only if every row was current when the forward
         # read the table.  Flushing here would be too late: the gradients are already those of stale rows
-        dense_lazy = bool(self._lazy) and any(name not in {e[7] for e in self.__dict__.get("_early", [])} for name in self._lazy)
+        covered = {e[7] for e in self.__dict__.get("_early", [])} | set(self._lazy_tail)
+        dense_lazy = bool(self._lazy) and any(name not in covered for name in self._lazy)
         if dense_lazy and self.tables_pending:
             raise RuntimeError("lazy_tables: step() without table_lazy() for %s while %d steps are pending -- the forward read rows that "
                                "were behind; call flush_tables() BEFORE a forward that does not go through Trainer.train_step"
@@ -661,7 +693,7 @@ class FusedAdamW:
         # id tables whose rows without a gradient were already stepped at the head of the step (table_early) or are stepped
         # lazily (table_lazy): the listed rows now, with their gradients; everything else as contiguous ranges around them
         for o, n, rows, width, ids, flags, hyper, lazy in sorted(early, key=lambda e: e[0]):
-            self.step_range(pos, o, gbuf)
+            self.step_ranges(pos, o, gbuf)
             step = -1 if live else self.step_count
             if lazy is not None and not pushed:          # this step's entry of the ring: the rate and bias corrections phase 1 uses
                 H.adamw_hist_push(self._lazy_hist, self._lr_arg(), self.betas[0], self.betas[1], step)
@@ -675,7 +707,9 @@ class FusedAdamW:
             if lazy is not None:
                 H.adamw_table_stamp(ids, rows, self._lazy[lazy]["stamps"], 0 if live else self.step_count, relative=live)
             pos = o + n
-        self.step_range(pos, st.n_live, gbuf)
+        self.step_ranges(pos, st.n_live, gbuf)
+        for name in sorted(lazy_rows):
+            self.table_lazy_rows(name, lazy_rows[name], gbuf)
         if dense_lazy:
             self._lazy_restamp()
         self.end_step()
@@ -696,6 +730,7 @@ class FusedAdamW:
         for e in self._lazy.values():
             H.adamw_table_stamp(None, e["rows"], e["stamps"], self.step_count)
         self._lazy_flushed = self.step_count
+        self._lazy_pushed = 0          # (a loaded count may meet the number of a step whose entry is in the ring: it is pushed again)
 
     def flush_tables(self):
         """Brings every row of the lazy tables to ``step_count`` (segmm_adamw_table_catchup over all rows, with the hyperparameters of
@@ -721,11 +756,14 @@ class FusedAdamW:
         if pending and (pending >= self.lazy_flush_every or self._lazy_snap != self._lazy_hyper_now()):
             self.flush_tables()
 
-    def table_lazy(self, name, ids):
+    def table_lazy(self, name, ids, mark=True):
         """Head of a lazy step of the id-embedding table ``name``, on the current stream and AHEAD of the forward that reads the rows:
         the rows in ``ids`` replay the steps they missed, up to the one before this (segmm_adamw_table_catchup), and are marked for
         this step's phase 1, which ``step()`` runs with the ring's new entry and the rows' new stamp.  Correct whether or not the
-        step then happens: a row caught up to step T - 1 holds what the dense run holds after T - 1."""
+        step then happens: a row caught up to step T - 1 holds what the dense run holds after T - 1.
+        ``mark=False`` (data parallel: ``ids`` are this rank's own, the step's rows are known after the row exchange): the rows catch
+        up and nothing else happens -- no flags, nothing queued; the table's range is left out of the step's dense launches
+        (:meth:`step_ranges`) and the tail is :meth:`table_lazy_rows` on the gathered list."""
         if self.lazy_flush_every is None:
             raise RuntimeError("table_lazy needs FusedAdamW(lazy_tables=...)")
         if self.ema is not None:
@@ -752,9 +790,46 @@ class FusedAdamW:
         live = self.__dict__.get("device_state", False)
         scale, wd = (1.0, self.wd) if hyper is None else hyper
         H.adamw_table_catchup(st.flat, self.m, self.v, o, rows, width, ids, e["stamps"], self._lazy_hist, -1 if live else self.step_count, scale,
-                              self.betas[0], self.betas[1], self.eps, wd, relative=live, flags=e["flags"])
+                              self.betas[0], self.betas[1], self.eps, wd, relative=live, flags=e["flags"] if mark else None)
         self._lazy_snap = self._lazy_hyper_now()
-        self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, e["flags"], hyper, name))
+        if mark:
+            self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, e["flags"], hyper, name))
+        else:
+            self._lazy_tail[name] = (o, n)
+
+    def table_lazy_rows(self, name, ids_all, gbuf=None):
+        """Tail of a data-parallel lazy step of the table ``name``, between ``begin_step`` and ``end_step`` on the stream that holds
+        the table's reduced gradient: the ring's entry of this step (once per step, whatever the number of tables), then ONE launch
+        (segmm_adamw_table_lazy_rows) over ``ids_all``, the gathered id list of all ranks -- every listed row replays what it
+        missed up to the step before, takes this step with its gradient row and is stamped.  A frozen table launches nothing."""
+        if self._frozen(name):
+            return
+        if name not in self._lazy_tail or name not in self._lazy:
+            raise RuntimeError("table_lazy_rows(%s) without table_lazy(%s, own_ids, mark=False) at the head of this step: the dense "
+                               "launches of the step have covered the table's range" % (name, name))
+        st = self._state()
+        e = self._lazy[name]
+        live = self.__dict__.get("device_state", False)
+        step = -1 if live else self.step_count
+        if self._lazy_pushed != self.step_count:
+            H.adamw_hist_push(self._lazy_hist, self._lr_arg(), self.betas[0], self.betas[1], step)
+            self._lazy_pushed = self.step_count
+        scale, wd = (1.0, self.wd) if self.groups is None else self.group_of(name)[:2]
+        H.adamw_table_lazy_rows(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, e["o"], e["rows"], e["width"], ids_all, e["stamps"],
+                                self._lazy_hist, self._lr_arg(), scale, self.betas[0], self.betas[1], self.eps, wd, step, coef=self._coef())
+        self._lazy_snap = self._lazy_hyper_now()
+
+    def step_ranges(self, start, end, gbuf=None):
+        """``step_range`` over [start, end) minus the ranges of the tables :meth:`table_lazy_rows` steps this step (none: the one
+        launch of ``step_range``).  Every dense launch of a step goes through here: the per-bucket schedule, the clipped single
+        range and ``step()``."""
+        pos = start
+        for o, n in sorted(self._lazy_tail.values()):
+            if o + n <= pos or o >= end:
+                continue
+            self.step_range(pos, max(pos, o), gbuf)
+            pos = min(end, o + n)
+        self.step_range(pos, end, gbuf)
 
     def early_on_aux(self):
         """True while a two-pass table's phase 0 of this step is queued (on the auxiliary stream: join it before ``step()``)."""
@@ -840,6 +915,7 @@ class FusedAdamW:
             # behind every AdamW launch of this step on this stream; the next step's first parameter write -- phase 0 of a two-pass
             # id table on the auxiliary stream -- is enqueued behind engine.aux_work's fork from this stream
             self.ema.update()
+        self._lazy_tail = {}          # (the next step's head names its tables again)
         self.model._store.fused_version += 1          # the pre-split weight planes of the GEMM engines are now stale
 
     def state_dict(self):

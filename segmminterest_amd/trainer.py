@@ -39,7 +39,7 @@ from .encoder import SegFormerX
 from .eval_passes import EvalPasses
 from .loop import CheckPointer, compute_final_result, early_stop_reached, fit  # noqa: F401
 from .optim import (GROUP_KEYS, FusedAdamW, LRSchedule, PlateauLR, WeightEMA, group_segments, no_decay_groups, parse_ema,  # noqa: F401
-                    resolve_param_groups)
+                    parse_lazy_data_parallel, parse_lazy_tables, resolve_param_groups)
 
 
 # ------------------------------------------------------------------------------------------------ model factory
@@ -124,11 +124,24 @@ class Trainer(EvalPasses):
                  param_groups=None, ema=None, lazy_tables=None):
         self.model = model
         # lazy_tables=None | True | dict(flush_every=F): lazy exact AdamW of the item-id tables (FusedAdamW; _tables_early) -- a step
-        # reads and writes only the batch's rows of the table.  Single process only: under data parallelism the rows touched are
-        # those of ALL ranks, known only after the row exchange
+        # reads and writes only the batch's rows of the table.  Under data parallelism the rows touched are those of ALL ranks, known
+        # only after the row exchange: that takes the opt-in lazy_tables=dict(data_parallel=True) -- the rank's own rows catch up at
+        # the head, the gathered list is stepped by one fused launch at the tail (_tables_early, _finish_step)
+        lazy_dp = False
         if lazy_tables is not None and comm is not None and comm.active:
-            raise ValueError("Trainer(lazy_tables=...) is not supported with an active DPComm (data parallel): the rows a step touches "
-                             "are all ranks' rows, known only after the row exchange; the dense table update stays there")
+            parse_lazy_tables(lazy_tables)          # (a malformed spec is refused for what it is, before anything below)
+            lazy_dp = parse_lazy_data_parallel(lazy_tables)
+            if not lazy_dp:
+                raise ValueError("Trainer(lazy_tables=...) is not supported with an active DPComm (data parallel) as it stands: the rows a "
+                                 "step touches are all ranks' rows, known only after the row exchange; the dense table update stays "
+                                 "there.  lazy_tables=dict(data_parallel=True) opts in to the lazy step behind the row exchange")
+            if not (bool(sparse_tables) and switches.read("trainer")["sparse_tables"]):
+                raise ValueError("Trainer(lazy_tables=dict(data_parallel=True)) needs the sparse row exchange: with sparse_tables off "
+                                 "(sparse_tables=False or SEGMM_SPARSE_TABLES=0) no gathered row list exists")
+            if micro_batch is not None:
+                raise ValueError("Trainer(lazy_tables=dict(data_parallel=True)) with micro_batch under an active DPComm is not supported: "
+                                 "each micro-batch pass has its own row exchange (a follow-up); use one of the two")
+        self._lazy_dp = lazy_dp
         if lazy_tables is not None and ema is not None and any(
                 bb is not None and bb.id_vid for bb in (model.backbone1, getattr(model, "backbone2", None))):
             raise ValueError("Trainer(lazy_tables=...) with ema: the EMA shadow would average the stale rows of the lazy item-id table; "
@@ -310,7 +323,8 @@ class Trainer(EvalPasses):
         traffic, 0.54 ms alone at the END of the step) is split in two -- the rows of this batch (the only ones with a gradient,
         known from the batch's ids) are stepped after the backward as before, every other row now, with g = 0, on an auxiliary
         stream under the forward and backward, which never touch those rows.  (Data parallel: the listed rows are those of ALL
-        ranks, known only after the row exchange -- the dense update stays.)"""
+        ranks, known only after the row exchange -- the dense update stays, unless lazy_tables=dict(data_parallel=True) opted in:
+        then the rank's own rows catch up here and the gathered list is stepped at the tail.)"""
         # a step that failed between this pass and opt.step() (forward / backward error, OOM) left its entry queued and its rows
         # flagged: drop both before queueing this step's, or the table's range would be stepped twice and the failed batch's rows
         # skipped (ADVICE r4)
@@ -332,7 +346,8 @@ class Trainer(EvalPasses):
         if lazy and self._param_hooks():
             raise RuntimeError("Trainer(lazy_tables=...) does not support parameter hooks: a hook may rewrite the gradient of table rows "
                                "outside the batch, which a lazy step never reads")
-        if self.comm.active or not (self.table_two_pass or lazy) or self._param_hooks():
+        # (an active comm with lazy tables is the opt-in lazy_tables=dict(data_parallel=True): the constructor refused anything else)
+        if (self.comm.active and not lazy) or not (self.table_two_pass or lazy) or self._param_hooks():
             return
         model, st = self.model, self.model._store
         ids = batch.get("photo_identity_id")
@@ -355,7 +370,9 @@ class Trainer(EvalPasses):
                 # lazy exact AdamW takes the early pass's place: the batch's rows catch up to the step before this one, on the MAIN
                 # stream -- the id-embedding forward reads them.  No repair is needed if the step then fails: rows caught up to
                 # T - 1 are right whether or not step T happens
-                self.opt.table_lazy(name, ids.reshape(-1))
+                # Data parallel: these are the rank's OWN rows -- the forward reads no others.  Nothing is marked or queued: the rows
+                # of the step, all ranks', are stepped behind the row exchange by one fused launch (_finish_step)
+                self.opt.table_lazy(name, ids.reshape(-1), mark=not self.comm.active)
                 continue
             if self.opt.ema is not None:          # the shadow is made and seeded on the main stream, before the early pass moves the table's rows
                 self.opt.ema.step_head(self.opt._state())
@@ -719,6 +736,7 @@ class Trainer(EvalPasses):
     def _finish_step(self, out):
         """The tail of the plain step: the data-parallel reductions still outstanding, then AdamW."""
         st = self.model._store
+        lazy_rows = self._lazy_rows(st)
         if self.comm.active and self.overlap:
             H.host_action(self._flush_bucket)          # the tail of the backward (embedding gradients) that stayed below the merge threshold
         if self.comm.active and self.overlap and self.per_bucket_adamw and self._covers_live(st):
@@ -734,22 +752,28 @@ class Trainer(EvalPasses):
                 # computes it from its own, identical copy of the all-reduced gradient), then one AdamW launch
                 H.host_action(functools.partial(self._wait_buckets, range(len(works))))
                 self.opt.begin_step()
-                self.opt.step_range(0, st.n_live)
+                self.opt.step_ranges(0, st.n_live)
+                for name, ids_all in lazy_rows.items():          # (the clip coefficient is the norm's, computed in begin_step)
+                    self.opt.table_lazy_rows(name, ids_all)
                 self.opt.end_step()
                 return out
             self.opt.begin_step()
+            # the lazy tables first: their gradient is the row exchange's segment sum, complete on this stream since the backward --
+            # no bucket to wait for (the table's range is in no all-reduce), so the launch runs under the collectives still in flight
+            for name, ids_all in lazy_rows.items():
+                self.opt.table_lazy_rows(name, ids_all)
             order = sorted(range(len(works)), key=lambda i: works[i][0])
             last = len(works) - 1
             early = [i for i in order if i != last]
             if early and works[early[-1]][1] <= works[last][0] and all(works[a][1] == works[b][0] for a, b in zip(early, early[1:])):
                 H.host_action(functools.partial(self._wait_buckets, early))
-                self.opt.step_range(works[early[0]][0], works[early[-1]][1])
+                self.opt.step_ranges(works[early[0]][0], works[early[-1]][1])
                 H.host_action(functools.partial(self._wait_buckets, [last]))
-                self.opt.step_range(works[last][0], works[last][1])
+                self.opt.step_ranges(works[last][0], works[last][1])
             else:          # not a prefix + tail (two backbones interleave their buckets): one launch per bucket
                 for i in range(len(works)):
                     H.host_action(functools.partial(self._wait_buckets, [i]))
-                    self.opt.step_range(works[i][0], works[i][1])
+                    self.opt.step_ranges(works[i][0], works[i][1])
             self.opt.end_step()
             return out
         if self.comm.active:
@@ -765,7 +789,20 @@ class Trainer(EvalPasses):
         H.mark(H.PHASE_STEP_TAIL)
         if self.opt.early_on_aux():
             E.join_aux(st)          # the tables' first pass (aux stream) is complete before their listed rows are stepped
-        self.opt.step()
+        self.opt.step(lazy_rows=lazy_rows)
+        return out
+
+    def _lazy_rows(self, st):
+        """Data parallel with lazy tables: name -> the gathered id list of all ranks, for every table whose head ran this step
+        (FusedAdamW.table_lazy with mark=False).  The list is the row exchange's persistent buffer (DPComm.gather_rows), which the
+        backward left in ``st._tab_rows``: the same tensor every step, so a recorded step names it by address.  Otherwise empty."""
+        out = {}
+        for name in self.opt._lazy_tail:
+            ent = st._tab_rows.get(name[:-len("_proj.weight")])
+            if ent is None:
+                raise RuntimeError("lazy_tables=dict(data_parallel=True): the backward left no gathered row list for %s (the sparse "
+                                   "row exchange did not run for this table)" % name)
+            out[name] = ent[1]
         return out
 
     # ---- the step as recorded launch sequences replayed from C (include/segmm_hip.h "Recorded launch sequences")

@@ -17,6 +17,17 @@ mean is slower than the dense mean by more than that spread.
 steps behind (the stamps are put back before every launch by a copy whose own time is measured and subtracted): at the batch's mean
 gap in each of the step part's pools and for each flush_every, then for a sweep of gaps; and ONE flush of the whole table after flush_every untouched steps.
 
+``--what dp_kernel``: segmm_adamw_table_lazy_rows (the data-parallel tail: replay + step T + stamp in one launch) against the three
+launches it replaces on the same list -- catch-up to T - 1, phase 1 of segmm_adamw_table_lrs, the stamp -- on the config-3 table at
+1024 / 2048 / 4096 listed ids (the gathered list of 1, 2 and 4 ranks) whose rows are 0, 16 and 58 steps behind T - 1 (58: the
+uniform-id mean gap at flush_every = 64).  The ring push is in neither: both protocols make it.
+
+``--what dp_step``: the recorded config-3 DATA-PARALLEL step (B = 1024 rows per rank), ``lazy_tables=dict(flush_every=64,
+data_parallel=True)`` against the dense data-parallel trainer, in alternating windows in ONE process group; the periodic flushes fall
+inside the windows.  Run it under ``torchrun --nproc_per_node=<GPUs>``; started plainly (one GPU) it makes a forced one-rank RCCL
+group (SEGMM_DP_FORCE=1): every collective is really issued but is an identity, and the gathered list is the rank's own.  Rank 0
+reports.  profiles/lazy_tables/dp_bench.txt is the output of ``--what dp_kernel,dp_step``.
+
     python tools/lazy_tables_bench.py [--what step,kernel] [--windows 8] [--steps 256] [--pool 512] [--settle 1100] [--out FILE]
 
 Needs the GPU; there is no fallback."""
@@ -188,6 +199,109 @@ def kernel(torch, windows, n_pool, dev):
         say("  flush_every %-5d %9.3f ms = %.1f us per step it covers" % (f, 1e-3 * us, us / f))
 
 
+DP_FLUSH = 64
+
+
+def dp_kernel(torch, windows, dev):
+    from segmminterest_amd import hipabi as H
+    model = _model(torch, dev)
+    rows, width = model.get_parameter(TABLE).shape
+    del model
+    n = rows * width
+    p, m, g = (torch.randn(n, device=dev) * 1e-2 for _ in range(3))
+    v = torch.rand(n, device=dev) * 1e-4
+    cap = DP_FLUSH
+    hist = torch.zeros((cap, 4), device=dev)
+    T = 5000 + cap
+    for t in range(T - cap + 1, T + 1):
+        H.adamw_hist_push(hist, 1e-3, 0.9, 0.999, t)
+    stamps, behind = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
+    flags = torch.zeros(rows, dtype=torch.int32, device=dev)
+    hp = (0.9, 0.999, 1e-8, 1e-2)
+    say("segmm_adamw_table_lazy_rows against catch-up + phase 1 + stamp: table %d x %d, distinct listed rows, each `gap` steps behind T - 1; "
+        "us per step tail (median of %d windows of 50), the copy that puts the stamps back subtracted" % (rows, width, windows))
+    for n_ids in (1024, 2048, 4096):
+        ids = torch.randperm(rows, device=dev)[:n_ids].to(torch.int64).contiguous()
+        for gap in (0, 16, 58):
+            behind.fill_(T - 1 - gap)
+
+            def fused():
+                H.copy_bytes(stamps, behind)
+                H.adamw_table_lazy_rows(p, g, m, v, 0, rows, width, ids, stamps, hist, 1e-3, 1.0, *hp, T)
+
+            def three():
+                H.copy_bytes(stamps, behind)
+                H.adamw_table_catchup(p, m, v, 0, rows, width, ids, stamps, hist, T - 1, 1.0, *hp, flags=flags)
+                H.adamw_table_lrs(p, g, m, v, 0, rows, width, ids, flags, 1e-3, 1.0, *hp, T, 1)
+                H.adamw_table_stamp(ids, rows, stamps, T)
+            res = {}
+            for name, fn in (("three", three), ("fused", fused), ("copy", lambda: H.copy_bytes(stamps, behind))):
+                fn()
+                torch.cuda.synchronize()
+                res[name] = statistics.median(_timed(torch, fn, 50) for _ in range(windows))
+            a, b = res["three"] - res["copy"], res["fused"] - res["copy"]
+            say("  ids %-5d gap %-3d three launches %8.2f us   fused %8.2f us   saved %7.2f us   fused / three %.3f" % (n_ids, gap, a, b, a - b, b / a))
+
+
+def dp_step(torch, steps, windows, n_pool, settle):
+    import torch.distributed as dist
+    from segmminterest_amd.synth import make_batch
+    world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
+    if world == 1:
+        os.environ.update(SEGMM_DP_FORCE="1", MASTER_ADDR=os.environ.get("MASTER_ADDR", "127.0.0.1"), MASTER_PORT=os.environ.get("MASTER_PORT", "29777"),
+                          RANK="0", WORLD_SIZE="1")
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    dev = torch.device("cuda", local)
+    torch.cuda.set_device(dev)
+    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    from segmminterest_amd.trainer import DPComm, Trainer
+    try:
+        S, Lt, D, _, B = CFG3
+        pool = [{k: v.to(dev) for k, v in make_batch(B, S, Lt, D, n_users=N_USERS, n_items=N_ITEMS, seed=1234 + 1000 * i + 7919 * rank,
+                                                     features=False).items()} for i in range(n_pool)]
+        legs = {}
+        for leg in ("dense", "lazy"):
+            tr = Trainer(_model(torch, dev), comm=DPComm(), device_state=True,
+                         lazy_tables=None if leg == "dense" else dict(flush_every=DP_FLUSH, data_parallel=True))
+            assert tr.comm.active and tr.sparse_tables
+            tr.train_step(pool[0])
+            tr.train_step(pool[1])
+            tr.record(pool[2], warmup=0, prev_batch=pool[1])
+            for i in range(settle):
+                tr.run_recorded(pool[(3 + i) % n_pool])
+            legs[leg] = [tr, 3 + settle]
+        torch.cuda.synchronize()
+        dist.barrier()
+        ms = {leg: [] for leg in legs}
+        for _ in range(windows):
+            for leg, e in legs.items():
+                tr = e[0]
+                torch.cuda.synchronize()
+                dist.barrier()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    tr.run_recorded(pool[(e[1] + i) % n_pool])
+                torch.cuda.synchronize()
+                ms[leg].append(1e3 * (time.perf_counter() - t0) / steps)
+                e[1] += steps
+        if rank == 0:
+            d, x = ms["dense"], ms["lazy"]
+            spread, mean0, mean = max(d) - min(d), statistics.mean(d), statistics.mean(x)
+            say("recorded config-3 DATA-PARALLEL step, %d rank%s x B = %d rows (RCCL%s), uniform item ids: pool of %d batches per rank, %d settling "
+                "steps, %d alternating windows of %d replays in one process group; flush_every = %d, its flushes inside the windows"
+                % (world, "" if world == 1 else "s", B, ", ONE FORCED RANK: every collective is issued and is an identity, the gathered list is "
+                   "the rank's own" if world == 1 else "", n_pool, settle, windows, steps, DP_FLUSH))
+            say("  dense data-parallel  median %.4f ms  mean %.4f ms  (min %.4f max %.4f: spread %.4f ms = %.2f %%)"
+                % (statistics.median(d), mean0, min(d), max(d), spread, 100 * spread / mean0))
+            say("  lazy data-parallel   median %.4f ms  mean %.4f ms  (min %.4f max %.4f)  mean / dense %.4f  saved %.4f ms per step"
+                % (statistics.median(x), mean, min(x), max(x), mean / mean0, mean0 - mean))
+            say("  lazy faster than dense by more than the dense leg's window spread: %s" % ("yes" if mean0 - mean > spread else "NO"))
+    finally:
+        dist.destroy_process_group()
+    return rank
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="step,kernel")
@@ -202,7 +316,7 @@ def main():
         raise SystemExit("lazy_tables_bench: no GPU (this tool measures the HIP path; there is no fallback)")
     from segmminterest_amd import hipabi as H
     H.lib()
-    dev = torch.device("cuda", 0)
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))          # (torchrun: --what dp_step, one GPU per rank)
     torch.cuda.set_device(dev)
     say("lazy_tables_bench: %s" % torch.cuda.get_device_name(0))
     ok = True
@@ -211,8 +325,14 @@ def main():
         kernel(torch, min(args.windows, 5), args.pool, dev)
     if "step" in what:
         ok = step(torch, args.steps, args.windows, args.pool, args.settle, dev)
-    say("lazy (best flush_every) not slower than dense beyond the dense leg's window spread, both draws: %s" % ("yes" if ok else "NO"))
-    if args.out:
+    if "step" in what or "kernel" in what:
+        say("lazy (best flush_every) not slower than dense beyond the dense leg's window spread, both draws: %s" % ("yes" if ok else "NO"))
+    rank = int(os.environ.get("RANK", "0"))
+    if "dp_kernel" in what and rank == 0:
+        dp_kernel(torch, min(args.windows, 5), dev)
+    if "dp_step" in what:
+        dp_step(torch, args.steps, args.windows, args.pool, args.settle)
+    if args.out and rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write("\n".join(LINES) + "\n")
