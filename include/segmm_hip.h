@@ -123,6 +123,22 @@ int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int 
 /* colsum_out (TN only, optional): [M] floats receiving sum_k A[k, m] -- the bias gradient of the Linear whose weight gradient
  * the call computes (dW = dY^T . X, db = column sums of dY), formed inside the same kernel (+)= with `accumulate`; with
  * splits > 1 the workspace must hold splits * (M * N + M) floats. */
+/* segmm_gemm_p with a PRODUCT COUNT (opt-in mixed precision).  products = 3: segmm_gemm_p itself, which is this call with 3 --
+ * same launcher, same kernels, same bits.  products = 1: every plane operand is its hi term, x ~= hi / s (11-bit significand:
+ * relative representation error <= 2^-11 while hi is a normal fp16 number); one v_mfma_f32_16x16x32_f16 per k-block, fp32
+ * accumulate; the column sums are sum hi / s.  Everything around the products is unchanged: the P32 operands (the lo halves are
+ * staged and not read), the operand-state verdicts and the fp32 fallback (split at the exact scale, then one product as well), the
+ * epilogue, the outputs (plane outputs carry both planes of the fp32 result), split-K and the combine.  Any other value is an error
+ * return that names it, never a launch.  The choice of kernel does not depend on `products`; a launch that falls through to a
+ * round-2 kernel (gemm_pl_nt / gemm_pl_tn: row-scaled outputs, a residual together with a d-activation, an extent >= 2^31, TN
+ * shapes that are no whole 128 x 256 tiles, the PL_VAR / TN_VAR settings that ask for them) RUNS WITH THREE PRODUCTS whatever is
+ * passed.  A repair launch passes the `products` of the launch it repairs. */
+int segmm_gemm_pq(int layout, int M, int N, int K, const uint16_t* a_planes, int lda2, const float* a_hdr, const float* a_f32, int ldaf,
+                  const uint16_t* b_planes, int ldb2, const float* b_hdr, const float* b_f32, int ldbf, float* C, int ldc,
+                  uint16_t* c_planes, int ldc2, float* c_hdr, const float* c_scale_in, int write_c, const float* bias, const float* row_scale,
+                  const float* residual, int ldr, int res_period, int activation, float* aux, int ldaux, float drop_p,
+                  uint64_t seed, uint32_t site, int splits, float* workspace, int accumulate, float* colsum_out, int products,
+                  segmm_stream_t stream);
 /* fp32 [rows, cols] (row stride ld) -> P32 planes.  mode 0: exact scale from the header's partial maxima (complete when
  * this runs), written to hdr[0], flag cleared.  mode 1: scale = hdr[0] as given; maxima and flag folded into hdr. */
 int segmm_split_p32(const float* x, int64_t rows, int cols, int ld, uint16_t* planes, int ld2, float* hdr, int mode,

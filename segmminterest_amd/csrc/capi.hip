@@ -840,12 +840,16 @@ int segmm_gemm_h(int layout, int M, int N, int K, const float* A, int lda, const
                      a_amax, a_namax, b_amax, b_namax, c_amax, stream);
 }
 
-/* ---- plane-operand GEMM (gemm_planes.h) */
-int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int lda2, const float* a_hdr, const float* a_f32, int ldaf,
-                 const uint16_t* b_planes, int ldb2, const float* b_hdr, const float* b_f32, int ldbf, float* C, int ldc,
-                 uint16_t* c_planes, int ldc2, float* c_hdr, const float* c_scale_in, int write_c, const float* bias, const float* row_scale,
-                 const float* residual, int ldr, int res_period, int activation, float* aux, int ldaux, float drop_p,
-                 uint64_t seed, uint32_t site, int splits, float* workspace, int accumulate, float* colsum_out, segmm_stream_t stream) {
+/* ---- plane-operand GEMM (gemm_planes.h).  `products` (3 or 1) picks the instantiation of the round-3 / round-6 kernels only: the
+ * choice of kernel below never reads it, and the round-2 kernels run with three products whatever it says. */
+int segmm_gemm_pq(int layout, int M, int N, int K, const uint16_t* a_planes, int lda2, const float* a_hdr, const float* a_f32, int ldaf,
+                  const uint16_t* b_planes, int ldb2, const float* b_hdr, const float* b_f32, int ldbf, float* C, int ldc,
+                  uint16_t* c_planes, int ldc2, float* c_hdr, const float* c_scale_in, int write_c, const float* bias, const float* row_scale,
+                  const float* residual, int ldr, int res_period, int activation, float* aux, int ldaux, float drop_p,
+                  uint64_t seed, uint32_t site, int splits, float* workspace, int accumulate, float* colsum_out, int products,
+                  segmm_stream_t stream) {
+    SEGMM_REQUIRE(products == 1 || products == 3, "gemm_pq: products %d (1 = hi . hi, 3 = hl + lh + hh)", products);
+    const bool one = products == 1;
     SEGMM_REQUIRE(layout == 0 || layout == 2, "gemm_p: layout %d (0 = NT, 2 = TN)", layout);
     SEGMM_REQUIRE(!colsum_out || layout == 2, "gemm_p: colsum_out is an output of the TN form");
     SEGMM_REQUIRE(a_planes && b_planes && a_hdr && b_hdr, "gemm_p: null plane operand / header");
@@ -914,7 +918,8 @@ int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int 
             // SEGMM_PL_VAR=44 forces it for every launch (tests, A/B)
             if (fits && (pl_var == 44 || (pl_var == 4 && K >= 768 && N >= 768))) {
                 g.nbm = (M + P4_BM - 1) / P4_BM; g.nbn = (N + P4_BN - 1) / P4_BN;
-                hipLaunchKernelGGL(gemm_pl_nt4, dim3(g.nbm * g.nbn), dim3(256), 0, s, g, q);
+                if (one) hipLaunchKernelGGL(gemm_pl_nt4<1>, dim3(g.nbm * g.nbn), dim3(256), 0, s, g, q);
+                else hipLaunchKernelGGL(gemm_pl_nt4<3>, dim3(g.nbm * g.nbn), dim3(256), 0, s, g, q);
                 LAUNCH_CHECK();
                 return 0;
             }
@@ -937,9 +942,13 @@ int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int 
                 g.nbm = (M + PBM - 1) / PBM; g.nbn = (N + 64 * best - 1) / (64 * best);
                 const dim3 grid(g.nbm * g.nbn);
                 // (the tile width of a repair launch need not match the first launch's: both write whole elements)
-                if (best == 4) hipLaunchKernelGGL(gemm_pl_nt8<4>, grid, dim3(512), 0, s, g, q);
-                else if (best == 3) hipLaunchKernelGGL(gemm_pl_nt8<3>, grid, dim3(512), 0, s, g, q);
-                else hipLaunchKernelGGL(gemm_pl_nt8<2>, grid, dim3(512), 0, s, g, q);
+                if (one) {
+                    if (best == 4) hipLaunchKernelGGL((gemm_pl_nt8<4, 1>), grid, dim3(512), 0, s, g, q);
+                    else if (best == 3) hipLaunchKernelGGL((gemm_pl_nt8<3, 1>), grid, dim3(512), 0, s, g, q);
+                    else hipLaunchKernelGGL((gemm_pl_nt8<2, 1>), grid, dim3(512), 0, s, g, q);
+                } else if (best == 4) hipLaunchKernelGGL((gemm_pl_nt8<4, 3>), grid, dim3(512), 0, s, g, q);
+                else if (best == 3) hipLaunchKernelGGL((gemm_pl_nt8<3, 3>), grid, dim3(512), 0, s, g, q);
+                else hipLaunchKernelGGL((gemm_pl_nt8<2, 3>), grid, dim3(512), 0, s, g, q);
                 LAUNCH_CHECK();
                 return 0;
             }
@@ -999,9 +1008,12 @@ int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int 
     const bool tn8 = !tn4 && fits8 && (tn_var == 8 || tn_var == 88 || tn_var == 4);
     if (tn4) {
         g.nbm = M / P4_BM; g.nbn = N / P4_BN;
-        hipLaunchKernelGGL(gemm_pl_tn4, dim3(g.nbm * g.nbn, 1, splits), dim3(256), 0, s, g, q);
-    } else if (tn8) hipLaunchKernelGGL(gemm_pl_tn8, dim3(g.nbm * g.nbn, 1, splits), dim3(512), 0, s, g, q);
-    else hipLaunchKernelGGL(gemm_pl_tn, dim3(g.nbm * g.nbn, 1, splits), dim3(512), 0, s, g, q);
+        if (one) hipLaunchKernelGGL(gemm_pl_tn4<1>, dim3(g.nbm * g.nbn, 1, splits), dim3(256), 0, s, g, q);
+        else hipLaunchKernelGGL(gemm_pl_tn4<3>, dim3(g.nbm * g.nbn, 1, splits), dim3(256), 0, s, g, q);
+    } else if (tn8) {
+        if (one) hipLaunchKernelGGL(gemm_pl_tn8<1>, dim3(g.nbm * g.nbn, 1, splits), dim3(512), 0, s, g, q);
+        else hipLaunchKernelGGL(gemm_pl_tn8<3>, dim3(g.nbm * g.nbn, 1, splits), dim3(512), 0, s, g, q);
+    } else hipLaunchKernelGGL(gemm_pl_tn, dim3(g.nbm * g.nbn, 1, splits), dim3(512), 0, s, g, q);
     LAUNCH_CHECK();
     if (splits > 1) {          // one combine launch for the slabs AND the folded column sums
         const long long n4 = (long long)M * (N / 4);
@@ -1012,6 +1024,16 @@ int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int 
         LAUNCH_CHECK();
     }
     return 0;
+}
+
+int segmm_gemm_p(int layout, int M, int N, int K, const uint16_t* a_planes, int lda2, const float* a_hdr, const float* a_f32, int ldaf,
+                 const uint16_t* b_planes, int ldb2, const float* b_hdr, const float* b_f32, int ldbf, float* C, int ldc,
+                 uint16_t* c_planes, int ldc2, float* c_hdr, const float* c_scale_in, int write_c, const float* bias, const float* row_scale,
+                 const float* residual, int ldr, int res_period, int activation, float* aux, int ldaux, float drop_p,
+                 uint64_t seed, uint32_t site, int splits, float* workspace, int accumulate, float* colsum_out, segmm_stream_t stream) {
+    return segmm_gemm_pq(layout, M, N, K, a_planes, lda2, a_hdr, a_f32, ldaf, b_planes, ldb2, b_hdr, b_f32, ldbf, C, ldc, c_planes, ldc2, c_hdr,
+                         c_scale_in, write_c, bias, row_scale, residual, ldr, res_period, activation, aux, ldaux, drop_p, seed, site, splits,
+                         workspace, accumulate, colsum_out, 3, stream);
 }
 
 int segmm_split_p32(const float* x, int64_t rows, int cols, int ld, uint16_t* planes, int ld2, float* hdr, int mode, segmm_stream_t stream) {

@@ -67,7 +67,11 @@ __device__ __forceinline__ void wait_lgkm() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// PROD: matrix-core products per k32 block.  3: hl + lh + hh (fp32-accurate, the default).  1: hh only -- every operand is its hi
+// term (ordinary fp16 mixed precision); the lo fragments are staged (same P32 rows, same DMA pieces and counted waits) but never read.
+template <int PROD>
 __global__ __launch_bounds__(256, 2) void gemm_pl_nt4(const GemmArgs p, const PGemmX q) {
+    static_assert(PROD == 1 || PROD == 3, "one product (hi . hi) or three (hl + lh + hh)");
     constexpr int NJ = 4;
     __shared__ __attribute__((aligned(16))) char smem[P4_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -185,17 +189,19 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_nt4(const GemmArgs p, const PG
     f32x4 bh[NJ], bl[NJ], ah[2], al[2];
     auto rdA = [&](const char* st, int i, int buf) {
         ah[buf] = *(const f32x4*)(st + fr[0] + i * 2048);
-        al[buf] = *(const f32x4*)(st + fr[1] + i * 2048);
+        if constexpr (PROD == 3) al[buf] = *(const f32x4*)(st + fr[1] + i * 2048);
     };
     auto rdB = [&](int j, const char* lo_half, const char* hi_half) {          // rows 0-31 / 32-63 of the wave's B rows
         const char* b = ((j >> 1) ? hi_half : lo_half) + (j & 1) * 2048;
         bh[j] = *(const f32x4*)(b + fr[0]);
-        bl[j] = *(const f32x4*)(b + fr[1]);
+        if constexpr (PROD == 3) bl[j] = *(const f32x4*)(b + fr[1]);
     };
     auto mma1 = [&](int r, int j, int buf) {
         f32x4 c = acc[r][j];
-        c = mfma16(bh[j], al[buf], c);          // (B fragment, A fragment): the accumulator tile is C^T
-        c = mfma16(bl[j], ah[buf], c);
+        if constexpr (PROD == 3) {
+            c = mfma16(bh[j], al[buf], c);          // (B fragment, A fragment): the accumulator tile is C^T
+            c = mfma16(bl[j], ah[buf], c);
+        }
         c = mfma16(bh[j], ah[buf], c);
         acc[r][j] = c;
     };
@@ -336,7 +342,9 @@ __device__ __forceinline__ void lds_dma16_asm(u32x4_t r, const void* lds_wave_ba
 #endif
 }
 
+template <int PROD>          // products per k32 block, as in gemm_pl_nt4; the column sums take the hi term alone at PROD = 1
 __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PGemmX q) {
+    static_assert(PROD == 1 || PROD == 3, "one product (hi . hi) or three (hl + lh + hh)");
     constexpr int NJ = 4;
     __shared__ __attribute__((aligned(16))) char smem[P4_LDS];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -400,17 +408,19 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
     f32x4 bh[NJ], bl[NJ], ah[2], al[2];
     auto rdA = [&](const char* st, int i, int buf) {
         ah[buf] = lds_tr8<2048>(st + xa(i, 0));
-        al[buf] = lds_tr8<2048>(st + xa(i, 1));
+        if constexpr (PROD == 3) al[buf] = lds_tr8<2048>(st + xa(i, 1));
     };
     // B: token octets 0, 1 (lanes lq < 2) in half `h0`, octets 2, 3 in half `h1`: a per-lane base
     auto rdB = [&](int j, const char* lane_half) {
         bh[j] = lds_tr8<1024>(lane_half + xb(j, 0));
-        bl[j] = lds_tr8<1024>(lane_half + xb(j, 1));
+        if constexpr (PROD == 3) bl[j] = lds_tr8<1024>(lane_half + xb(j, 1));
     };
     auto mma1 = [&](int r, int j, int buf) {
         f32x4 c = acc[r][j];
-        c = mfma16(bh[j], al[buf], c);
-        c = mfma16(bl[j], ah[buf], c);
+        if constexpr (PROD == 3) {
+            c = mfma16(bh[j], al[buf], c);
+            c = mfma16(bl[j], ah[buf], c);
+        }
         c = mfma16(bh[j], ah[buf], c);
         acc[r][j] = c;
     };
@@ -418,7 +428,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pl_tn4(const GemmArgs p, const PG
     auto colsum1 = [&](int i, int buf) {          // the column sums of A tile i ride along in wave i >> 1 of the first column tile's workgroup
         if ((i >> 1) == wn) {
             f32x4 cb = accb[i & 1];
-            cb = mfma16(ones, al[buf], cb);
+            if constexpr (PROD == 3) cb = mfma16(ones, al[buf], cb);
             cb = mfma16(ones, ah[buf], cb);
             accb[i & 1] = cb;
         }

@@ -46,9 +46,12 @@ namespace segmm {
 __device__ __forceinline__ f32x4 mfma16(f32x4 a, f32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-template <int NJ>
+// PROD: matrix-core products per k32 block.  3: hl + lh + hh (fp32-accurate, the default).  1: hh only -- every operand is its hi
+// term (ordinary fp16 mixed precision); the lo fragments are staged (same P32 rows, same pieces and counted waits) but never read.
+template <int NJ, int PROD>
 __global__ __launch_bounds__(512, 2) void gemm_pl_nt8(const GemmArgs p, const PGemmX q) {
     static_assert(NJ >= 2 && NJ <= 4, "tile widths 128, 192, 256");
+    static_assert(PROD == 1 || PROD == 3, "one product (hi . hi) or three (hl + lh + hh)");
     constexpr int BNW = 64 * NJ;                                         // tile columns
     // 128 KB: two stages x (A 32 KB | B 16 NJ KB); + 32 KB: a 16-row x 256-byte transpose patch per wave for the epilogue's stores
     __shared__ __attribute__((aligned(16))) char smem[2 * PSTAGE + 8 * 4096];
@@ -138,14 +141,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_nt8(const GemmArgs p, const PG
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             ah[i] = *(const f32x4*)(st + fa[0] + (mh * 4 + i) * 2048);
-            al[i] = *(const f32x4*)(st + fa[1] + (mh * 4 + i) * 2048);
+            if constexpr (PROD == 3) al[i] = *(const f32x4*)(st + fa[1] + (mh * 4 + i) * 2048);
         }
     };
     auto readB = [&](const char* st) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             bh[j] = *(const f32x4*)(st + fb[0] + j * 2048);
-            bl[j] = *(const f32x4*)(st + fb[1] + j * 2048);
+            if constexpr (PROD == 3) bl[j] = *(const f32x4*)(st + fb[1] + j * 2048);
         }
     };
     auto mma = [&](auto mh_tag) {
@@ -156,8 +159,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_nt8(const GemmArgs p, const PG
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 f32x4 c = acc[mh * 4 + i][j];
-                c = mfma16(bh[j], al[i], c);          // (B fragment, A fragment): the accumulator tile is C^T
-                c = mfma16(bl[j], ah[i], c);
+                if constexpr (PROD == 3) {
+                    c = mfma16(bh[j], al[i], c);          // (B fragment, A fragment): the accumulator tile is C^T
+                    c = mfma16(bl[j], ah[i], c);
+                }
                 c = mfma16(bh[j], ah[i], c);
                 acc[mh * 4 + i][j] = c;
             }
@@ -246,7 +251,9 @@ namespace segmm {
 // The bias gradient (column sums of A over k) rides along in the workgroups of the first column tile: wave (wm, wn) adds
 // one MFMA pair per phase against an all-ones fragment for its m-tile wn.  Output: split-K slabs (plain float4 stores from the
 // accumulators, C^T trick as in gemm_pl_nt8) combined by splitk_reduce, or C itself for a single split.
+template <int PROD>          // products per k32 block, as in gemm_pl_nt8; the column sums take the hi term alone at PROD = 1
 __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PGemmX q) {
+    static_assert(PROD == 1 || PROD == 3, "one product (hi . hi) or three (hl + lh + hh)");
     // two stages x (A: 32 tokens x 1 KB | B: 32 tokens x 1 KB) + a 4 KB transpose patch per wave for the output stores
     __shared__ __attribute__((aligned(16))) char smem[2 * PSTAGE + 8 * 4096];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -332,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             ah[i] = lds_tr8<4096>(sa_ + fr.x[2 * (i >> 1)] + fr.h[i & 1]);
-            al[i] = lds_tr8<4096>(sa_ + fr.x[2 * (i >> 1) + 1] + fr.h[i & 1]);
+            if constexpr (PROD == 3) al[i] = lds_tr8<4096>(sa_ + fr.x[2 * (i >> 1) + 1] + fr.h[i & 1]);
         }
     };
     auto readB = [&](const char* st) {
@@ -340,7 +347,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             bh[j] = lds_tr8<4096>(sb_ + fr.x[2 * (j >> 1)] + fr.h[j & 1]);
-            bl[j] = lds_tr8<4096>(sb_ + fr.x[2 * (j >> 1) + 1] + fr.h[j & 1]);
+            if constexpr (PROD == 3) bl[j] = lds_tr8<4096>(sb_ + fr.x[2 * (j >> 1) + 1] + fr.h[j & 1]);
         }
     };
     auto mma = [&](auto mh_tag, auto cs_tag) {
@@ -352,10 +359,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
             // the column sums of this wave's A tile i = wn of the phase (a wave-uniform choice among fragments it holds anyway)
             f32x4 cb = accb[mh];
             switch (wn) {
-                case 0: cb = mfma16(ones, al[0], cb); cb = mfma16(ones, ah[0], cb); break;
-                case 1: cb = mfma16(ones, al[1], cb); cb = mfma16(ones, ah[1], cb); break;
-                case 2: cb = mfma16(ones, al[2], cb); cb = mfma16(ones, ah[2], cb); break;
-                default: cb = mfma16(ones, al[3], cb); cb = mfma16(ones, ah[3], cb); break;
+                case 0: if constexpr (PROD == 3) cb = mfma16(ones, al[0], cb); cb = mfma16(ones, ah[0], cb); break;
+                case 1: if constexpr (PROD == 3) cb = mfma16(ones, al[1], cb); cb = mfma16(ones, ah[1], cb); break;
+                case 2: if constexpr (PROD == 3) cb = mfma16(ones, al[2], cb); cb = mfma16(ones, ah[2], cb); break;
+                default: if constexpr (PROD == 3) cb = mfma16(ones, al[3], cb); cb = mfma16(ones, ah[3], cb); break;
             }
             accb[mh] = cb;
         }
@@ -364,8 +371,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pl_tn8(const GemmArgs p, const PG
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 f32x4 c = acc[mh * 4 + i][j];
-                c = mfma16(bh[j], al[i], c);
-                c = mfma16(bl[j], ah[i], c);
+                if constexpr (PROD == 3) {
+                    c = mfma16(bh[j], al[i], c);
+                    c = mfma16(bl[j], ah[i], c);
+                }
                 c = mfma16(bh[j], ah[i], c);
                 acc[mh * 4 + i][j] = c;
             }

@@ -132,6 +132,32 @@ def backbone_layout(prefix: str, bb) -> Tuple[List[Tuple[str, List[List[str]]]],
     return buckets
 
 
+MP_ROLES = ("forward", "dgrad", "wgrad")          # forward linear (NT, repair launch included) | input gradient (NT on W^T planes) | weight gradient (TN)
+ALL_PRODUCTS = {r: 3 for r in MP_ROLES}
+
+
+def resolve_mixed_precision(arg):
+    """``Trainer(mixed_precision=...)`` -> None (off) or the resolved {"forward", "dgrad", "wgrad"} -> bool dict.  True: every role;
+    a dict: its keys (default True), unknown keys refused by name; all roles False is off."""
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        arg = {}
+    if not isinstance(arg, dict):
+        raise TypeError("mixed_precision: None, a bool or a dict of %s, not %r" % (", ".join(MP_ROLES), arg))
+    unknown = sorted(str(k) for k in arg if k not in MP_ROLES)
+    if unknown:
+        raise ValueError("mixed_precision: unknown key(s) %s (roles: %s)" % (", ".join(unknown), ", ".join(MP_ROLES)))
+    out = {r: bool(arg.get(r, True)) for r in MP_ROLES}
+    if not any(out.values()):
+        return None
+    if H.GEMM_ENGINE != H.ENGINE_F16X3P:
+        name = {H.ENGINE_F32: "f32", H.ENGINE_BF16X6: "bf16x6", H.ENGINE_F16X3: "f16x3"}[H.GEMM_ENGINE]
+        raise RuntimeError("mixed_precision needs the plane GEMM engine SEGMM_GEMM=f16x3p: the engine in force, SEGMM_GEMM=%s, has no "
+                           "planes to take one product of" % name)
+    return out
+
+
 class ParamStore:
     """All parameters of a model re-pointed into ONE flat fp32 buffer: live tensors first (in
     backward-completion order, bucketed), dead tensors after.  ``nn.Parameter.data`` become views, so
@@ -194,8 +220,21 @@ class ParamStore:
         self._planes_key = None
         self._transposes: List[Tuple[int, int, int]] = []
         self._plane_ranges: List[Tuple[int, int]] = []
+        # opt-in mixed precision (Trainer(mixed_precision=...)): None, or {"forward", "dgrad", "wgrad"} -> bool, the roles whose plane
+        # GEMMs multiply one product (hi . hi) in TRAINING passes; ``products`` is what is in force for the pass being enqueued
+        self.mixed_precision: Optional[Dict[str, bool]] = None
+        self.in_train_step = False          # set by the trainer around an optimisation step (Trainer._step_scope)
+        self.products = dict(ALL_PRODUCTS)
 
     MAX_SITES = 1024
+
+    def set_pass_products(self, step_pass: bool):
+        """Called at the head of a backbone's forward and backward: the product count of each GEMM role for that pass.  Only the
+        passes of the trainer's optimisation step (``step_pass``) take the setting; every other forward -- eval_step, the validation
+        and test passes, dump_logits, the EMA-applied passes -- runs three products: metrics and dumped logits are the fp32-accurate
+        forward of whatever weights were trained."""
+        mp = self.mixed_precision if step_pass else None
+        self.products = {r: 1 if (mp and mp[r]) else 3 for r in MP_ROLES}
 
     def site(self, name: str) -> int:
         i = self.site_index.get(name)
@@ -821,7 +860,7 @@ def _wgrad(store, dY, y_off, X, x_off, Mrows, n_out, n_in, gW, accumulate=False,
         splits = _splits_for_p(n_out, n_in, Mrows, store.split_target_p, store.split_target_few)
         ws = store.buf("splitk_ws_side" if store._on_side else "splitk_ws", (max(splits, 1) * (n_out * n_in + n_out),)) if splits > 1 else None
         H.gemm_p(H.LAYOUT_TN, n_out, n_in, Mrows, dY.pt(y_off, n_out), X.pt(x_off, n_in), gW, n_in, splits=splits, workspace=ws,
-                 accumulate=accumulate, colsum_out=gb)
+                 accumulate=accumulate, colsum_out=gb, products=store.products["wgrad"])
         return
     _needs_f32(dY, "the on-the-fly weight-gradient GEMM")
     _needs_f32(X, "the on-the-fly weight-gradient GEMM")
@@ -844,6 +883,7 @@ def _lin_fwd(store, M, N, K, X, wname, out, ldo, c_act=None, **kw):
     if out is None and not (plane and c_act is not None and c_act.po is not None):
         raise RuntimeError("a planes-only output needs the plane GEMM with a calibrated output site (%s)" % wname)
     if plane:
+        kw["products"] = store.products["forward"]          # (the repair launch passes the products of the launch it repairs)
         if c_act is not None and c_act.po is not None:
             H.gemm_p(H.LAYOUT_NT, M, N, K, X.pt(), w, out, ldo, c_pt=c_act.pt(), c_scale_ptr=c_act.scale_ptr, write_c=out is not None, **kw)
             if out is None:
@@ -866,6 +906,7 @@ def _lin_dgrad(store, M, n_in, n_out, dY, wname, out, c_act=None, **kw):
     k-contiguous), otherwise the NN layout on the fp32 weights."""
     wT = store.wTpt.get(wname) if store.engine_p else None
     if wT is not None and dY.planes is not None:
+        kw["products"] = store.products["dgrad"]
         if c_act is not None and c_act.po is not None:
             H.gemm_p(H.LAYOUT_NT, M, n_in, n_out, dY.pt(), wT, out, n_in, c_pt=c_act.pt(), c_scale_ptr=c_act.scale_ptr, **kw)
             c_act.filled = True
@@ -1015,6 +1056,8 @@ class BackboneRun:
         p_drop = float(bb.dropout_p) if train else 0.0
         p_inner = MLP_INNER_DROPOUT if train else 0.0
         self.p_drop, self.p_inner, self.seed = p_drop, p_inner, seed
+        self.step_pass = bool(st.in_train_step)
+        st.set_pass_products(self.step_pass)
         # (head weight, head bias, logits buffer) left by the model for a single-backbone Linear(d, 1) head: the output LayerNorm
         # of the last live layer then computes the raw logits too (_side_post); st._head_dot_done tells the head
         self._head_dot = st.__dict__.pop("_head_dot", None)
@@ -1553,6 +1596,7 @@ class BackboneRun:
         B, S, Lt, Mv, Mu = self.B, self.S, self.Lt, self.Mv, self.Mu
         dXv = d_vid_out.contiguous().view(-1, d)
         dXu = None
+        st.set_pass_products(self.step_pass)
         # The interest head (Linear(d, 1), single backbone, trainer's direct gradient delivery) hands over d_vid UNWRITTEN, with
         # (address, d logits per row, head weight) on the store: the first consumer -- the last layer's LayerNorm backward --
         # forms dl[row] * w[c] itself (segmm_layernorm_bwd_outer: one launch and a 63 MB round trip less on the critical chain

@@ -121,8 +121,12 @@ class Trainer(EvalPasses):
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
                  feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None,
-                 param_groups=None, ema=None, lazy_tables=None):
+                 param_groups=None, ema=None, lazy_tables=None, mixed_precision=None):
         self.model = model
+        # mixed_precision=None | False | True | dict(forward=True, dgrad=True, wgrad=True): the plane GEMMs of the named roles multiply
+        # ONE product (hi . hi: fp16 operands, fp32 accumulate) in the passes of the optimisation step; master weights, AdamW and
+        # every evaluation pass are untouched.  Lives on the model's ParamStore, where the GEMM helpers of engine.py read it.
+        mixed_precision = E.resolve_mixed_precision(mixed_precision)          # (a malformed spec is refused before the model is touched)
         # lazy_tables=None | True | dict(flush_every=F): lazy exact AdamW of the item-id tables (FusedAdamW; _tables_early) -- a step
         # reads and writes only the batch's rows of the table.  Under data parallelism the rows touched are those of ALL ranks, known
         # only after the row exchange: that takes the opt-in lazy_tables=dict(data_parallel=True) -- the rank's own rows catch up at
@@ -171,6 +175,7 @@ class Trainer(EvalPasses):
         self.comm = comm if comm is not None else DPComm()
         self.overlap = overlap
         st = model._store
+        st.mixed_precision = mixed_precision
         model._dp_hook = self.comm.global_label_stats if self.comm.active else None
         model._dp_stats_bufs = self.comm.label_stats_buffers if self.comm.active else None
         st.bucket_hook = self._on_bucket if self.comm.active else None
@@ -211,6 +216,16 @@ class Trainer(EvalPasses):
             if self.opt.schedule is not None:
                 self.opt._install_schedule()
             st.live_seed = H.LIVE_SEED | 0x5E6D0001          # the (constant) seed argument of every dropout launch
+
+    @property
+    def mixed_precision(self):
+        """The resolved setting: ``None`` (off), or a dict role -> bool over ``forward``, ``dgrad``, ``wgrad``."""
+        mp = self.model._store.mixed_precision
+        return None if mp is None else dict(mp)
+
+    @mixed_precision.setter
+    def mixed_precision(self, value):
+        self.model._store.mixed_precision = E.resolve_mixed_precision(value)
 
     def _on_bucket(self, name, after_side=False):
         if self._micro_on:          # a micro-batched step reduces the SUMMED gradient once, after its last pass (_train_step_micro)
@@ -518,6 +533,7 @@ class Trainer(EvalPasses):
             H.step_advance(*self.opt.betas)          # optimizer step), fresh header rows
             st.hdr_step_begin()
         st._trusted = False
+        st.in_train_step = True          # (the step's passes take Trainer(mixed_precision=...); evaluation passes never run in here)
         try:
             yield
             r = self.__dict__.get("_recorded")
@@ -525,6 +541,7 @@ class Trainer(EvalPasses):
                 r["prev_batch"] = batch          # a recorded step that follows names this step's batch as "the previous one"
         finally:
             st._trusted = False
+            st.in_train_step = False
             model.__dict__.pop("_stats_pre", None)          # (a step that failed before its forward must not leave this batch's statistics behind)
             if self.device_state:
                 st.hdr_step_end()          # evaluation passes between steps draw their headers from the wrapping ring
@@ -895,7 +912,9 @@ class Trainer(EvalPasses):
         lr = self.opt.lr if self.opt.schedule is None else H.LIVE_LR
         # (the recorded segmm_ema_update carries the EMA's weight and warm-up flag by value)
         return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm, self.opt.group_table(),
-                None if self.ema is None else self.ema.hyper())
+                None if self.ema is None else self.ema.hyper(),
+                # (the recorded plane GEMMs carry their product count in the command: segmm_gemm_p or segmm_gemm_pq(..., 1))
+                None if self.mixed_precision is None else tuple(sorted(self.mixed_precision.items())))
 
     def run_recorded(self, batch: Dict[str, torch.Tensor], timed=None):
         """One training step from the recorded launch sequences (see :meth:`record`): patch the batch's addresses, then one C
