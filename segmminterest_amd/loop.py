@@ -54,7 +54,9 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
     launch by launch (they calibrate the delayed scales), the next step is RECORDED while it runs (``Trainer.record`` with the
     previous batch: no extra optimisation step), every later batch of the same shapes is enqueued from the recorded launch
     sequences (``run_recorded``: one C call per phase, bit-identical to the eager step); a batch of another shape (the short last
-    batch of an epoch) takes the eager step.  Every batch is still stepped on exactly once, in order.
+    batch of an epoch) takes the eager step.  Every batch is still stepped on exactly once, in order.  The replay that follows
+    such an eager step clears what that step left for its successor (id mode: the table-gradient rows it scattered into) by that
+    step's own row list, single process or data parallel: image mode and id mode end bit-identical to ``recorded=False``.
     ``lr_plateau`` (a dict of :class:`PlateauLR` arguments, e.g. ``dict(factor=0.5, patience=2, min_lr=1e-6)``; ``mode`` defaults to
     "max", the sense of the early-stop tests): reduce-on-plateau with torch.optim.lr_scheduler.ReduceLROnPlateau's rules, fed after
     every validation of the loop the number early stopping reads -- every data-parallel rank decides alike -- and acting through

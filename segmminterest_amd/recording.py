@@ -5,8 +5,10 @@ A recording is a plain dict: ``phases`` ([(Phase, Cmd array) | (host action, Non
 the recorded pointers name: host structs, the private memory pool of the recorded run), ``relocs`` ([(Cmd array, command, argument
 slot, batch key, byte offset, lag)]: the pointer slots that name a batch tensor; lag 1 = the PREVIOUS batch's), ``spans``
 (:func:`batch_shapes` of the recorded batch), ``main`` / ``events`` / ``table`` (the stream it replays on, the stream table of
-``hipabi.run_phase``) and ``n_cmds``.  Its owner adds what only it knows (the step: ``prev_batch``, ``tab_keys``, ``hyper``,
-``out``; the validation batch: its named tail commands, ``cfg``, ``n_replays``)."""
+``hipabi.run_phase``), ``n_cmds`` and, made on the first replay, ``reloc_keys`` (the (batch key, lag) pairs of ``relocs``: the
+tensors :func:`check_shapes` looks at before every replay).  Its owner adds what only it knows (the step: ``prev_batch`` -- None
+behind a step that was no replay of it --, ``tab_keys``, ``hdr_cleared`` / ``hdr_used``, ``hyper``, ``out``; the validation batch:
+its named tail commands, ``cfg``, ``n_replays``)."""
 from __future__ import annotations
 
 import contextlib
@@ -78,12 +80,36 @@ def rebase(r, batch, prev=None):
         arr[ci].a[ai].p = (prev if lag else batch)[k].data_ptr() + off
 
 
-def replay(r, who, what, batch, prev=None, timed=None):
+def check_shapes(r, who, what, batch, prev=None):
+    """Refuses a replay one of whose pointer slots would name a tensor of another shape or dtype than the recorded one: every
+    recorded count, stride and byte size travels by value, so such a launch reads or writes outside the tensor.  Looks at the
+    tensor each slot is about to name -- ``prev`` for lag 1, ``batch`` for lag 0 -- and at nothing else of the batches."""
+    spans = r.get("spans")
+    if spans is None:
+        return
+    keys = r.get("reloc_keys")
+    if keys is None:
+        keys = r["reloc_keys"] = sorted({(k, lag) for _, _, _, k, _, lag in r["relocs"]})
+    for k, lag in keys:
+        src = prev if lag else batch
+        v = src.get(k) if src is not None else None
+        if not torch.is_tensor(v) or (tuple(v.shape), v.dtype) != spans[k] or not v.is_contiguous():
+            got = "missing" if not torch.is_tensor(v) else "%s %s" % (tuple(v.shape), v.dtype)
+            raise RuntimeError("%s: %s[%r] is %s, the %s was recorded for %s %s" % (who, "the previous batch" if lag else "batch", k, got, what,
+                                                                                   spans[k][0], spans[k][1]))
+
+
+def replay(r, who, what, batch, prev=None, timed=None, before=None):
     """Enqueues the recording ``r`` on ``batch``: refuses a current stream other than the recorded one (``who`` / ``what``: the
-    caller and "step" / "validation batch" in the message) BEFORE anything of ``r`` is touched, re-bases the batch pointers, then
-    one C call per phase.  ``timed``: see ``Trainer.run_recorded``."""
+    caller and "step" / "validation batch" in the message) and a tensor of another shape behind a pointer slot
+    (:func:`check_shapes`) BEFORE anything of ``r`` is touched, re-bases the batch pointers, then one C call per phase.
+    ``before``: launches of the caller's that belong ahead of the first phase, enqueued once the checks have passed.
+    ``timed``: see ``Trainer.run_recorded``."""
     if H._stream() != r["main"]:
         raise RuntimeError("%s: the current stream is not the stream the %s was recorded on" % (who, what))
+    check_shapes(r, who, what, batch, prev)
+    if before is not None:
+        before()
     rebase(r, batch, prev)
     table = r["table"]
     if timed is not None:

@@ -521,8 +521,12 @@ class Trainer(EvalPasses):
     @contextlib.contextmanager
     def _step_scope(self, batch):
         """Head and tail of one optimisation step on ``batch``, plain or micro-batched: the step's first launches on entry; on exit,
-        however the body ends, the store leaves the step, and a completed eager step is noted as the recording's previous batch."""
+        however the body ends, the store leaves the step.  An eager step -- of any shape, completed or not -- tells the recording
+        that the step before its next replay is not one of its own (:meth:`run_recorded` then clears the id-table gradients itself)."""
         model, st = self.model, self.model._store
+        r = self.__dict__.get("_recorded")
+        if r is not None and H.RECORDER is None:
+            r["prev_batch"] = None
         if self.device_state:
             H.step_bind(self._step_state)          # (a host-side pointer: the launches below carry it in their arguments)
         if model.training != bool(self.dropout):
@@ -536,9 +540,6 @@ class Trainer(EvalPasses):
         st.in_train_step = True          # (the step's passes take Trainer(mixed_precision=...); evaluation passes never run in here)
         try:
             yield
-            r = self.__dict__.get("_recorded")
-            if r is not None and H.RECORDER is None:
-                r["prev_batch"] = batch          # a recorded step that follows names this step's batch as "the previous one"
         finally:
             st._trusted = False
             st.in_train_step = False
@@ -833,6 +834,13 @@ class Trainer(EvalPasses):
         addresses are patched per step.  ``run_recorded(batch)`` then enqueues a step with one C call per phase
         (segmm_step_begin, segmm_embed_fwd, segmm_layer_fwd, ...): the eager two-stream schedule without the per-launch host
         work.  Results are bit-identical to ``train_step`` in the same mode.
+        Eager steps of any shape (``train_step``: the short last batch of an epoch) and validation passes may run between replays.
+        What the recorded step takes over from the step before it -- id mode: the list of the table-gradient rows that step
+        scattered into, by which this one clears them; the site-header rows it used -- is right as recorded only behind a replay of
+        this recording (or the recorded step itself).  Behind any other step ``run_recorded`` clears both itself, from the host
+        state that step left, and points the recorded list at its own batch.  No replay names memory outside a tensor of the shape
+        it was recorded with: ``run_recorded`` checks every batch tensor a pointer is about to name, on the host, before it
+        launches.
         ``prev_batch``: the batch of the ``train_step`` that ran immediately before (same shapes, other tensors).  With it NO
         warm-up step runs -- the caller has already stepped (the sites are calibrated) -- so the only optimisation step ``record``
         takes is the recorded one, on ``batch``: what an epoch loop needs (:func:`fit` with ``recorded=True``)."""
@@ -861,6 +869,7 @@ class Trainer(EvalPasses):
             self.train_step(prev)
         self.opt.flush_tables()          # lazy tables: a flush is never part of a recording -- the recorded step starts with none pending
         aux = st.__dict__.get("_aux_stream")
+        hdr_cleared = st.__dict__.get("_arena_used", 0)          # the header rows the recorded step clears at its head (by value)
         with R.capture(st, st.side_stream().cuda_stream, aux.cuda_stream if aux is not None else 0) as cap:
             # The recorded step must carry the per-step weight split (segmm_wsplit_p32): ParamStore.refresh_planes skips it when the planes
             # are current -- which they are when an EVALUATION pass ran since the last optimizer step (it split the new weights itself).
@@ -870,15 +879,17 @@ class Trainer(EvalPasses):
             out = self.train_step(batch)
         # the tensors of the batch and of the one before it: every recorded pointer that falls inside one of them is re-based per step
         r = R.finish(cap, (batch, prev))
-        # host-side state of the eager path that names a batch tensor (id mode: the id list whose table-gradient rows the NEXT
-        # backward clears): kept current by run_recorded, so that eager steps and recorded steps can be mixed
+        # host-side state of the eager path (id mode: the id list whose table-gradient rows the NEXT backward clears): kept current
+        # by run_recorded, so that eager steps and recorded steps can be mixed.  A list that is a batch tensor is named by its key
+        # (every replay leaves its own batch's); any other list is a persistent buffer the replays fill again (data parallel: the
+        # gathered ids of DPComm.gather_rows) and is kept as the tensor itself -- a later eager step of another shape makes the
+        # communicator allocate new buffers, the recording goes on using these
         tab_keys = []
         for ek, (gptr, t) in getattr(st, "_tab_rows", {}).items():
-            for k in r["spans"]:
-                v = batch[k]
-                if t.data_ptr() == v.data_ptr() and t.numel() * t.element_size() == v.numel() * v.element_size():
-                    tab_keys.append((ek, gptr, k))
-        r.update(prev_batch=batch, tab_keys=tab_keys, out=out, hyper=self._hyper())
+            k = next((k for k in r["spans"] if t.data_ptr() == batch[k].data_ptr()
+                      and t.numel() * t.element_size() == batch[k].numel() * batch[k].element_size()), None)
+            tab_keys.append((ek, gptr, k if k is not None else t))
+        r.update(prev_batch=batch, tab_keys=tab_keys, out=out, hyper=self._hyper(), hdr_cleared=hdr_cleared, hdr_used=st._arena_used)
         self._recorded = r
         return out
 
@@ -939,17 +950,45 @@ class Trainer(EvalPasses):
                 raise RuntimeError("run_recorded(): batch[%r] is %s %s, the step was recorded for %s %s" % (k, tuple(v.shape), v.dtype, sh, dt))
         if self.opt.lazy_flush_every is not None:
             self.opt.lazy_step_head()          # the host's periodic flush, between two replays
-        # (a wrong current stream is refused before a slot is patched: a refused call leaves the recording as it found it)
-        R.replay(r, "run_recorded()", "step", batch, r["prev_batch"], timed)
-        r["prev_batch"] = batch          # (also keeps the tensors a lag-1 pointer names alive until the next step has run)
-        # mirror the host side effects of the eager step (FusedAdamW.begin_step / end_step; the id list of the table rows this
-        # step's backward scattered into)
-        self.opt.step_count += 1
         st = self.model._store
+        # The recorded step clears the id-table gradients by the row list of the step before it: a lag-1 pointer into the previous
+        # batch with the recorded count, or (data parallel) the recording's own gathered-id buffer.  Both are right only behind a
+        # replay of this recording (or the recorded step itself).  Behind any other step -- an eager one, of whatever shape --
+        # the rows that step left are cleared here, by its own list, ahead of the first phase; the lag-1 slots then name THIS
+        # batch (the recorded shape), whose rows the recorded zero_rows finds clear already
+        prev, before = r["prev_batch"], None
+        if prev is None:
+            prev, before = batch, functools.partial(self._after_foreign_step, st, r)
+        # (a wrong current stream or a tensor of another shape behind a slot is refused before a slot is patched or anything is
+        # enqueued: a refused call leaves the recording as it found it)
+        R.replay(r, "run_recorded()", "step", batch, prev, timed, before=before)
+        r["prev_batch"] = batch          # (also keeps the tensors a lag-1 pointer names alive until the next step has run)
+        # mirror the host side effects of the eager step (FusedAdamW.begin_step / end_step; the id lists of the table rows this
+        # step's backward scattered into -- exactly those the recorded step left, nothing of an earlier eager step)
+        self.opt.step_count += 1
         st.fused_version += 1
-        for ek, gptr, k in r["tab_keys"]:
-            st._tab_rows[ek] = (gptr, batch[k].reshape(-1))
+        st._tab_rows = {ek: (gptr, batch[k].reshape(-1) if isinstance(k, str) else k) for ek, gptr, k in r["tab_keys"]}
+        # (the site-header rows this step wrote: the next eager step clears what the step before it used, ParamStore.hdr_step_begin)
+        st._arena_used = max(st._arena_used, r["hdr_used"])
         return r["out"]
+
+    def _after_foreign_step(self, st, r):
+        """Ahead of a replay that follows a step not of this recording: what the recorded step expects of the step before it, made so.
+        The dense id-table gradients are cleared of what the last backward scattered into them, the way the next eager backward
+        would (engine._embed_bwd): by the row list it left in ``st._tab_rows``, densely where it left none; the lists are used up.
+        The site-header rows that step used beyond the ones the recorded step clears itself (a micro-batched step of more passes)
+        are cleared too."""
+        if st._arena_used > r["hdr_cleared"]:
+            H.fill_zero(st._hdr_arena[r["hdr_cleared"]:st._arena_used])
+        mods = dict(self.model.named_modules())
+        for name in st.live_names:
+            if name.endswith(("vid_proj.weight", "usr_proj.weight")) and isinstance(mods.get(name.rsplit(".", 1)[0]), torch.nn.Embedding):
+                gtab = st.g(name)
+                ent = st._tab_rows.pop(name[:-len("_proj.weight")], None)
+                if ent is not None and ent[0] == gtab.data_ptr() and ent[1].device == gtab.device:
+                    H.zero_rows(gtab, ent[1])
+                else:
+                    H.fill_zero(gtab)
 
     def _param_hooks(self) -> bool:
         plist = self.__dict__.get("_hook_plist")
