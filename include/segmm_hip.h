@@ -479,6 +479,33 @@ int segmm_adamw_table_stamp(const int64_t* ids, int n_ids, int64_t n_rows, int32
 int segmm_adamw_table_lazy_rows(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                                 int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2, float eps,
                                 float weight_decay, int step, const float* coef, segmm_stream_t stream);
+/* The same with the weight average (segmm_ema_update) of the table kept exact; added under ABI version 30, nothing that existed
+ * changed.  A row's shadow obeys shadow_t = shadow_{t-1} + (p_t - shadow_{t-1}) w_t: it depends on the row's own p_t and on step
+ * t's weight only, so it is replayed WITH the row, in order, with segmm_ema_update's three rounded fp32 operations.  After a flush
+ * the shadow holds the bits of segmm_ema_update run over the densely stepped table after every step.  `shadow`: the table's
+ * n_rows x width floats of the EMA shadow, 16-byte aligned and disjoint from p.
+ * segmm_adamw_hist_push_ema: segmm_adamw_hist_push, and the entry's fourth float is w_t -- ema_weight, or with ema_warmup != 0
+ *   max(ema_weight, (float)(9.0 / (10.0 + (double)t))), t = step by value or the bound device step state's count: exactly the w of
+ *   segmm_ema_update(weight, warmup, step).  (segmm_adamw_hist_push goes on writing 0 there, the replays above go on ignoring it.)
+ *   The ring holds the weight each step USED: the decay may change between two steps without a flush.
+ * segmm_adamw_table_catchup_ema: segmm_adamw_table_catchup without flags (this mode runs no phase 1).  A claimed row replays, for
+ *   s = stamp + 1 .. target: the g = 0 AdamW step with the ring's entry of s, then shadow <- shadow + (p - shadow) w_s.  p, m, v and
+ *   shadow are each read once and written once.  ids == NULL: the flush.  Claim, duplicates, ids out of range and target as above.
+ * segmm_adamw_table_lazy_rows_ema: segmm_adamw_table_lazy_rows plus the shadow: the replay of old + 1 .. T - 1 as above, step T
+ *   with the row of g (coef, lr_scale as above), then shadow <- shadow + (p_T - shadow) w_T.  w_T is READ FROM THE RING's entry of
+ *   T: segmm_adamw_hist_push_ema for step T must have been enqueued on the same stream ahead of this call.  A row already at T is
+ *   neither read nor written.
+ * One lazy step T in this mode: catchup_ema(own ids, target T - 1) ahead of the forward; hist_push_ema(T); lazy_rows_ema(the
+ * step's ids, T); segmm_ema_update over everything but the table. */
+int segmm_adamw_hist_push_ema(float* hist, int cap, float lr, float beta1, float beta2, int step, float ema_weight, int ema_warmup,
+                              segmm_stream_t stream);
+int segmm_adamw_table_catchup_ema(float* p, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                  int32_t* stamps, const float* hist, int cap, int target, int relative, float lr_scale, float beta1,
+                                  float beta2, float eps, float weight_decay, segmm_stream_t stream);
+int segmm_adamw_table_lazy_rows_ema(float* p, const float* g, float* m, float* v, float* shadow, int64_t n_rows, int width,
+                                    const int64_t* ids, int n_ids, int32_t* stamps, const float* hist, int cap, float lr, float lr_scale,
+                                    float beta1, float beta2, float eps, float weight_decay, int step, const float* coef,
+                                    segmm_stream_t stream);
 /* Device-side step state, so that a whole training step (main_for_seq_leave_earlystop_SegMM.py:265-300) can be replayed from its
  * recorded launch sequences with unchanged kernel arguments: two dropout seed words and the optimizer's step count with its bias
  * corrections live in device memory -- a struct of segmm_step_state_bytes() bytes in CALLER-OWNED, 16-byte aligned device memory

@@ -2342,6 +2342,79 @@ int segmm_ema_update(float* shadow, const float* p, int64_t n, float weight, int
     return 0;
 }
 
+// ---- lazy exact AdamW with the EMA shadow replayed beside it (rowops.h; the checks of the three entry points they extend)
+int segmm_adamw_hist_push_ema(float* hist, int cap, float lr, float beta1, float beta2, int step, float ema_weight, int ema_warmup,
+                              segmm_stream_t stream) {
+    SEGMM_REQUIRE(hist && aligned16(hist) && cap >= 1, "adamw_hist_push_ema: ring pointer/alignment, cap=%d (>= 1)", cap);
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_hist_push_ema: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_hist_push_ema: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+    SEGMM_REQUIRE(ema_weight > 0.f && ema_weight <= 1.f, "adamw_hist_push_ema: ema_weight=%g (0 < weight <= 1; weight = 1 - decay)", (double)ema_weight);
+    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    SEGMM_REQUIRE(step > 0 || live, "adamw_hist_push_ema: no device-side step state");
+    hipLaunchKernelGGL(adamw_hist_push_ema_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamwHist*)hist, cap, step, lr, (float)bc1, (float)sqrt(bc2),
+                       ema_weight, ema_warmup ? 1 : 0, live);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// the shadow of a lazy table: 16-byte aligned and disjoint from the n_rows x width floats at p
+static int lazy_shadow_check(const char* who, const float* shadow, const float* p, int64_t n_rows, int width) {
+    SEGMM_REQUIRE(shadow && aligned16(shadow), "%s: shadow pointer/alignment", who);
+    const uintptr_t nb = (uintptr_t)n_rows * (uintptr_t)width * 4u, ps = (uintptr_t)shadow, pp = (uintptr_t)p;
+    SEGMM_REQUIRE(ps + nb <= pp || pp + nb <= ps, "%s: shadow overlaps p (they must be disjoint)", who);
+    return 0;
+}
+
+int segmm_adamw_table_catchup_ema(float* p, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                  int32_t* stamps, const float* hist, int cap, int target, int relative, float lr_scale, float beta1,
+                                  float beta2, float eps, float weight_decay, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && m && v && stamps && hist && aligned16(p) && aligned16(m) && aligned16(v) && aligned16(hist),
+                  "adamw_table_catchup_ema: pointer/alignment");
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_catchup_ema: width %% 4, sizes, cap >= 1");
+    if (const int rc = lazy_shadow_check("adamw_table_catchup_ema", shadow, p, n_rows, width)) return rc;
+    SEGMM_REQUIRE(relative ? (target == 0 || target == -1) : target >= 0,
+                  "adamw_table_catchup_ema: target=%d (relative=%d: >= 0 by value; 0 or -1 from the device-side step count)", target, relative);
+    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_catchup_ema: lr_scale=%g (finite, >= 0)", (double)lr_scale);
+    const long long n = ids ? (long long)n_ids : (long long)n_rows;
+    if (n == 0 || n_rows == 0) return 0;
+    const StepState* live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    long long blocks = (n + 3) / 4;          // one wave per row; the flush strides over a capped grid, as segmm_adamw_table_catchup's
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(adamw_table_catchup_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, m, v, shadow, (long long)n_rows,
+                       width, (const long long*)ids, n, (int*)stamps, (const AdamwHist*)hist, cap, target, live, lr_scale, beta1, beta2, eps,
+                       weight_decay);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_adamw_table_lazy_rows_ema(float* p, const float* g, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids,
+                                    int n_ids, int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && g && m && v && stamps && hist && (ids || n_ids == 0) && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) &&
+                      aligned16(hist),
+                  "adamw_table_lazy_rows_ema: pointer/alignment");
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_lazy_rows_ema: width %% 4, sizes, cap >= 1");
+    if (const int rc = lazy_shadow_check("adamw_table_lazy_rows_ema", shadow, p, n_rows, width)) return rc;
+    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_lazy_rows_ema: step=%d (>= 1, or -1: the device-side step state)", step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table_lazy_rows_ema: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_lazy_rows_ema: lr_scale=%g (finite, >= 0)", (double)lr_scale);
+    if (n_rows == 0 || n_ids == 0) return 0;
+    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    const int w4 = width / 4;
+    if (coef)
+        hipLaunchKernelGGL(adamw_table_lazy_rows_ema_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow,
+                           (long long)n_rows, w4, (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps,
+                           weight_decay, (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
+    else
+        hipLaunchKernelGGL(adamw_table_lazy_rows_ema_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow,
+                           (long long)n_rows, w4, (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps,
+                           weight_decay, (float)bc1, (float)sqrt(bc2), live, (const float*)nullptr, lr_scale);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int segmm_vec_swap(float* a, float* b, int64_t n, segmm_stream_t stream) {
     if (const int rc = flat_pair_check("vec_swap", a, b, n)) return rc;
     if (n == 0) return 0;

@@ -1294,6 +1294,98 @@ __global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void ema_update_kernel(floa
     }
 }
 
+// ---------------------------------------------------------------- lazy exact AdamW with the EMA shadow replayed beside it
+// (segmm_adamw_hist_push_ema, segmm_adamw_table_catchup_ema, segmm_adamw_table_lazy_rows_ema).  What holds for a row's (p, m, v)
+// holds for its shadow: shadow_t = shadow_{t-1} + (p_t - shadow_{t-1}) w_t depends on the row's own p_t and on the step's weight
+// only, so a row that replays its missed steps replays its shadow with them, in order, with ema_lerp's three rounded operations:
+// after a flush the shadow holds the bits ema_update_kernel leaves when it runs over the dense table every step.  w_t sits in the
+// fourth float of the ring's entry of step t -- the weight that step actually used, so the EMA's decay may move between steps.
+// The kernels are the two above with a fourth vector per lane (one wave per list entry, four floats per lane, four rows per
+// workgroup); the shadow's lerp does not feed the next AdamW step, so it is independent work beside the dependent sqrt / divide
+// chain.  The old kernels are untouched: the loops are stated again here.
+__global__ void adamw_hist_push_ema_kernel(AdamwHist* __restrict__ hist, int cap, int t, float lr, float bc1, float bc2_sqrt, float weight, int warmup,
+                                           const StepState* live) {
+    const float w = ema_weight(weight, warmup, t, live);          // (ema_update_kernel's call: t by value, or the state's count)
+    if (live) { t = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    if (t < 0) return;          // (a step state that was never set)
+    hist[t % cap] = AdamwHist{lr, bc1, bc2_sqrt, w};
+}
+// adamw_table_catchup_kernel without flags, plus the shadow: per replayed step s the AdamW step with g = 0, then the lerp with w_s
+__global__ __launch_bounds__(256) void adamw_table_catchup_ema_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                                      float* __restrict__ shadow, long long n_rows, int width,
+                                                                      const long long* __restrict__ ids, long long n_items, int* __restrict__ stamps,
+                                                                      const AdamwHist* __restrict__ hist, int cap, int target, const StepState* live,
+                                                                      float lr_scale, float b1, float b2, float eps, float wd) {
+#pragma clang fp contract(off)
+    if (live) target += live->step;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int w4 = width >> 2;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (long long k = blockIdx.x * 4LL + wave; k < n_items; k += gridDim.x * 4LL) {
+        const long long id = ids ? ids[k] : k;
+        int old = target;
+        if (lane == 0 && id >= 0 && id < n_rows) old = atomicMax(stamps + id, target);
+        old = __builtin_amdgcn_readfirstlane(old);
+        if (old >= target) continue;
+        for (int c = lane; c < w4; c += 64) {
+            const long long i = id * w4 + c;
+            f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], ss = ((f32x4*)shadow)[i];
+            int slot = (int)((unsigned)(old + 1) % (unsigned)cap);          // (whatever the stamp holds, the slot is in the ring)
+            for (int s = old + 1; s <= target; ++s) {
+                const AdamwHist h = hist[slot];
+                slot = slot + 1 == cap ? 0 : slot + 1;
+                const float lr = h.lr * lr_scale;
+                const float step = lr / h.bc1;
+                adamw_elem4(pp, zero, mm, vv, lr, b1, b2, eps, wd, step, h.bc2_sqrt);
+                ss = ema_lerp(ss, pp, h.pad_);
+            }
+            ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv; ((f32x4*)shadow)[i] = ss;
+        }
+    }
+}
+// adamw_table_lazy_rows_kernel plus the shadow: the replay as above, step T with the gradient row, then the lerp with w_T -- read
+// from the ring's entry of T, which adamw_hist_push_ema_kernel wrote on this stream ahead of this launch
+template <bool SCALED>
+__global__ __launch_bounds__(256) void adamw_table_lazy_rows_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                        float* __restrict__ v, float* __restrict__ shadow, long long n_rows, int w4,
+                                                                        const long long* __restrict__ ids, int n_ids, int* __restrict__ stamps,
+                                                                        const AdamwHist* __restrict__ hist, int cap, int T, float lr, float b1,
+                                                                        float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                                        const StepState* live, const float* __restrict__ coef, float lr_scale) {
+#pragma clang fp contract(off)
+    if (live) { T = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    lr = lr * lr_scale;
+    const float step = lr / bc1;
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (k >= n_ids) return;
+    const long long id = ids[k];
+    if (id < 0 || id >= n_rows) return;
+    int old = T;
+    if (lane == 0) old = atomicMax(stamps + id, T);
+    old = __builtin_amdgcn_readfirstlane(old);
+    if (old >= T) return;          // another entry of the list holds the same id and has taken the row, or the row was stepped already
+    const float w_T = hist[(unsigned)T % (unsigned)cap].pad_;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int c = lane; c < w4; c += 64) {
+        const long long i = id * w4 + c;
+        const f32x4 graw = ((const f32x4*)g)[i];
+        f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], ss = ((f32x4*)shadow)[i];
+        int slot = (int)((unsigned)(old + 1) % (unsigned)cap);
+        for (int s = old + 1; s < T; ++s) {
+            const AdamwHist h = hist[slot];
+            slot = slot + 1 == cap ? 0 : slot + 1;
+            const float lr_s = h.lr * lr_scale;
+            const float step_s = lr_s / h.bc1;
+            adamw_elem4(pp, zero, mm, vv, lr_s, b1, b2, eps, wd, step_s, h.bc2_sqrt);
+            ss = ema_lerp(ss, pp, h.pad_);
+        }
+        adamw_elem4(pp, adamw_grad4<SCALED>(graw, coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        ss = ema_lerp(ss, pp, w_T);
+        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv; ((f32x4*)shadow)[i] = ss;
+    }
+}
+
 // ---------------------------------------------------------------- a <-> b over a flat range (segmm_vec_swap)
 // WeightEMA.applied(): the shadow goes into the live range of the flat parameter buffer and back.  16 bytes of traffic per element;
 // the shape of the two kernels above (a lane reads the elements it owns from both ranges before it writes them).

@@ -1196,6 +1196,73 @@ def adamw_table_lazy_rows(p, g, m, v, off, n_rows, width, ids, stamps, hist, lr,
                                              _ptr(coef), _stream()), "segmm_adamw_table_lazy_rows")
 
 
+# ---- the same with the EMA shadow of the table replayed beside the rows (include/segmm_hip.h): ``shadow`` is the flat shadow tensor,
+# the table's shadow rows start ``shadow_off`` floats into it
+def adamw_hist_push_ema(hist, lr, beta1, beta2, step, ema_weight, ema_warmup):
+    """segmm_adamw_hist_push_ema: :func:`adamw_hist_push`, and the entry's fourth float is the w of
+    ``ema_update(weight=ema_weight, warmup=ema_warmup, step=step)``."""
+    if hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 2 or hist.shape[1] != 4:
+        raise RuntimeError("adamw_hist_push_ema: the history ring must be contiguous float32 [cap, 4]")
+    _dev(hist)
+    _check(lib().segmm_adamw_hist_push_ema(hist.data_ptr(), hist.shape[0], float(lr), float(beta1), float(beta2), int(step), float(ema_weight),
+                                           int(bool(ema_warmup)), _stream()), "segmm_adamw_hist_push_ema")
+
+
+def _lazy_shadow(who, shadow, shadow_off, n_rows, width):
+    _f32c(shadow, who + ": shadow")
+    _dev(shadow)
+    if shadow_off < 0 or shadow_off + n_rows * width > shadow.numel():
+        raise RuntimeError("%s: the shadow of a table of %d x %d at float %d does not fit a tensor of %d elements"
+                           % (who, n_rows, width, shadow_off, shadow.numel()))
+
+
+def adamw_table_catchup_ema(p, m, v, shadow, off, shadow_off, n_rows, width, ids, stamps, hist, target, lr_scale, beta1, beta2, eps, weight_decay,
+                            relative=False):
+    """segmm_adamw_table_catchup_ema: :func:`adamw_table_catchup` (no flags) whose replay also averages the rows' shadow, step by
+    step, with the weights the ring holds."""
+    n_rows, width = int(n_rows), int(width)
+    _lazy_state(stamps, hist, n_rows)
+    if hist is None:
+        raise RuntimeError("adamw_table_catchup_ema: needs the history ring")
+    if off < 0 or off + n_rows * width > min(p.numel(), m.numel(), v.numel()):
+        raise RuntimeError("adamw_table_catchup_ema: a table of %d x %d at float %d does not fit buffers of %d / %d / %d elements"
+                           % (n_rows, width, off, p.numel(), m.numel(), v.numel()))
+    _lazy_shadow("adamw_table_catchup_ema", shadow, shadow_off, n_rows, width)
+    if ids is not None and (ids.dtype != torch.int64 or not ids.is_contiguous()):
+        raise RuntimeError("adamw_table_catchup_ema: ids must be contiguous int64")
+    _dev(p, m, v, ids)
+    if ids is not None and ids.numel() == 0:          # an empty list (torch hands out a null pointer for it, the C ABI's flush) lists nothing
+        return
+    _check(lib().segmm_adamw_table_catchup_ema(p.data_ptr() + 4 * off, m.data_ptr() + 4 * off, v.data_ptr() + 4 * off,
+                                               shadow.data_ptr() + 4 * shadow_off, n_rows, width, _ptr(ids), 0 if ids is None else ids.numel(),
+                                               stamps.data_ptr(), hist.data_ptr(), hist.shape[0], int(target), int(bool(relative)), float(lr_scale),
+                                               float(beta1), float(beta2), float(eps), float(weight_decay), _stream()),
+           "segmm_adamw_table_catchup_ema")
+
+
+def adamw_table_lazy_rows_ema(p, g, m, v, shadow, off, shadow_off, n_rows, width, ids, stamps, hist, lr, lr_scale, beta1, beta2, eps, weight_decay,
+                              step, coef=None):
+    """segmm_adamw_table_lazy_rows_ema: :func:`adamw_table_lazy_rows` that also averages the rows' shadow -- through the replayed
+    steps and, with the weight :func:`adamw_hist_push_ema` has just written for it, through step T."""
+    n_rows, width = int(n_rows), int(width)
+    _lazy_state(stamps, hist, n_rows)
+    if hist is None:
+        raise RuntimeError("adamw_table_lazy_rows_ema: needs the history ring")
+    if off < 0 or off + n_rows * width > min(p.numel(), g.numel(), m.numel(), v.numel()):
+        raise RuntimeError("adamw_table_lazy_rows_ema: a table of %d x %d at float %d does not fit buffers of %d / %d / %d / %d elements"
+                           % (n_rows, width, off, p.numel(), g.numel(), m.numel(), v.numel()))
+    _lazy_shadow("adamw_table_lazy_rows_ema", shadow, shadow_off, n_rows, width)
+    if ids is None or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise RuntimeError("adamw_table_lazy_rows_ema: ids must be contiguous int64 (the id list of the step)")
+    _dev(p, g, m, v, ids, coef)
+    if ids.numel() == 0:
+        return
+    _check(lib().segmm_adamw_table_lazy_rows_ema(p.data_ptr() + 4 * off, g.data_ptr() + 4 * off, m.data_ptr() + 4 * off, v.data_ptr() + 4 * off,
+                                                 shadow.data_ptr() + 4 * shadow_off, n_rows, width, ids.data_ptr(), ids.numel(), stamps.data_ptr(),
+                                                 hist.data_ptr(), hist.shape[0], float(lr), float(lr_scale), float(beta1), float(beta2), float(eps),
+                                                 float(weight_decay), int(step), _ptr(coef), _stream()), "segmm_adamw_table_lazy_rows_ema")
+
+
 GRAD_NORM_SCRATCH = 1024         # fp64 partials segmm_grad_norm may write
 
 

@@ -292,14 +292,15 @@ def _check_ema_decay(decay):
     return float(decay)
 
 
-LAZY_KEYS = ("flush_every", "data_parallel")
+LAZY_KEYS = ("flush_every", "data_parallel", "ema")
 LAZY_FLUSH_EVERY = 64          # lazy_tables=True (profiles/lazy_tables/)
 
 
 def parse_lazy_tables(spec):
     """``lazy_tables=`` of FusedAdamW / Trainer -> ``flush_every`` (the history ring's capacity) or None.  ``spec``: None (dense, as
-    ever), True (the default capacity) or ``dict(flush_every=int, data_parallel=bool)``; an unknown key, a flush_every < 1 and a
-    data_parallel that is no bool are refused by name (:func:`parse_lazy_data_parallel` returns that flag)."""
+    ever), True (the default capacity) or ``dict(flush_every=int, data_parallel=bool, ema=bool)``; an unknown key, a flush_every < 1
+    and a data_parallel or ema that is no bool are refused by name (:func:`parse_lazy_data_parallel` and :func:`parse_lazy_ema`
+    return those flags)."""
     if spec is None:
         return None
     if spec is True:
@@ -313,6 +314,7 @@ def parse_lazy_tables(spec):
     if isinstance(fe, bool) or not isinstance(fe, int) or fe < 1:
         raise ValueError("lazy_tables: flush_every must be an int >= 1, not %r" % (fe,))
     parse_lazy_data_parallel(spec)
+    parse_lazy_ema(spec)
     return fe
 
 
@@ -323,6 +325,16 @@ def parse_lazy_data_parallel(spec):
     if not isinstance(dp, bool):
         raise ValueError("lazy_tables: data_parallel must be a bool, not %r" % (dp,))
     return dp
+
+
+def parse_lazy_ema(spec):
+    """The ``ema`` key of ``lazy_tables=`` (default False): the opt-in to lazy tables beside a weight average (``ema=...``), where a
+    lazy row's shadow is replayed with the row (segmm_adamw_table_catchup_ema / segmm_adamw_table_lazy_rows_ema).  Without an EMA
+    the key changes nothing."""
+    le = spec.get("ema", False) if isinstance(spec, dict) else False
+    if not isinstance(le, bool):
+        raise ValueError("lazy_tables: ema must be a bool, not %r" % (le,))
+    return le
 
 
 class WeightEMA:
@@ -345,7 +357,13 @@ class WeightEMA:
     ``applied()``: a context manager that swaps the shadow INTO the live range (segmm_vec_swap) and back out on exit, bumping
     ``store.fused_version`` both times so that the weight planes are re-split for the averaged weights and again for the trained
     ones.  While applied, ``train_step`` / ``record`` / ``run_recorded`` are refused, and so is a nested ``applied()``.
-    ``decay`` may be assigned between steps (a recorded step is then refused like after any hyperparameter change)."""
+    ``decay`` may be assigned between steps (a recorded step is then refused like after any hyperparameter change).
+
+    Beside lazy id tables (``lazy_tables=dict(ema=True)``) the shadow rows of a lazy table are averaged LAZILY, with the row: the
+    step's update walks around the table's range, and a row that replays its missed AdamW steps replays its lerps with them, each
+    with the weight its step used (the ring's fourth float).  ``applied()``, ``state_dict()`` and ``load_state_dict()`` flush first
+    (``opt.flush_tables()``), after which the shadow holds the dense run's bits; a RAW read of ``ema.shadow`` needs
+    ``opt.flush_tables()`` first -- with steps pending, the rows outside the recent batches are behind."""
 
     def __init__(self, opt, decay=0.999, warmup=True):
         self.opt, self.warmup = opt, bool(warmup)
@@ -404,7 +422,11 @@ class WeightEMA:
         return st
 
     def update(self):
-        """The step's update (FusedAdamW.end_step): one launch on the current stream."""
+        """The step's update (FusedAdamW.end_step): one launch on the current stream -- or, beside lazy id tables
+        (``lazy_tables=dict(ema=True)``), one launch per range AROUND the tables stepped lazily this step (``opt._lazy_tail``, as
+        ``step_ranges`` walks around them for AdamW): their listed rows took this step's lerp in segmm_adamw_table_lazy_rows_ema,
+        every other row of theirs takes it when it next catches up.  Parameter offsets are multiples of 32 floats: every piece is
+        16-byte aligned."""
         if self.is_applied:
             raise RuntimeError("ema: an optimizer step inside ema.applied() (the live range holds the averaged weights)")
         opt = self.opt
@@ -412,7 +434,17 @@ class WeightEMA:
         live = opt.__dict__.get("device_state", False)
         if live and opt.__dict__.get("_step_state") is not None:
             H.step_bind(opt._step_state)
-        H.ema_update(self.shadow, st.flat, st.n_live, self.weight, self.warmup, -1 if live else opt.step_count)
+        pos, step = 0, -1 if live else opt.step_count
+        tail = opt.__dict__.get("_lazy_tail")
+        if not tail:
+            H.ema_update(self.shadow, st.flat, st.n_live, self.weight, self.warmup, step)
+            return
+        for o, n in sorted(tail.values()):
+            if o > pos:
+                H.ema_update(self.shadow, st.flat, o - pos, self.weight, self.warmup, step, shadow_off=pos, p_off=pos)
+            pos = max(pos, o + n)
+        if st.n_live > pos:
+            H.ema_update(self.shadow, st.flat, st.n_live - pos, self.weight, self.warmup, step, shadow_off=pos, p_off=pos)
 
     def _swap(self, st):
         H.vec_swap(st.flat, self.shadow, st.n_live)
@@ -424,6 +456,7 @@ class WeightEMA:
             raise RuntimeError("ema.applied() is already active (nested applied() is refused)")
         if H.RECORDER is not None:
             raise RuntimeError("ema.applied() inside a recorded step")
+        self._flush_lazy()
         st = self._store()
         self._swap(st)
         self.is_applied = True
@@ -437,6 +470,13 @@ class WeightEMA:
                                    "trained weights are in ema.shadow")
             self._swap(st)
 
+    def _flush_lazy(self):
+        """Lazy id tables (``lazy_tables=dict(ema=True)``): every row and its shadow current before the shadow is read as a whole or
+        replaced.  Nothing pending: no launch.  (``flush_tables`` refuses to run inside a recording.)"""
+        flush = getattr(self.opt, "flush_tables", None)
+        if flush is not None:
+            flush()
+
     def _refuse_applied(self, who):
         if self.is_applied:
             raise RuntimeError("%s inside ema.applied(): the live range holds the averaged weights; leave the context first" % who)
@@ -445,6 +485,7 @@ class WeightEMA:
         """The model's ``state_dict`` keys and shapes (host tensors): the live parameters from the shadow, everything else (dead
         parameters, buffers) copied from the model -- what the reference's model loads directly."""
         self._refuse_applied("ema.state_dict()")
+        self._flush_lazy()
         st = self._store()
         out = {k: v.detach().cpu().clone() for k, v in self.opt.model.state_dict().items()}
         for n in st.live_names:
@@ -455,6 +496,7 @@ class WeightEMA:
     def load_state_dict(self, sd):
         """The inverse of :meth:`state_dict`: the live parameters' entries become the shadow (the seed is replaced)."""
         self._refuse_applied("ema.load_state_dict()")
+        self._flush_lazy()          # (what is pending belongs to the old average: it is applied before the new one replaces it)
         st = self._store()
         for n in st.live_names:
             if n not in sd:
@@ -517,7 +559,7 @@ class FusedAdamW:
     (``CheckPointer`` and the trainer's evaluation passes do).  A rebuild of the flat buffer with rows pending LOSES their pending
     decay and momentum steps (the moments are zeroed there as ever): from then on the run is not the dense run's; call
     ``flush_tables()`` before anything that rebuilds the buffer.  ``tables_pending``: the steps since the last flush.  Refused by
-    name: an EMA (its shadow would average stale rows), unknown keys, flush_every < 1, :meth:`table_lazy` with ``flush_every`` steps
+    name: an EMA without the ``ema`` key below (its shadow would average stale rows), unknown keys, flush_every < 1, :meth:`table_lazy` with ``flush_every`` steps
     pending (the trainer calls :meth:`lazy_step_head` first).  A forward of the caller's own (not ``Trainer.train_step``) reads the
     table as it stands: call ``flush_tables()`` before it.  ``step()`` for a lazy table that did not come through
     :meth:`table_lazy` steps it densely and sets every stamp; with steps pending it raises, because that forward read stale rows.
@@ -526,7 +568,17 @@ class FusedAdamW:
     ``table_lazy(name, own_ids, mark=False)`` -- the rank's own rows catch up, nothing is marked or queued -- and the tail
     :meth:`table_lazy_rows` on the gathered list (segmm_adamw_table_lazy_rows: replay, this step and the stamp in one launch), while
     the dense launches walk around the table (:meth:`step_ranges`).  Stamps, ring and flush rule depend on the step count only:
-    every rank flushes at the same step and holds the same bits, without a collective.  Without an active comm the key changes nothing."""
+    every rank flushes at the same step and holds the same bits, without a collective.  Without an active comm the key changes nothing.
+    ``dict(ema=True)`` (a bool, default False; combinable with both other keys; ``opt.lazy_ema``): the opt-in to lazy tables beside
+    ``ema=...``.  A row's shadow depends on the row's own p_t and step t's weight only, so it is replayed with the row, in order, with
+    segmm_ema_update's three rounded operations; the ring's fourth float holds the weight each step used (``ema.decay`` may move
+    between steps without a flush).  A step is then, single process or data parallel: ``table_lazy(name, own_ids, mark=False)``
+    (segmm_adamw_table_catchup_ema, behind the seeding of the shadow), the dense ranges around the table, the ring's entry
+    (segmm_adamw_hist_push_ema), :meth:`table_lazy_rows` on the step's list -- ``step(lazy_rows={name: ids})``, single process the
+    batch's own ids -- (segmm_adamw_table_lazy_rows_ema) and the EMA's update around the table; no phase 1, no stamp launch, no flags.
+    ``flush_tables()`` brings the shadow up with the rows; ``ema.applied()`` / ``ema.state_dict()`` / ``ema.load_state_dict()`` flush
+    first, so evaluation on the averaged weights and ``"model_ema"`` in a checkpoint are the dense trainer's, bit for bit.  Without
+    an EMA the key changes nothing."""
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None,
                  param_groups=None, ema=None, lazy_tables=None):
@@ -541,6 +593,10 @@ class FusedAdamW:
         # way -- the ranges the dense launches of the step walk around (step_ranges); _lazy_pushed: the step whose ring entry is in
         self.lazy_data_parallel = parse_lazy_data_parallel(lazy_tables)
         self._lazy_tail, self._lazy_pushed = {}, 0
+        # lazy_tables=dict(ema=True): lazy tables beside the weight average -- a lazy row's shadow is replayed with the row (the
+        # *_ema launches); every lazy step then runs as table_lazy(mark=False) + table_lazy_rows, single process too.  Without an
+        # EMA the key changes nothing (_lazy_ema_on: the mode itself)
+        self.lazy_ema = parse_lazy_ema(lazy_tables)
         # resolved groups (resolve_param_groups; entry 0 = the default group) or None; _segs: their segment table on the device
         self.groups = None if param_groups is None else resolve_param_groups(list(model.named_parameters()), param_groups, weight_decay)
         self._group_idx = None if self.groups is None else {n: gi for gi, G in enumerate(self.groups) for n in G["names"]}
@@ -664,7 +720,8 @@ class FusedAdamW:
     def step(self, gbuf=None, lazy_rows=None):
         """``lazy_rows`` (data parallel, ``lazy_tables=dict(data_parallel=True)``): name -> the gathered id list of all ranks, for
         every table whose head ran as ``table_lazy(name, own_ids, mark=False)``; those tables take :meth:`table_lazy_rows` behind the
-        dense ranges, which walk around them."""
+        dense ranges, which walk around them.  Single process such heads run under ``lazy_tables=dict(ema=True)`` beside an EMA: the
+        list is the batch's own."""
         lazy_rows = lazy_rows or {}
         missing = sorted(n for n in self._lazy_tail if n not in lazy_rows)
         if missing:
@@ -720,6 +777,11 @@ class FusedAdamW:
         """The optimizer steps since the last flush of the lazy tables (0: every row is current)."""
         return self.step_count - self._lazy_flushed if self._lazy else 0
 
+    @property
+    def _lazy_ema_on(self):
+        """``lazy_tables=dict(ema=True)`` beside an EMA: the lazy tables' shadow rows are replayed with the rows."""
+        return self.lazy_ema and self.ema is not None and self.lazy_flush_every is not None
+
     def _lazy_hyper_now(self):
         """What a replayed step takes from the launch arguments, not from the ring: betas, eps and each lazy table's (scale, decay)."""
         tabs = tuple((n,) + ((1.0, self.wd) if self.groups is None else tuple(self.group_of(n)[:2])) for n in sorted(self._lazy))
@@ -745,8 +807,12 @@ class FusedAdamW:
         betas, eps, tabs = self._lazy_snap
         for name, scale, wd in tabs:
             e = self._lazy[name]
-            H.adamw_table_catchup(st.flat, self.m, self.v, e["o"], e["rows"], e["width"], None, e["stamps"], self._lazy_hist, self.step_count,
-                                  scale, betas[0], betas[1], eps, wd)
+            if self._lazy_ema_on:          # the rows' shadow catches up with them, lerp by lerp with the ring's weights
+                H.adamw_table_catchup_ema(st.flat, self.m, self.v, self.ema.shadow, e["o"], e["o"], e["rows"], e["width"], None, e["stamps"],
+                                          self._lazy_hist, self.step_count, scale, betas[0], betas[1], eps, wd)
+            else:
+                H.adamw_table_catchup(st.flat, self.m, self.v, e["o"], e["rows"], e["width"], None, e["stamps"], self._lazy_hist, self.step_count,
+                                      scale, betas[0], betas[1], eps, wd)
         self._lazy_flushed = self.step_count
 
     def lazy_step_head(self):
@@ -766,9 +832,15 @@ class FusedAdamW:
         (:meth:`step_ranges`) and the tail is :meth:`table_lazy_rows` on the gathered list."""
         if self.lazy_flush_every is None:
             raise RuntimeError("table_lazy needs FusedAdamW(lazy_tables=...)")
-        if self.ema is not None:
-            raise RuntimeError("lazy_tables with ema: the shadow would average the stale rows of the lazy table %s; use one of the two" % name)
+        if self.ema is not None and not self.lazy_ema:
+            raise RuntimeError("lazy_tables with ema: the shadow would average the stale rows of the lazy table %s; use one of the two, or "
+                               "opt in to the lazily averaged shadow with lazy_tables=dict(ema=True)" % name)
+        if self._lazy_ema_on and mark:
+            raise RuntimeError("table_lazy(%s): lazy_tables=dict(ema=True) steps its rows in one launch at the tail -- the head is "
+                               "table_lazy(name, ids, mark=False), the tail step(lazy_rows={name: ids})" % name)
         st = self._state()
+        if self._lazy_ema_on:
+            self.ema.step_head(st)          # the shadow is seeded before anything moves the table's rows (or replays their shadow)
         if self.tables_pending >= self.lazy_flush_every:          # the ring rule: target - stamp <= cap, or a replay reads an overwritten slot
             raise RuntimeError("table_lazy: %d steps are pending and the ring holds %d -- call lazy_step_head() (or flush_tables()) "
                                "between steps, before the step begins" % (self.tables_pending, self.lazy_flush_every))
@@ -789,8 +861,12 @@ class FusedAdamW:
             self._lazy_hist = torch.zeros((self.lazy_flush_every, 4), dtype=torch.float32, device=dev)
         live = self.__dict__.get("device_state", False)
         scale, wd = (1.0, self.wd) if hyper is None else hyper
-        H.adamw_table_catchup(st.flat, self.m, self.v, o, rows, width, ids, e["stamps"], self._lazy_hist, -1 if live else self.step_count, scale,
-                              self.betas[0], self.betas[1], self.eps, wd, relative=live, flags=e["flags"] if mark else None)
+        if self._lazy_ema_on:
+            H.adamw_table_catchup_ema(st.flat, self.m, self.v, self.ema.shadow, o, o, rows, width, ids, e["stamps"], self._lazy_hist,
+                                      -1 if live else self.step_count, scale, self.betas[0], self.betas[1], self.eps, wd, relative=live)
+        else:
+            H.adamw_table_catchup(st.flat, self.m, self.v, o, rows, width, ids, e["stamps"], self._lazy_hist, -1 if live else self.step_count, scale,
+                                  self.betas[0], self.betas[1], self.eps, wd, relative=live, flags=e["flags"] if mark else None)
         self._lazy_snap = self._lazy_hyper_now()
         if mark:
             self.__dict__.setdefault("_early", []).append((o, n, rows, width, ids, e["flags"], hyper, name))
@@ -811,12 +887,21 @@ class FusedAdamW:
         e = self._lazy[name]
         live = self.__dict__.get("device_state", False)
         step = -1 if live else self.step_count
+        ema = self.ema if self._lazy_ema_on else None
         if self._lazy_pushed != self.step_count:
-            H.adamw_hist_push(self._lazy_hist, self._lr_arg(), self.betas[0], self.betas[1], step)
+            if ema is not None:          # ... and the weight of this step's lerp: the launch below reads it from the ring
+                H.adamw_hist_push_ema(self._lazy_hist, self._lr_arg(), self.betas[0], self.betas[1], step, ema.weight, ema.warmup)
+            else:
+                H.adamw_hist_push(self._lazy_hist, self._lr_arg(), self.betas[0], self.betas[1], step)
             self._lazy_pushed = self.step_count
         scale, wd = (1.0, self.wd) if self.groups is None else self.group_of(name)[:2]
-        H.adamw_table_lazy_rows(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, e["o"], e["rows"], e["width"], ids_all, e["stamps"],
-                                self._lazy_hist, self._lr_arg(), scale, self.betas[0], self.betas[1], self.eps, wd, step, coef=self._coef())
+        if ema is not None:
+            H.adamw_table_lazy_rows_ema(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, ema.shadow, e["o"], e["o"], e["rows"], e["width"],
+                                        ids_all, e["stamps"], self._lazy_hist, self._lr_arg(), scale, self.betas[0], self.betas[1], self.eps, wd,
+                                        step, coef=self._coef())
+        else:
+            H.adamw_table_lazy_rows(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, e["o"], e["rows"], e["width"], ids_all, e["stamps"],
+                                    self._lazy_hist, self._lr_arg(), scale, self.betas[0], self.betas[1], self.eps, wd, step, coef=self._coef())
         self._lazy_snap = self._lazy_hyper_now()
 
     def step_ranges(self, start, end, gbuf=None):

@@ -39,7 +39,7 @@ from .encoder import SegFormerX
 from .eval_passes import EvalPasses
 from .loop import CheckPointer, compute_final_result, early_stop_reached, fit  # noqa: F401
 from .optim import (GROUP_KEYS, FusedAdamW, LRSchedule, PlateauLR, WeightEMA, group_segments, no_decay_groups, parse_ema,  # noqa: F401
-                    parse_lazy_data_parallel, parse_lazy_tables, resolve_param_groups)
+                    parse_lazy_data_parallel, parse_lazy_ema, parse_lazy_tables, resolve_param_groups)
 
 
 # ------------------------------------------------------------------------------------------------ model factory
@@ -130,7 +130,8 @@ class Trainer(EvalPasses):
         # lazy_tables=None | True | dict(flush_every=F): lazy exact AdamW of the item-id tables (FusedAdamW; _tables_early) -- a step
         # reads and writes only the batch's rows of the table.  Under data parallelism the rows touched are those of ALL ranks, known
         # only after the row exchange: that takes the opt-in lazy_tables=dict(data_parallel=True) -- the rank's own rows catch up at
-        # the head, the gathered list is stepped by one fused launch at the tail (_tables_early, _finish_step)
+        # the head, the gathered list is stepped by one fused launch at the tail (_tables_early, _finish_step).  Beside ema=... it takes
+        # the opt-in lazy_tables=dict(ema=True): the table's shadow rows are then averaged lazily, with the rows (below)
         lazy_dp = False
         if lazy_tables is not None and comm is not None and comm.active:
             parse_lazy_tables(lazy_tables)          # (a malformed spec is refused for what it is, before anything below)
@@ -146,10 +147,14 @@ class Trainer(EvalPasses):
                 raise ValueError("Trainer(lazy_tables=dict(data_parallel=True)) with micro_batch under an active DPComm is not supported: "
                                  "each micro-batch pass has its own row exchange (a follow-up); use one of the two")
         self._lazy_dp = lazy_dp
+        # lazy tables beside a weight average take the opt-in lazy_tables=dict(ema=True): the shadow rows of the lazy table are then
+        # replayed with the rows (FusedAdamW), and every lazy step, single process too, runs head + fused tail (_tables_early, _lazy_rows)
         if lazy_tables is not None and ema is not None and any(
                 bb is not None and bb.id_vid for bb in (model.backbone1, getattr(model, "backbone2", None))):
-            raise ValueError("Trainer(lazy_tables=...) with ema: the EMA shadow would average the stale rows of the lazy item-id table; "
-                             "use one of the two")
+            parse_lazy_tables(lazy_tables)          # (a malformed spec is refused for what it is)
+            if not parse_lazy_ema(lazy_tables):
+                raise ValueError("Trainer(lazy_tables=...) with ema: the EMA shadow would average the stale rows of the lazy item-id table; "
+                                 "use one of the two, or opt in to the lazily averaged shadow with lazy_tables=dict(ema=True)")
         # micro_batch=m: a batch of more than m rows is stepped in ceil(B / m) micro-batches with ONE optimizer step on the whole
         # batch's gradient (train_step / _train_step_micro); None, or m >= the batch's rows: the plain step, launch for launch
         if micro_batch is not None and (isinstance(micro_batch, bool) or not isinstance(micro_batch, int) or micro_batch < 1):
@@ -358,6 +363,7 @@ class Trainer(EvalPasses):
                 seed, _, _ = H.step_get()
                 H.step_set(seed, self.opt.step_count + 1, *self.opt.betas)
         lazy = self.opt.lazy_flush_every is not None
+        self._lazy_own = {}          # name -> the batch's own id list, of the tables whose head runs below with mark=False, single process
         if lazy and self._param_hooks():
             raise RuntimeError("Trainer(lazy_tables=...) does not support parameter hooks: a hook may rewrite the gradient of table rows "
                                "outside the batch, which a lazy step never reads")
@@ -387,7 +393,12 @@ class Trainer(EvalPasses):
                 # T - 1 are right whether or not step T happens
                 # Data parallel: these are the rank's OWN rows -- the forward reads no others.  Nothing is marked or queued: the rows
                 # of the step, all ranks', are stepped behind the row exchange by one fused launch (_finish_step)
-                self.opt.table_lazy(name, ids.reshape(-1), mark=not self.comm.active)
+                # Beside an EMA (lazy_tables=dict(ema=True)) the single process takes the same form: the fused tail also averages the
+                # rows' shadow, on the batch's own list (_lazy_rows)
+                own = ids.reshape(-1)
+                self.opt.table_lazy(name, own, mark=not (self.comm.active or self.opt._lazy_ema_on))
+                if name in self.opt._lazy_tail:
+                    self._lazy_own[name] = own
                 continue
             if self.opt.ema is not None:          # the shadow is made and seeded on the main stream, before the early pass moves the table's rows
                 self.opt.ema.step_head(self.opt._state())
@@ -680,7 +691,7 @@ class Trainer(EvalPasses):
             H.mark(H.PHASE_STEP_TAIL)
             if self.opt.early_on_aux():
                 E.join_aux(st)          # the tables' first pass (aux stream) is complete before their listed rows are stepped
-            self.opt.step()
+            self.opt.step(lazy_rows=self._lazy_rows(st))          # (lazy_tables=dict(ema=True): the whole batch's ids; otherwise none)
             res = {}
             for key in keys:
                 res[key] = logits if key == "logits" else batch["label"] if key == "gt" else sums[12] if key == "loss" else sums[_LIDX[key]]
@@ -813,8 +824,18 @@ class Trainer(EvalPasses):
     def _lazy_rows(self, st):
         """Data parallel with lazy tables: name -> the gathered id list of all ranks, for every table whose head ran this step
         (FusedAdamW.table_lazy with mark=False).  The list is the row exchange's persistent buffer (DPComm.gather_rows), which the
-        backward left in ``st._tab_rows``: the same tensor every step, so a recorded step names it by address.  Otherwise empty."""
+        backward left in ``st._tab_rows``: the same tensor every step, so a recorded step names it by address.  Single process such
+        heads run only beside an EMA (``lazy_tables=dict(ema=True)``): the list is the batch's own.  Otherwise empty."""
         out = {}
+        if not self.comm.active:
+            # single process (lazy_tables=dict(ema=True)): the step's rows are the batch's own, the list the head caught up -- a batch
+            # tensor, which a recorded step names by its slot
+            for name in self.opt._lazy_tail:
+                own = self.__dict__.get("_lazy_own", {}).get(name)
+                if own is None:
+                    raise RuntimeError("lazy_tables=dict(ema=True): no id list of this step for %s (its head did not run)" % name)
+                out[name] = own
+            return out
         for name in self.opt._lazy_tail:
             ent = st._tab_rows.get(name[:-len("_proj.weight")])
             if ent is None:
@@ -923,7 +944,8 @@ class Trainer(EvalPasses):
         lr = self.opt.lr if self.opt.schedule is None else H.LIVE_LR
         # (the recorded segmm_ema_update carries the EMA's weight and warm-up flag by value)
         return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm, self.opt.group_table(),
-                None if self.ema is None else self.ema.hyper(),
+                # (... and beside lazy tables the recorded *_ema launches stand for the key lazy_tables=dict(ema=True))
+                None if self.ema is None else self.ema.hyper() + (bool(getattr(self.opt, "lazy_ema", False)),),
                 # (the recorded plane GEMMs carry their product count in the command: segmm_gemm_p or segmm_gemm_pq(..., 1))
                 None if self.mixed_precision is None else tuple(sorted(self.mixed_precision.items())))
 

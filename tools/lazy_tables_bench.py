@@ -28,6 +28,15 @@ inside the windows.  Run it under ``torchrun --nproc_per_node=<GPUs>``; started 
 group (SEGMM_DP_FORCE=1): every collective is really issued but is an identity, and the gathered list is the rank's own.  Rank 0
 reports.  profiles/lazy_tables/dp_bench.txt is the output of ``--what dp_kernel,dp_step``.
 
+``--what ema_kernel``: lazy tables beside a weight average (``lazy_tables=dict(ema=True)``): segmm_adamw_table_catchup_ema and
+segmm_adamw_table_lazy_rows_ema alone, each against its sibling without the shadow, at 1024 / 2048 / 4096 listed ids whose rows are 0
+and 58 steps behind T - 1, and ONE EMA-mode flush of the whole table after 64 untouched steps against today's flush.
+
+``--what ema_step``: the recorded config-3 step with ``ema=0.999``: ``lazy_tables=dict(flush_every=64, ema=True)`` against the dense
+two-pass trainer with the dense EMA launch and against the lazy trainer without an EMA, three legs in alternating windows in one
+process, uniform and skewed ids, the periodic flushes inside the windows.  profiles/lazy_tables/ema_bench.txt is the output of
+``--what ema_kernel,ema_step --settle 200``.
+
     python tools/lazy_tables_bench.py [--what step,kernel] [--windows 8] [--steps 256] [--pool 512] [--settle 1100] [--out FILE]
 
 Needs the GPU; there is no fallback."""
@@ -302,6 +311,107 @@ def dp_step(torch, steps, windows, n_pool, settle):
     return rank
 
 
+EMA_DECAY = 0.999
+
+
+def ema_kernel(torch, windows, dev):
+    """The *_ema launches against their siblings of the same build, and the EMA-mode flush against today's."""
+    from segmminterest_amd import hipabi as H
+    model = _model(torch, dev)
+    rows, width = model.get_parameter(TABLE).shape
+    del model
+    n = rows * width
+    p, m, g, sh = (torch.randn(n, device=dev) * 1e-2 for _ in range(4))
+    v = torch.rand(n, device=dev) * 1e-4
+    cap = DP_FLUSH
+    hist = torch.zeros((cap, 4), device=dev)
+    T = 5000 + cap
+    for t in range(T - cap + 1, T + 1):
+        H.adamw_hist_push_ema(hist, 1e-3, 0.9, 0.999, t, 1.0 - EMA_DECAY, True)
+    stamps, behind = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
+    hp = (0.9, 0.999, 1e-8, 1e-2)
+    say("the *_ema launches against their siblings: table %d x %d, distinct listed rows, each `gap` steps behind T - 1; us per launch (median of "
+        "%d windows of 50), the copy that puts the stamps back subtracted" % (rows, width, windows))
+    for n_ids in (1024, 2048, 4096):
+        ids = torch.randperm(rows, device=dev)[:n_ids].to(torch.int64).contiguous()
+        for gap in (0, 58):
+            behind.fill_(T - 1 - gap)
+            fns = {
+                "catchup": lambda: H.adamw_table_catchup(p, m, v, 0, rows, width, ids, stamps, hist, T - 1, 1.0, *hp),
+                "catchup_ema": lambda: H.adamw_table_catchup_ema(p, m, v, sh, 0, 0, rows, width, ids, stamps, hist, T - 1, 1.0, *hp),
+                "lazy_rows": lambda: H.adamw_table_lazy_rows(p, g, m, v, 0, rows, width, ids, stamps, hist, 1e-3, 1.0, *hp, T),
+                "lazy_rows_ema": lambda: H.adamw_table_lazy_rows_ema(p, g, m, v, sh, 0, 0, rows, width, ids, stamps, hist, 1e-3, 1.0, *hp, T),
+                "copy": lambda: None}
+            res = {}
+            for name, fn in fns.items():
+                def both(fn=fn):
+                    H.copy_bytes(stamps, behind)
+                    fn()
+                both()
+                torch.cuda.synchronize()
+                res[name] = statistics.median(_timed(torch, both, 50) for _ in range(windows))
+            c, ce, r, re_ = (res[k] - res["copy"] for k in ("catchup", "catchup_ema", "lazy_rows", "lazy_rows_ema"))
+            say("  ids %-5d gap %-3d catchup %8.2f us  catchup_ema %8.2f us (x %.3f)   lazy_rows %8.2f us  lazy_rows_ema %8.2f us (x %.3f)"
+                % (n_ids, gap, c, ce, ce / c if c > 0 else float("nan"), r, re_, re_ / r if r > 0 else float("nan")))
+    say("ONE flush of the whole table after %d untouched steps (%d x %d = %.0f M floats; 24 B per float without the shadow, 32 B with it):"
+        % (cap, rows, width, n / 1e6))
+    behind.fill_(T - cap)
+    for name, fn in (("segmm_adamw_table_catchup", lambda: H.adamw_table_catchup(p, m, v, 0, rows, width, None, stamps, hist, T, 1.0, *hp)),
+                     ("segmm_adamw_table_catchup_ema", lambda: H.adamw_table_catchup_ema(p, m, v, sh, 0, 0, rows, width, None, stamps, hist, T, 1.0, *hp))):
+        def flush(fn=fn):
+            H.copy_bytes(stamps, behind)
+            fn()
+        flush()
+        torch.cuda.synchronize()
+        us = statistics.median(_timed(torch, flush, 2) for _ in range(3))
+        say("  %-30s %9.3f ms = %.1f us per step it covers" % (name, 1e-3 * us, us / cap))
+
+
+def ema_step(torch, steps, windows, n_pool, settle, dev):
+    """The recorded config-3 step with a weight average: lazy tables + lazily averaged shadow against the dense two-pass trainer with the
+    dense EMA launch (the parent's behaviour) and against the lazy trainer without an EMA, alternating windows in one process."""
+    from segmminterest_amd.trainer import Trainer
+    legs_kw = (("dense + ema", dict(ema=EMA_DECAY)), ("lazy, no ema", dict(lazy_tables=dict(flush_every=DP_FLUSH))),
+               ("lazy + ema (key)", dict(ema=EMA_DECAY, lazy_tables=dict(flush_every=DP_FLUSH, ema=True))))
+    for skewed in (False, True):
+        pool = _pool(torch, dev, n_pool, skewed)
+        legs = {}
+        for leg, kw in legs_kw:
+            tr = Trainer(_model(torch, dev), device_state=True, **kw)
+            tr.train_step(pool[0])
+            tr.train_step(pool[1])
+            tr.record(pool[2], prev_batch=pool[1])
+            for i in range(settle):
+                tr.run_recorded(pool[(3 + i) % n_pool])
+            legs[leg] = [tr, 3 + settle]
+        torch.cuda.synchronize()
+        ms = {leg: [] for leg in legs}
+        for _ in range(windows):
+            for leg, e in legs.items():
+                tr = e[0]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(steps):
+                    tr.run_recorded(pool[(e[1] + i) % n_pool])
+                torch.cuda.synchronize()
+                ms[leg].append(1e3 * (time.perf_counter() - t0) / steps)
+                e[1] += steps
+        d = ms["dense + ema"]
+        spread, mean0 = max(d) - min(d), statistics.mean(d)
+        say("recorded config-3 step (B = %d) with a weight average (decay %g, warm-up), item ids %s: pool of %d batches, %d settling steps, %d "
+            "alternating windows of %d replays; flush_every = %d, the flushes inside the windows"
+            % (CFG3[4], EMA_DECAY, "SKEWED (1 + floor(n u^4))" if skewed else "uniform", n_pool, settle, windows, steps, DP_FLUSH))
+        for leg, _ in legs_kw:
+            x = ms[leg]
+            say("  %-18s median %.4f ms  mean %.4f ms  (min %.4f max %.4f: spread %.4f ms)  mean - (dense + ema) %+.4f ms"
+                % (leg, statistics.median(x), statistics.mean(x), min(x), max(x), max(x) - min(x), statistics.mean(x) - mean0))
+        x = ms["lazy + ema (key)"]
+        say("  lazy + ema faster than dense + ema by more than the dense leg's window spread (%.4f ms): %s"
+            % (spread, "yes" if mean0 - statistics.mean(x) > spread else "NO"))
+        del legs, pool
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="step,kernel")
@@ -332,6 +442,10 @@ def main():
         dp_kernel(torch, min(args.windows, 5), dev)
     if "dp_step" in what:
         dp_step(torch, args.steps, args.windows, args.pool, args.settle)
+    if "ema_kernel" in what and rank == 0:
+        ema_kernel(torch, min(args.windows, 5), dev)
+    if "ema_step" in what and rank == 0:
+        ema_step(torch, args.steps, args.windows, args.pool, args.settle, dev)
     if args.out and rank == 0:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
