@@ -45,6 +45,24 @@ int segmm_l1norm(const float* x, float* y, float* inv_scale, int64_t rows, int D
 #define SEGMM_ELEM_BF16 2
 int segmm_l1norm_h(const uint16_t* x, int elem, float* y, float* inv_scale, int64_t rows, int D, float* amax, uint16_t* planes, int ld2,
                    float* hdr, const float* scale_in, segmm_stream_t stream);
+/* 8-BIT INPUT FEATURES.  The same two kernels take their input as OCP e4m3fn, OCP e5m2 (gfx950's fp8 / bf8; not MI300's fnuz
+ * encodings) or int8: a quarter of float32's bytes.  Every code of the three formats is an exact fp32 value, so the definition of the
+ * 16-bit forms carries over unchanged: every output is the fp32 entry point's on the exactly widened input, bit for bit (NaN codes
+ * widen to NaN, e5m2's inf codes to inf).  No scale travels with a row: the rows are L1-normalised as they are read, which cancels
+ * a per-row scale up to the 1e-6 of the denominator; with normalize == 0 (segmm_gather_l1_b) the codes ARE the values.  `elem` is
+ * one of the three constants below; 1 and 2 belong to the _h forms, which keep refusing everything else.  x / table: 4-byte aligned,
+ * D % 4 == 0 (rows of an 8-bit tensor are 4-byte aligned only); every other argument as in the fp32 entry point. */
+#define SEGMM_ELEM_E4M3 3
+#define SEGMM_ELEM_E5M2 4
+#define SEGMM_ELEM_I8 5
+int segmm_l1norm_b(const uint8_t* x, int elem, float* y, float* inv_scale, int64_t rows, int D, float* amax, uint16_t* planes, int ld2,
+                   float* hdr, const float* scale_in, segmm_stream_t stream);
+/* The loader of an 8-bit table: float32 rows x [rows, D] -> codes q [rows, D] of type `elem`, one wave per row.  With a = max|x_j|
+ * (a < 2^-100 or not finite: all-zero codes, scale 0), the row is multiplied by s = 2^(8-e) (e4m3) / 2^(15-e) (e5m2), a = m 2^e with
+ * 0.5 <= m < 1 -- exact, |x s| < 256 / 32768, far inside either format -- or by r = 127 / a (int8), and every product is rounded to
+ * nearest, ties to even.  scale_out: optional, one float per row, the factor the row was multiplied by (the codes do not need it under
+ * L1 normalisation).  x: 16-byte aligned, q: 4-byte aligned, D % 4 == 0. */
+int segmm_quantize_rows(const float* x, int64_t rows, int D, int elem, uint8_t* q, float* scale_out, segmm_stream_t stream);
 /* PLANE OUTPUTS of producers (the four trailing arguments `planes, ld2, hdr, scale_in` of segmm_l1norm, segmm_gather_l1,
  * segmm_layernorm_fwd / _bwd; segmm_attn_planes_t; c_planes / c_hdr / c_scale_in of segmm_gemm_p): a kernel that writes a
  * tensor some GEMM reads can also write that tensor's P32 fp16 planes (format: segmm_gemm_p) with the DELAYED scale
@@ -604,6 +622,11 @@ int segmm_gather_l1(const float* table, int64_t n_lines, int D, const int64_t* i
 /* the same from a table of 16-bit elements (SEGMM_ELEM_F16 / SEGMM_ELEM_BF16, see segmm_l1norm_h): out, mask, maxima and planes are
  * those of segmm_gather_l1 on the widened table, bit for bit.  table: 8-byte aligned, D % 4 == 0. */
 int segmm_gather_l1_h(const uint16_t* table, int elem, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize,
+                      float* out, uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in,
+                      segmm_stream_t stream);
+/* the same from a table of 8-bit elements (SEGMM_ELEM_E4M3 / _E5M2 / _I8, see segmm_l1norm_b), with either `normalize`.  table: 4-byte
+ * aligned, D % 4 == 0. */
+int segmm_gather_l1_b(const uint8_t* table, int elem, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize,
                       float* out, uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in,
                       segmm_stream_t stream);
 /* (f)-1, the step before the gather: index batches assembled on the device from a COMPILED interaction table

@@ -674,6 +674,43 @@ int segmm_l1norm_h(const uint16_t* x, int elem, float* y, float* inv_scale, int6
     return 0;
 }
 
+static inline bool aligned4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
+static inline bool elem8(int elem) { return elem == SEGMM_ELEM_E4M3 || elem == SEGMM_ELEM_E5M2 || elem == SEGMM_ELEM_I8; }
+// the instance of an 8-bit row kernel for (elem, D): the V ladder of the 16-bit forms (one raw dword per lane and V)
+#define ROW_B_LAUNCH(KERNEL, ...)                                                                                        \
+    do {                                                                                                                 \
+        if (elem == SEGMM_ELEM_E4M3) { ROW_H_LAUNCH_V(KERNEL, ELEM_E4M3, __VA_ARGS__); }                                 \
+        else if (elem == SEGMM_ELEM_E5M2) { ROW_H_LAUNCH_V(KERNEL, ELEM_E5M2, __VA_ARGS__); }                            \
+        else { ROW_H_LAUNCH_V(KERNEL, ELEM_I8, __VA_ARGS__); }                                                           \
+    } while (0)
+
+int segmm_l1norm_b(const uint8_t* x, int elem, float* y, float* inv_scale, int64_t rows, int D, float* amax, uint16_t* planes, int ld2,
+                   float* hdr, const float* scale_in, segmm_stream_t stream) {
+    PLANE_OUT_CHECK("l1norm_b", D);
+    SEGMM_REQUIRE(elem8(elem), "l1norm_b: elem = %d (SEGMM_ELEM_E4M3 = 3, SEGMM_ELEM_E5M2 = 4, SEGMM_ELEM_I8 = 5)", elem);
+    SEGMM_REQUIRE(x && (y || inv_scale || (planes && scale_in)), "l1norm_b: null pointer");
+    SEGMM_REQUIRE(D > 0 && D % 4 == 0 && aligned4(x) && (!y || aligned16(y)), "l1norm_b: D %% 4 / alignment (D=%d)", D);
+    if (rows <= 0) return 0;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    ROW_B_LAUNCH(l1norm_b_kernel, x, y, inv_scale, (long long)rows, D, amax, plane_out(planes, ld2, hdr, scale_in));
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_quantize_rows(const float* x, int64_t rows, int D, int elem, uint8_t* q, float* scale_out, segmm_stream_t stream) {
+    SEGMM_REQUIRE(elem8(elem), "quantize_rows: elem = %d (SEGMM_ELEM_E4M3 = 3, SEGMM_ELEM_E5M2 = 4, SEGMM_ELEM_I8 = 5)", elem);
+    SEGMM_REQUIRE(x && q && rows >= 0, "quantize_rows: null pointer / rows");
+    SEGMM_REQUIRE(D > 0 && D % 4 == 0 && aligned16(x) && aligned4(q) && (!scale_out || aligned4(scale_out)),
+                  "quantize_rows: D %% 4 / alignment (D=%d)", D);
+    if (rows <= 0) return 0;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    if (elem == SEGMM_ELEM_E4M3) hipLaunchKernelGGL((quantize_rows_kernel<ELEM_E4M3>), grid, block, 0, (hipStream_t)stream, x, (long long)rows, D, q, scale_out);
+    else if (elem == SEGMM_ELEM_E5M2) hipLaunchKernelGGL((quantize_rows_kernel<ELEM_E5M2>), grid, block, 0, (hipStream_t)stream, x, (long long)rows, D, q, scale_out);
+    else hipLaunchKernelGGL((quantize_rows_kernel<ELEM_I8>), grid, block, 0, (hipStream_t)stream, x, (long long)rows, D, q, scale_out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 static int gemm_impl(int layout, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                      const float* bias, const float* row_scale, const float* residual, int ldr, int res_period,
                      int activation, float* aux, int ldaux, float drop_p, uint64_t seed, uint32_t site, int splits,
@@ -2066,6 +2103,21 @@ int segmm_gather_l1_h(const uint16_t* table, int elem, int64_t n_lines, int D, c
     if (rows <= 0) return 0;
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     ROW_H_LAUNCH(gather_l1_h_kernel, table, (long long)n_lines, D, (const long long*)idx, (long long)rows, normalize, out, mask, amax,
+                 plane_out(planes, ld2, hdr, scale_in));
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_gather_l1_b(const uint8_t* table, int elem, int64_t n_lines, int D, const int64_t* idx, int64_t rows, int normalize,
+                      float* out, uint8_t* mask, float* amax, uint16_t* planes, int ld2, float* hdr, const float* scale_in,
+                      segmm_stream_t stream) {
+    PLANE_OUT_CHECK("gather_l1_b", D);
+    SEGMM_REQUIRE(elem8(elem), "gather_l1_b: elem = %d (SEGMM_ELEM_E4M3 = 3, SEGMM_ELEM_E5M2 = 4, SEGMM_ELEM_I8 = 5)", elem);
+    SEGMM_REQUIRE(table && idx && out && n_lines > 0 && D > 0 && D % 4 == 0 && aligned4(table) && aligned16(out),
+                  "gather_l1_b: pointer / D %% 4 / alignment (D=%d)", D);
+    if (rows <= 0) return 0;
+    const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    ROW_B_LAUNCH(gather_l1_b_kernel, table, (long long)n_lines, D, (const long long*)idx, (long long)rows, normalize, out, mask, amax,
                  plane_out(planes, ld2, hdr, scale_in));
     LAUNCH_CHECK();
     return 0;

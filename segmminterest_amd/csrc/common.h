@@ -101,6 +101,64 @@ __device__ __forceinline__ f32x4 widen4(uint32_t a, uint32_t b) {
 template <int ELEM>
 __device__ __forceinline__ f32x4 widen4(u32x2 r) { return widen4<ELEM>(r.x, r.y); }
 
+// ---- 8-bit input features (ELEM = SEGMM_ELEM_E4M3 / _E5M2 / _I8 of the header): four consecutive elements are ONE 4-byte load (a row
+// of an 8-bit [n, D] tensor with D % 4 == 0 is 4-byte aligned only: D = 12 has a 12-byte pitch), ld_row4b's cache policy; the raw dword
+// stays in a register (1 VGPR per 4 elements) and is widened where it is used.  Every OCP e4m3fn / e5m2 code and every int8 is an exact
+// fp32 value and gfx950 converts each with one instruction (v_cvt_f32_fp8 / v_cvt_f32_bf8 with a byte select -- OCP on this part, not
+// MI300's fnuz --, v_cvt_f32_i32 of the sign-extended byte), so the rule of the 16-bit forms carries over: widen, then the fp32 twin's
+// arithmetic, gives that twin's result on the widened tensor, bit for bit.  What a code MEANS is fixed by tests/feature8_ref.py.
+constexpr int ELEM_E4M3 = 3, ELEM_E5M2 = 4, ELEM_I8 = 5;
+__device__ __forceinline__ uint32_t ld_row4q(const uint8_t* p) {
+#if SEGMM_ROW_NT >= 2
+    return __builtin_nontemporal_load((const uint32_t*)p);
+#else
+    return *(const uint32_t*)p;
+#endif
+}
+template <int ELEM>
+__device__ __forceinline__ f32x4 widen4(uint32_t w) {
+    static_assert(ELEM == ELEM_E4M3 || ELEM == ELEM_E5M2 || ELEM == ELEM_I8, "widen4(dword): an 8-bit element type");
+    const int i = (int)w;
+    if constexpr (ELEM == ELEM_E4M3) {
+        return f32x4{__builtin_amdgcn_cvt_f32_fp8(i, 0), __builtin_amdgcn_cvt_f32_fp8(i, 1), __builtin_amdgcn_cvt_f32_fp8(i, 2),
+                     __builtin_amdgcn_cvt_f32_fp8(i, 3)};
+    } else if constexpr (ELEM == ELEM_E5M2) {
+        return f32x4{__builtin_amdgcn_cvt_f32_bf8(i, 0), __builtin_amdgcn_cvt_f32_bf8(i, 1), __builtin_amdgcn_cvt_f32_bf8(i, 2),
+                     __builtin_amdgcn_cvt_f32_bf8(i, 3)};
+    } else {
+        return f32x4{(float)(int8_t)(w), (float)(int8_t)(w >> 8), (float)(int8_t)(w >> 16), (float)(i >> 24)};
+    }
+}
+
+// The row quantiser's code of one SCALED value v (|v| <= 256 / 32768 / 127.5 by the row rule of segmm_quantize_rows, far inside each
+// format's range): round to nearest, ties to even, in integer and exactly-rounded fp32 operations only, so that the host reference
+// (tests/feature8_ref.py) states the same thing in numpy.  fp8 (EB exponent bias, M mantissa bits): at or above the smallest normal
+// 2^(1-EB) the fp32 mantissa is rounded to M bits in place (a carry walks into the exponent by itself); below it the code is the
+// count of subnormal steps, rint(|v| 2^(EB-1+M)), which reaches the smallest normal's code 2^M on its own.
+template <int ELEM>
+__host__ __device__ __forceinline__ uint32_t quant8_code(float v) {
+    if constexpr (ELEM == ELEM_I8) {
+        return (uint32_t)(int)rintf(v) & 0xffu;
+    } else {
+        constexpr int EB = ELEM == ELEM_E4M3 ? 7 : 15, M = ELEM == ELEM_E4M3 ? 3 : 2;
+        union { float f; uint32_t u; } b;
+        b.f = v;
+        const uint32_t sign = (b.u >> 24) & 0x80u;
+        uint32_t u = b.u & 0x7fffffffu;
+        uint32_t code;
+        if (u >= ((uint32_t)(127 + 1 - EB) << 23)) {
+            u += ((u >> (23 - M)) & 1u) + ((1u << (22 - M)) - 1u);
+            code = (u >> (23 - M)) - ((uint32_t)(127 - EB) << M);
+        } else {
+            b.u = u;
+            union { float f; uint32_t u; } k;
+            k.u = (uint32_t)(127 + EB - 1 + M) << 23;
+            code = (uint32_t)(int)rintf(b.f * k.f);
+        }
+        return sign | code;
+    }
+}
+
 // ---------------------------------------------------------------- counter-based dropout stream
 // Dropout masks are a pure function of (seed, site, element index), so the backward kernels
 // regenerate them instead of storing them.  The generator is a stateless integer hash (two chained

@@ -431,6 +431,76 @@ __global__ __launch_bounds__(256) void gather_l1_h_kernel(const uint16_t* __rest
     plane_finish(po, amax, am, (unsigned)r, ps, r == 0 && lane == 0);
 }
 
+// The same for a table of 8-bit elements (ELEM: OCP e4m3fn, e5m2 or int8, common.h widen4 of one dword): a quarter of the float32
+// table's bytes per row.  Widened exactly, then gather_l1_kernel's arithmetic: its result on the widened table, bit for bit, with
+// either ``normalize``.  V > 0: the raw dwords stay in registers between the sum and the divide (1 VGPR per 4 elements, D <= 256 V <=
+// 2048); V == 0: two passes.  Table rows are 4-byte aligned only (D % 4 == 0): 4-byte loads.
+template <int ELEM, int V>
+__global__ __launch_bounds__(256) void gather_l1_b_kernel(const uint8_t* __restrict__ table, long long n_lines, int D,
+                                                          const long long* __restrict__ idx, long long rows, int normalize,
+                                                          float* __restrict__ out, unsigned char* __restrict__ mask, float* amax,
+                                                          PlaneOut po) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const long long i = idx[r];
+    const bool ok = i >= 0 && i < n_lines;
+    if (mask && lane == 0) mask[r] = ok ? 1 : 0;
+    float* o = out + r * D;
+    const float ps = plane_scale(po);
+    if (!ok) {
+        for (int c = lane * 4; c < D; c += 256) {
+            *(f32x4*)(o + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (ps > 0.f) plane_store4_pair(po.p, po.ld2, r, c, f32x4{0.f, 0.f, 0.f, 0.f}, ps);
+        }
+        plane_finish(po, amax, 0.f, (unsigned)r, ps, r == 0 && lane == 0);
+        return;
+    }
+    const uint8_t* t = table + i * D;
+    float s = 0.f, am = 0.f;
+    if constexpr (V > 0) {
+        uint32_t rw[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int c = lane * 4 + k * 256;
+            rw[k] = 0u;
+            if (c < D) {
+                rw[k] = ld_row4q(t + c);
+                const f32x4 v = widen4<ELEM>(rw[k]);
+                s += fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w);
+            }
+        }
+        if (normalize) s = wave_sum(s) + 1e-6f;
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const int c = lane * 4 + k * 256;
+            if (c < D) {
+                f32x4 v = widen4<ELEM>(rw[k]);
+                if (normalize) { v.x /= s; v.y /= s; v.z /= s; v.w /= s; }
+                *(f32x4*)(o + c) = v;
+                if (ps > 0.f) plane_store4_pair(po.p, po.ld2, r, c, v, ps);
+                am = absmax4(am, v);
+            }
+        }
+    } else {
+        if (normalize) {
+            for (int c = lane * 4; c < D; c += 256) {
+                const f32x4 v = widen4<ELEM>(ld_row4q(t + c));
+                s += fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w);
+            }
+            s = wave_sum(s) + 1e-6f;
+        }
+        for (int c = lane * 4; c < D; c += 256) {
+            f32x4 v = widen4<ELEM>(ld_row4q(t + c));
+            if (normalize) { v.x /= s; v.y /= s; v.z /= s; v.w /= s; }
+            *(f32x4*)(o + c) = v;
+            if (ps > 0.f) plane_store4_pair(po.p, po.ld2, r, c, v, ps);
+            am = absmax4(am, v);
+        }
+    }
+    plane_finish(po, amax, am, (unsigned)r, ps, r == 0 && lane == 0);
+}
+
 // ---------------------------------------------------------------- delayed scaling: end-of-pass update of the site scales
 // arena: n_rows site headers of the pass that just ended; site_idx[r] = index of row r's tensor site in site_scale (< 0:
 // none).  For every row that was produced (max > 0): site_scale[idx] = the power of two s with max * s in

@@ -142,6 +142,110 @@ __global__ __launch_bounds__(256) void l1norm_h_kernel(const uint16_t* __restric
     }
 }
 
+// The same for an 8-bit x (ELEM: OCP e4m3fn, e5m2 or int8, common.h widen4 of one dword): widened exactly, then the arithmetic
+// above, so the result is segmm_l1norm's on the widened tensor, bit for bit.  V > 0: the row's raw dwords stay in registers between
+// the two passes (1 VGPR per 4 elements, D <= 256 V <= 2048) and x is read once; V == 0: the two-pass loop, for wider rows.
+template <int ELEM, int V>
+__global__ __launch_bounds__(256) void l1norm_b_kernel(const uint8_t* __restrict__ x, float* y, float* inv_scale, long long rows, int D,
+                                                       float* amax, PlaneOut po) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const uint8_t* xr = x + row * D;
+    uint32_t rw[V > 0 ? V : 1];
+    float s = 0.f;
+    if constexpr (V > 0) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const int c = lane * 4 + i * 256;
+            rw[i] = 0u;
+            if (c < D) {
+                rw[i] = ld_row4q(xr + c);
+                const f32x4 v = widen4<ELEM>(rw[i]);
+                s += fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w);
+            }
+        }
+    } else {
+        for (int c = lane * 4; c < D; c += 256) {
+            const f32x4 v = widen4<ELEM>(ld_row4q(xr + c));
+            s += fabsf(v.x) + fabsf(v.y) + fabsf(v.z) + fabsf(v.w);
+        }
+    }
+    s = wave_sum(s);
+    const float inv = 1.0f / (s + 1e-6f);
+    if (inv_scale && lane == 0) inv_scale[row] = inv;
+    const float ps = plane_scale(po);
+    if (y || ps > 0.f) {
+        const float den = s + 1e-6f;
+        float am = 0.f;
+        if constexpr (V > 0) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const int c = lane * 4 + i * 256;
+                if (c < D) {
+                    f32x4 o = widen4<ELEM>(rw[i]);
+                    o.x /= den; o.y /= den; o.z /= den; o.w /= den;
+                    if (y) st_row4b(y + row * D + c, o);
+                    if (ps > 0.f) plane_store4_pair(po.p, po.ld2, row, c, o, ps);
+                    am = absmax4(am, o);
+                }
+            }
+        } else {
+            for (int c = lane * 4; c < D; c += 256) {
+                f32x4 o = widen4<ELEM>(ld_row4q(xr + c));
+                o.x /= den; o.y /= den; o.z /= den; o.w /= den;
+                if (y) *(f32x4*)(y + row * D + c) = o;
+                if (ps > 0.f) plane_store4_pair(po.p, po.ld2, row, c, o, ps);
+                am = absmax4(am, o);
+            }
+        }
+        plane_finish(po, amax, am, (unsigned)row, ps, row == 0 && lane == 0);
+    }
+}
+
+// ---------------------------------------------------------------- float32 rows -> 8-bit codes (the loader of an 8-bit feature table)
+// One wave per row.  a = max|x_j|, taken on the bit patterns (an unsigned compare orders |x| and puts NaN above inf, so a non-finite
+// element is seen whatever its place); a < 2^-100 or non-finite: all-zero codes, scale 0.  Otherwise the row is multiplied by
+//   e4m3: s = 2^(8-e), e5m2: s = 2^(15-e)  (a = m 2^e, 0.5 <= m < 1: a power of two, the product is exact, |x s| < 256 / 32768)
+//   int8: r = 127 / a  (a true division; |rint(x r)| <= 127)
+// and each product becomes its code by quant8_code (common.h): round to nearest even.  Four codes are one dword store (q rows are
+// 4-byte aligned: D % 4 == 0).  The scale is not kept with the codes: the rows are L1-normalised as they are read, which cancels it.
+// The rule is stated in numpy in tests/feature8_ref.py; this kernel gives its bytes.
+template <int ELEM>
+__global__ __launch_bounds__(256) void quantize_rows_kernel(const float* __restrict__ x, long long rows, int D, uint8_t* __restrict__ q,
+                                                            float* __restrict__ scale_out) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = x + row * D;
+    uint32_t a = 0u;
+    for (int c = lane * 4; c < D; c += 256) {
+        const f32x4 v = *(const f32x4*)(xr + c);
+        const uint32_t m0 = max(__float_as_uint(v.x) & 0x7fffffffu, __float_as_uint(v.y) & 0x7fffffffu);
+        const uint32_t m1 = max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu);
+        a = max(a, max(m0, m1));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a = max(a, (uint32_t)__shfl_xor((int)a, o, 64));
+    const bool live = a >= ((127u - 100u) << 23) && a < 0x7f800000u;
+    float s = 0.f;
+    if (live) {
+        if constexpr (ELEM == ELEM_I8) s = 127.0f / __uint_as_float(a);
+        else s = __uint_as_float((uint32_t)((ELEM == ELEM_E4M3 ? 261 : 268) - (int)(a >> 23)) << 23);      // e = (a >> 23) - 126
+    }
+    if (scale_out && lane == 0) scale_out[row] = s;
+    uint32_t* qr = (uint32_t*)(q + row * D);
+    for (int c = lane * 4; c < D; c += 256) {
+        uint32_t w = 0u;
+        if (live) {
+            const f32x4 v = *(const f32x4*)(xr + c);
+            w = quant8_code<ELEM>(v.x * s) | (quant8_code<ELEM>(v.y * s) << 8) | (quant8_code<ELEM>(v.z * s) << 16) |
+                (quant8_code<ELEM>(v.w * s) << 24);
+        }
+        qr[c >> 2] = w;
+    }
+}
+
 // ---------------------------------------------------------------- LayerNorm forward (eps 1e-12, encoder.py:39-40)
 // y = LN(x) * gamma + beta, optional dropout on y (embedding, encoder.py:461,471); saves mean / rstd.
 // V = float4 per lane (d <= 256 V): the row lives in 4V registers, so the register count -- and with it the

@@ -233,7 +233,7 @@ def torch_fallback(what):
     result without any error."""
     if RECORDER is not None:
         raise RuntimeError("record(): %s runs a torch kernel inside the step; a recorded step would silently drop it "
-                           "(pass bool masks, int64 ids / labels and contiguous float32 / float16 / bfloat16 features, at most %d ids per table lookup)" % (what, ARGSORT_MAX))
+                           "(pass bool masks, int64 ids / labels and contiguous float32 / float16 / bfloat16 / 8-bit features, at most %d ids per table lookup)" % (what, ARGSORT_MAX))
 
 
 def mark(kind, backbone=0, layer=0):
@@ -449,20 +449,28 @@ def _po(po):
 
 ELEM_F16, ELEM_BF16 = _K["SEGMM_ELEM_F16"], _K["SEGMM_ELEM_BF16"]
 _ELEM = {torch.float16: ELEM_F16, torch.bfloat16: ELEM_BF16}          # 16-bit input features -> the ``elem`` code of the _h entry points
+ELEM_E4M3, ELEM_E5M2, ELEM_I8 = _K["SEGMM_ELEM_E4M3"], _K["SEGMM_ELEM_E5M2"], _K["SEGMM_ELEM_I8"]
+# 8-bit input features -> the ``elem`` code of the _b entry points (OCP fp8 / bf8 and int8; uint8 is NOT a feature dtype: features are
+# signed, and a mask buffer must not pass for a table)
+_ELEM8 = {torch.float8_e4m3fn: ELEM_E4M3, torch.float8_e5m2: ELEM_E5M2, torch.int8: ELEM_I8}
+FEATURE_DTYPES = (torch.float32, torch.float16, torch.bfloat16) + tuple(_ELEM8)
+FEATURE_DTYPE_NAMES = ("torch.float32, torch.float16 or torch.bfloat16, or 8-bit: torch.float8_e4m3fn, torch.float8_e5m2 or torch.int8 "
+                       "(not torch.uint8: features are signed)")
 
 
 def _feat(t, name):
-    """The ``elem`` code of an input feature tensor (None: float32); refuses every other dtype and non-contiguous views."""
-    if t.dtype != torch.float32 and t.dtype not in _ELEM:
-        raise RuntimeError("%s is %s; input features are torch.float32, torch.float16 or torch.bfloat16" % (name, t.dtype))
+    """The ``elem`` code of an input feature tensor (None: float32; 1, 2: the _h forms; 3, 4, 5: the _b forms); refuses every other
+    dtype and non-contiguous views."""
+    if t.dtype not in FEATURE_DTYPES:
+        raise RuntimeError("%s is %s; input features are %s" % (name, t.dtype, FEATURE_DTYPE_NAMES))
     if not t.is_contiguous():
         raise RuntimeError("%s (%s) must be contiguous" % (name, t.dtype))
-    return _ELEM.get(t.dtype)
+    return _ELEM.get(t.dtype, _ELEM8.get(t.dtype))
 
 
 def l1norm(x, out=None, inv_scale=None, amax=None, po=None):
-    """``x``: float32, or float16 / bfloat16 (widened exactly in the kernel: the float32 result on ``x.float()``, bit for bit);
-    ``out`` / ``inv_scale``: float32.  ``amax``: optional zeroed [AMAX_SLOTS] vector that receives the partial maxima of |out|
+    """``x``: float32, or float16 / bfloat16, or float8_e4m3fn / float8_e5m2 / int8 (widened exactly in the kernel: the float32 result
+    on the widened ``x``, bit for bit); ``out`` / ``inv_scale``: float32.  ``amax``: optional zeroed [AMAX_SLOTS] vector that receives the partial maxima of |out|
     (fp16x3 GEMM operand); ``po``: optional plane output (PO)."""
     _dev(x)
     elem = _feat(x, "l1norm: x")
@@ -473,8 +481,33 @@ def l1norm(x, out=None, inv_scale=None, amax=None, po=None):
     rows = x.numel() // D
     if elem is None:
         _check(lib().segmm_l1norm(_ptr(x), _ptr(out), _ptr(inv_scale), rows, D, _ptr(amax), *_po(po), _stream()), "segmm_l1norm")
-    else:
+    elif x.dtype in _ELEM:
         _check(lib().segmm_l1norm_h(_ptr(x), elem, _ptr(out), _ptr(inv_scale), rows, D, _ptr(amax), *_po(po), _stream()), "segmm_l1norm_h")
+    else:
+        _check(lib().segmm_l1norm_b(_ptr(x), elem, _ptr(out), _ptr(inv_scale), rows, D, _ptr(amax), *_po(po), _stream()), "segmm_l1norm_b")
+
+
+def quantize_rows(x, dtype, out=None, scale_out=None):
+    """float32 rows ``x`` [..., D] -> 8-bit codes of ``dtype`` (float8_e4m3fn / float8_e5m2 / int8), one wave per row: each row is
+    scaled by a power of two (fp8: max|x| lands in [128, 256) / [16384, 32768)) or by 127 / max|x| (int8) and rounded to nearest even;
+    a row whose max|x| is under 2^-100 or not finite gives zero codes.  ``scale_out``: optional float32 [rows], the factor per row (0
+    for such a row).  The scale is not needed by the readers: L1 normalisation cancels it (segmm_quantize_rows in the header)."""
+    _dev(x)
+    if dtype not in _ELEM8:
+        raise RuntimeError("quantize_rows: dtype %s; the 8-bit feature dtypes are torch.float8_e4m3fn, torch.float8_e5m2 and torch.int8" % (dtype,))
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() < 1:
+        raise RuntimeError("quantize_rows: x must be a contiguous float32 tensor (got %s, contiguous=%s)" % (x.dtype, x.is_contiguous()))
+    D = x.shape[-1]
+    rows = x.numel() // D if D else 0
+    if out is None:
+        out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    if out.dtype != dtype or out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+        raise RuntimeError("quantize_rows: out must be a contiguous %s tensor of x's shape on x's device" % (dtype,))
+    if scale_out is not None and (scale_out.dtype != torch.float32 or scale_out.numel() != rows or not scale_out.is_contiguous()
+                                  or scale_out.device != x.device):
+        raise RuntimeError("quantize_rows: scale_out must be a contiguous float32 tensor of one element per row on x's device")
+    _check(lib().segmm_quantize_rows(_ptr(x), rows, D, _ELEM8[dtype], _ptr(out), _ptr(scale_out), _stream()), "segmm_quantize_rows")
+    return out
 
 
 def gemm(layout, M, N, K, A, lda, B, ldb, Cout, ldc, bias=None, row_scale=None, residual=None, ldr=0, res_period=0,
@@ -1424,7 +1457,8 @@ def row_metrics_accumulate(irec, frec, acc, S):
 
 def gather_l1(table, idx, normalize=True, out=None, mask=None, amax=None, po=None):
     """out[..., :] = (L1-normalised) table[idx[...]], mask[...] = idx in range; idx int64 of any shape.  ``table``: float32, or
-    float16 / bfloat16 (widened exactly in the kernel: the float32 result on ``table.float()``, bit for bit); ``out``: float32."""
+    float16 / bfloat16, or float8_e4m3fn / float8_e5m2 / int8 (widened exactly in the kernel: the float32 result on the widened table,
+    bit for bit); ``out``: float32."""
     _dev(table, idx)
     elem = _feat(table, "gather_l1: table")
     if table.dim() != 2:
@@ -1441,10 +1475,14 @@ def gather_l1(table, idx, normalize=True, out=None, mask=None, amax=None, po=Non
         with _kprof("gather_l1", rows * (8 * D + 9)):
             _check(lib().segmm_gather_l1(_ptr(table), table.shape[0], D, _ptr(idx.contiguous()), rows, int(bool(normalize)),
                                          _ptr(out), _ptr(mask), _ptr(amax), *_po(po), _stream()), "segmm_gather_l1")
-    else:          # a 16-bit table: 2 D bytes read, 4 D written per row
+    elif table.dtype in _ELEM:          # a 16-bit table: 2 D bytes read, 4 D written per row
         with _kprof("gather_l1", rows * (6 * D + 9)):
             _check(lib().segmm_gather_l1_h(_ptr(table), elem, table.shape[0], D, _ptr(idx.contiguous()), rows, int(bool(normalize)),
                                            _ptr(out), _ptr(mask), _ptr(amax), *_po(po), _stream()), "segmm_gather_l1_h")
+    else:          # an 8-bit table: D bytes read, 4 D written per row
+        with _kprof("gather_l1", rows * (5 * D + 9)):
+            _check(lib().segmm_gather_l1_b(_ptr(table), elem, table.shape[0], D, _ptr(idx.contiguous()), rows, int(bool(normalize)),
+                                           _ptr(out), _ptr(mask), _ptr(amax), *_po(po), _stream()), "segmm_gather_l1_b")
     return out, mask.view(torch.bool)
 
 

@@ -422,7 +422,8 @@ class Trainer(EvalPasses):
 
     def normalize(self, key, x):
         """a1: x / (sum|x| + 1e-6) over the feature dim, into a persistent float32 buffer.  ``x``: float32, or float16 / bfloat16 (half
-        the bytes over the host link; hipabi.l1norm widens exactly) -- the single point where a batch's feature dtype enters the step."""
+        the bytes over the host link), or float8_e4m3fn / float8_e5m2 / int8 (a quarter; hipabi.l1norm widens exactly) -- the single
+        point where a batch's feature dtype enters the step."""
         bk = (key, self._slot)
         buf = self._norm.get(bk)
         if buf is None or buf.shape != x.shape or buf.device != x.device:
@@ -922,22 +923,23 @@ class Trainer(EvalPasses):
                 raise RuntimeError("%s: batch[%r] is not contiguous" % (who, k))
             # the zero-copy paths of the step: anything else is converted by a torch kernel, which a replay would drop (the
             # conversions also raise by themselves while recording: hipabi.torch_fallback)
-            # (16-bit features: only the two tensors that go through normalize(); the recorded commands carry their element size, and
-            # run_recorded() refuses a batch of another dtype)
-            if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32 and not (
-                    k in ("user", "photo") and v.dtype in (torch.float16, torch.bfloat16)):
+            # (16-bit and 8-bit features: only the two tensors that go through normalize(); the recorded commands carry their element
+            # type, and run_recorded() refuses a batch of another dtype.  int8 is a feature dtype there and nowhere else.)
+            feat = k in ("user", "photo") and v.dtype in H.FEATURE_DTYPES if torch.is_tensor(v) else False
+            if torch.is_tensor(v) and v.is_floating_point() and v.dtype != torch.float32 and not feat:
                 raise RuntimeError("%s: batch[%r] is %s; the recorded %s takes float32 features (batch['user'] / batch['photo']: "
-                                   "float32, float16 or bfloat16)" % (who, k, v.dtype, what))
+                                   "float32, float16 or bfloat16, or 8-bit: float8_e4m3fn, float8_e5m2 or int8)" % (who, k, v.dtype, what))
             if torch.is_tensor(v) and k.endswith("_mask") and v.dtype != torch.bool:
                 raise RuntimeError("%s: batch[%r] is %s; the recorded %s takes bool masks" % (who, k, v.dtype, what))
-            if torch.is_tensor(v) and not v.is_floating_point() and v.dtype not in (torch.bool, torch.int64):
+            if torch.is_tensor(v) and not v.is_floating_point() and v.dtype not in (torch.bool, torch.int64) and not feat:
                 raise RuntimeError("%s: batch[%r] is %s; the recorded %s takes int64 ids and labels" % (who, k, v.dtype, what))
-        # one feature dtype per recorded batch: a batch that carries 16-bit features carries both tensors so (a pipeline stores its
-        # features in one format); a half-precision tensor next to a float32 one is the stray conversion record() has always refused
-        fdt = {k: batch[k].dtype for k in ("user", "photo") if torch.is_tensor(batch.get(k)) and batch[k].is_floating_point()}
+        # one feature dtype per recorded batch: a batch that carries 16-bit or 8-bit features carries both tensors so (a pipeline stores
+        # its features in one format); a half-precision tensor next to a float32 one is the stray conversion record() has always refused
+        fdt = {k: batch[k].dtype for k in ("user", "photo")
+               if torch.is_tensor(batch.get(k)) and (batch[k].is_floating_point() or batch[k].dtype == torch.int8)}
         if len(set(fdt.values())) > 1:
             raise RuntimeError("%s: batch['user'] is %s and batch['photo'] is %s; the recorded %s takes both feature tensors in "
-                               "one dtype (float32, float16 or bfloat16)" % (who, fdt["user"], fdt["photo"], what))
+                               "one dtype (float32, float16 or bfloat16, or one of the 8-bit dtypes)" % (who, fdt["user"], fdt["photo"], what))
 
     def _hyper(self):
         # under an lr_schedule the recorded commands carry the sentinel, not a rate: the rate may move, the schedule's presence not
