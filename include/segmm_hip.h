@@ -739,6 +739,30 @@ int segmm_store_head(const float* pred, const int32_t* rowidx, const float* vals
 int segmm_store_head_bwd(const float* g, const int32_t* rowidx, const float* vals, int64_t m, const float* neg_vals, int64_t m_neg,
                          const float* weight, const int64_t* duration, int64_t rows, int S, float* dpred, segmm_stream_t stream);
 
+/* The store's writer and its index build on the device; added under ABI version 30: nothing that existed changed.
+ * segmm_store_append: one batch of the inference pass into preallocated tables -- keys[row0 + r] = (user[r], photo[r], time_ms[r]) and
+ *   vals[row0 + r, 0 .. S) = logits[r * ld .. r * ld + S) for r < B, bit copies (keys int64 [capacity, 3], vals float32 [capacity, S]).
+ *   Any S >= 1, ld >= S and alignment of the rows (4-byte floats, 8-byte ids): 16-byte accesses where S % 4 == 0, ld % 4 == 0 and both
+ *   value bases are 16-byte aligned, one dword per lane otherwise.  Nothing outside rows [row0, row0 + B) is written.  B == 0 launches
+ *   nothing.  Refused by name: row0 < 0, row0 + B > capacity, a null pointer, S < 1, ld < S.  One launch, a recordable command: the recorded
+ *   dump (Trainer.dump_logits(recorded=True)) rewrites row0 / capacity / keys / vals per replay.
+ * segmm_store_index: the index of a store (the format stated above segmm_store_lookup) from its unsorted key rows keys [n, 3]:
+ *   out_keys [n, 3] / out_rows [n] hold, in their first *n_unique entries, the distinct keys in lexicographic SIGNED order and the row
+ *   of each key's LAST occurrence; *n_unique (device int64) = their number; the entries behind them are not written.  The order (user,
+ *   item, time, row) is total, so the result is the one of any correct comparison sort (bridge.LogitStore._build_index on the host).
+ *   The rows are sorted as 4-word tuples by a bitonic network in `ws` (segmm_store_index_ws(&bytes, n) gives its size -- a helper without a stream, not a command; 16-byte
+ *   aligned): chunks of 2048 tuples in LDS, every larger stride one global compare-exchange launch; padding slots compare above
+ *   every real tuple by a flag, never by a key value (any int64 triple is a legal key).  Then the last-of-run flags are counted per
+ *   block, the counts scanned by one workgroup, and the flagged tuples scattered to their ranks: separate launches, no workgroup
+ *   waits for another.  Deterministic.  n == 0 launches no kernel and clears *n_unique.  0 <= n <= 2^24 (SEGMM_STORE_INDEX_MAX);
+ *   beyond, the call is refused by name (the host-side index build, DeviceLogitStore.finalize() without on_device, has no limit). */
+#define SEGMM_STORE_INDEX_MAX 16777216
+int segmm_store_append(const int64_t* user, const int64_t* photo, const int64_t* time_ms, const float* logits, int ld, int B, int S,
+                       int64_t row0, int64_t capacity, int64_t* keys, float* vals, segmm_stream_t stream);
+int segmm_store_index_ws(int64_t* ws_bytes, int64_t n);
+int segmm_store_index(const int64_t* keys, int64_t n, void* ws, int64_t ws_bytes, int64_t* out_keys, int32_t* out_rows,
+                      int64_t* n_unique, segmm_stream_t stream);
+
 /* up to three column sums out_i[n] = sum_m X_i[m, n] of same-shaped matrices in one launch pair (X1/X2 may be null);
  * workspace: 3 * segmm_colsum_chunks(M) * N floats.  Used for the partial buffers of segmm_layernorm_bwd. */
 int segmm_colsum3(const float* X0, const float* X1, const float* X2, int ld, int64_t M, int N, float* out0, float* out1,

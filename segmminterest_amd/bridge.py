@@ -154,16 +154,76 @@ class DeviceLogitStore:
     (``LogitStore.weights``) with ``segmm_store_lookup`` and ``segmm_store_head`` (include/segmm_hip.h).  ``head`` forms no
     [B, I, S] tensor and is differentiable in ``pred``."""
 
-    def __init__(self, S: int = 40, device="cuda"):
+    def __init__(self, S: int = 40, device="cuda", capacity=None):
+        """``capacity`` (rows; None = the block list of ``add_batch``): the PREALLOCATED form -- one keys table [capacity, 3], one
+        values table [capacity, S] and a host-side row count; ``append`` writes a batch at the count with one ``segmm_store_append``
+        and the tables grow geometrically when a batch would not fit (``reserve`` sizes them ahead)."""
         self.S = S
         self.device = torch.device(device)
-        self._keys = []          # device [n_i, 3] int64 blocks
+        self._keys = []          # device [n_i, 3] int64 blocks (the block-list form)
         self._vals = []          # device [n_i, S] float32 blocks
+        self._ktab = self._vtab = None          # the preallocated form: tables [capacity, 3] int64 / [capacity, S] float32 ...
+        self._n = 0                             # ... and the rows written so far (a host integer: no synchronisation)
         self._index = None       # (keys [n, 3] int64, rows [n] int32) on the device
         self._maps = {}          # id(dict) -> (dict, its length, dense device map): the last MAX_MAPS dicts
+        if capacity is not None:
+            if int(capacity) < 0:
+                raise ValueError("DeviceLogitStore: capacity=%r" % (capacity,))
+            self.reserve(int(capacity))
 
     # ---- writer side
+    @property
+    def capacity(self):
+        """Rows of the preallocated tables; None in the block-list form."""
+        return None if self._ktab is None else self._ktab.shape[0]
+
+    def reserve(self, rows):
+        """Makes room for ``rows`` rows in all (a block-list store becomes a preallocated one, its blocks the tables' first rows): new
+        tables, the rows written so far moved by two ``segmm_copy_bytes`` on the stream.  No synchronisation."""
+        from . import hipabi as H
+        rows = int(rows)
+        if self._ktab is None:
+            k, v = self._cat()
+            self._keys, self._vals = [], []
+            old, self._n = (k, v), k.shape[0]
+        else:
+            old = (self._ktab, self._vtab)
+        if self._ktab is not None and rows <= self._ktab.shape[0]:
+            return self
+        cap = max(rows, self._n)
+        self._ktab = torch.empty((cap, 3), dtype=torch.int64, device=self.device)
+        self._vtab = torch.empty((cap, self.S), dtype=torch.float32, device=self.device)
+        if self._n:
+            H.copy_bytes(self._ktab[:self._n], old[0][:self._n])
+            H.copy_bytes(self._vtab[:self._n], old[1][:self._n])
+        return self
+
+    def _room(self, B):
+        """The tables hold ``B`` more rows behind the count: grown geometrically when they do not."""
+        if self._n + B > self._ktab.shape[0]:
+            self.reserve(max(2 * self._ktab.shape[0], self._n + B))
+
+    def append(self, user_id, photo_id, time_ms, logits):
+        """One batch at the current row count (preallocated form): device int64 [B] key columns, float32 [B, S] logits (any row stride),
+        ONE ``segmm_store_append``.  Nothing is converted: anything else is refused by name."""
+        from . import hipabi as H
+        if self._ktab is None:
+            raise RuntimeError("DeviceLogitStore.append: the store has no preallocated tables (DeviceLogitStore(capacity=...) or reserve())")
+        if logits.dim() != 2 or logits.shape[1] != self.S:
+            raise ValueError("logits have %s segments, store expects %d" % (list(logits.shape[1:]), self.S))
+        B = logits.shape[0]
+        self._room(B)
+        H.store_append(user_id, photo_id, time_ms, logits, self._n, self._ktab, self._vtab)
+        self._n += B
+        self._index = None
+
     def add_batch(self, user_id, photo_id, time_ms, logits):
+        if self._ktab is not None:
+            k = [torch.as_tensor(v).to(self.device, torch.int64).reshape(-1).contiguous() for v in (user_id, photo_id, time_ms)]
+            v = torch.as_tensor(logits).detach().to(self.device, torch.float32).reshape(k[0].shape[0], -1)
+            if v.shape[1] != self.S:
+                raise ValueError("logits have %d segments, store expects %d" % (v.shape[1], self.S))
+            return self.append(k[0], k[1], k[2], v.contiguous())
         k = torch.stack([torch.as_tensor(v).to(self.device, torch.int64).reshape(-1) for v in (user_id, photo_id, time_ms)], 1)
         v = torch.as_tensor(logits).detach().to(self.device, torch.float32, copy=True).reshape(k.shape[0], -1)          # a copy: forward buffers are reused
         if v.shape[1] != self.S:
@@ -173,6 +233,8 @@ class DeviceLogitStore:
         self._index = None
 
     def _cat(self):
+        if self._ktab is not None:          # the rows appended so far: views of the tables
+            return self._ktab[:self._n], self._vtab[:self._n]
         if len(self._keys) > 1:
             self._keys, self._vals = [torch.cat(self._keys, 0)], [torch.cat(self._vals, 0)]
         if not self._keys:
@@ -181,11 +243,23 @@ class DeviceLogitStore:
         return self._keys[0], self._vals[0]
 
     def __len__(self):
+        if self._ktab is not None:
+            return self._n
         return sum(k.shape[0] for k in self._keys)
 
-    def finalize(self):
+    def finalize(self, on_device=False):
         """Builds the index by ``LogitStore``'s rule (lexicographic order, last occurrence of a key wins): ONE device-to-host copy
-        of the key columns, the sort on the host, the sorted keys and their value rows back up."""
+        of the key columns, the sort on the host, the sorted keys and their value rows back up.
+        ``on_device=True`` (opt-in): the same index from ``segmm_store_index`` -- sort, run flags, scan and compaction as launches on
+        the stream, then ONE 8-byte read-back (the number of distinct keys, the pass's only synchronisation) to shape the index
+        tensors.  Built for up to ``hipabi.STORE_INDEX_MAX`` keys; beyond, the library refuses by name and this default still works."""
+        if self._index is None and on_device:
+            from . import hipabi as H
+            k, _ = self._cat()
+            ok, orows, nu = H.store_index(k)
+            m = int(nu.item())
+            # (copies when keys repeated: the views would keep the full [n, 3] / [n] outputs alive for the life of the index)
+            self._index = (ok, orows) if m == k.shape[0] else (ok[:m].clone(), orows[:m].clone())
         if self._index is None:
             k, _ = self._cat()
             h = LogitStore(self.S)

@@ -2236,6 +2236,86 @@ int segmm_store_head_bwd(const float* g, const int32_t* rowidx, const float* val
     return 0;
 }
 
+int segmm_store_append(const int64_t* user, const int64_t* photo, const int64_t* time_ms, const float* logits, int ld, int B, int S,
+                       int64_t row0, int64_t capacity, int64_t* keys, float* vals, segmm_stream_t stream) {
+    SEGMM_REQUIRE(B >= 0 && S >= 1 && ld >= S, "store_append: B = %d, S = %d, ld = %d (B >= 0, S >= 1, ld >= S)", B, S, ld);
+    SEGMM_REQUIRE(row0 >= 0, "store_append: negative row0 (%lld)", (long long)row0);
+    SEGMM_REQUIRE(capacity >= 0 && (int64_t)B <= capacity && row0 <= capacity - (int64_t)B,
+                  "store_append: rows [%lld, %lld) overflow the capacity of %lld rows", (long long)row0, (long long)row0 + B, (long long)capacity);
+    SEGMM_REQUIRE(user && photo && time_ms && logits && keys && vals, "store_append: null pointer");
+    SEGMM_REQUIRE(((((uintptr_t)user) | ((uintptr_t)photo) | ((uintptr_t)time_ms) | ((uintptr_t)keys)) & 7u) == 0 &&
+                  ((((uintptr_t)logits) | ((uintptr_t)vals)) & 3u) == 0, "store_append: ids need 8-byte, floats 4-byte alignment");
+    if (B == 0) return 0;
+    long long* kdst = (long long*)keys + 3 * row0;
+    unsigned* vdst = (unsigned*)vals + (size_t)row0 * S;
+    const bool v4 = S % 4 == 0 && ld % 4 == 0 && aligned16(logits) && aligned16(vdst);
+    const long long items = (long long)B * (v4 ? S / 4 : S) + 3ll * B;
+    const long long need = (items + 255) / 256;
+    const unsigned blocks = (unsigned)(need < 8192 ? need : 8192);
+    if (v4)
+        hipLaunchKernelGGL(store_append_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const long long*)user, (const long long*)photo,
+                           (const long long*)time_ms, (const unsigned*)logits, ld, (long long)B, S, kdst, vdst);
+    else
+        hipLaunchKernelGGL(store_append_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const long long*)user, (const long long*)photo,
+                           (const long long*)time_ms, (const unsigned*)logits, ld, (long long)B, S, kdst, vdst);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// the sort's padded length and the layout of the workspace: k0 | k1 | k2 (int64 [np2]) | row (int32 [np2]) | block counts (int32)
+static int store_index_np2(int64_t n) {
+    int np2 = STORE_SORT_CHUNK;
+    while (np2 < n) np2 <<= 1;
+    return np2;
+}
+static int64_t store_index_bytes(int np2) { return (int64_t)np2 * 28 + (int64_t)(np2 / STORE_SCAN_BLOCK) * 4; }
+
+int segmm_store_index_ws(int64_t* ws_bytes, int64_t n) {
+    SEGMM_REQUIRE(ws_bytes, "store_index_ws: null pointer");
+    SEGMM_REQUIRE(n >= 0 && n <= SEGMM_STORE_INDEX_MAX,
+                  "store_index_ws: n = %lld keys (0 <= n <= %d is built; finalize() without on_device builds the index on the host for any n)",
+                  (long long)n, SEGMM_STORE_INDEX_MAX);
+    *ws_bytes = n == 0 ? 0 : store_index_bytes(store_index_np2(n));
+    return 0;
+}
+
+int segmm_store_index(const int64_t* keys, int64_t n, void* ws, int64_t ws_bytes, int64_t* out_keys, int32_t* out_rows, int64_t* n_unique,
+                      segmm_stream_t stream) {
+    SEGMM_REQUIRE(n >= 0 && n <= SEGMM_STORE_INDEX_MAX,
+                  "store_index: n = %lld keys (0 <= n <= %d is built; finalize() without on_device builds the index on the host for any n)",
+                  (long long)n, SEGMM_STORE_INDEX_MAX);
+    SEGMM_REQUIRE(n_unique && (((uintptr_t)n_unique) & 7u) == 0, "store_index: null or misaligned n_unique");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        const hipError_t e = hipMemsetAsync(n_unique, 0, 8, s);
+        SEGMM_REQUIRE(e == hipSuccess, "store_index: hipMemsetAsync: %s", hipGetErrorString(e));
+        return 0;
+    }
+    SEGMM_REQUIRE(keys && out_keys && out_rows && ws, "store_index: null pointer");
+    SEGMM_REQUIRE(((((uintptr_t)keys) | ((uintptr_t)out_keys)) & 7u) == 0 && (((uintptr_t)out_rows) & 3u) == 0 && aligned16(ws),
+                  "store_index: keys need 8-byte, rows 4-byte, the workspace 16-byte alignment");
+    const int np2 = store_index_np2(n), nb = np2 / STORE_SCAN_BLOCK;
+    SEGMM_REQUIRE(ws_bytes >= store_index_bytes(np2), "store_index: %lld keys need a workspace of %lld bytes (got %lld)", (long long)n,
+                  (long long)store_index_bytes(np2), (long long)ws_bytes);
+    StoreSortWs w;
+    w.k0 = (long long*)ws; w.k1 = w.k0 + np2; w.k2 = w.k1 + np2; w.row = (int*)(w.k2 + np2);
+    int* sums = w.row + np2;
+    constexpr int C = STORE_SORT_CHUNK;
+    hipLaunchKernelGGL(store_index_init_kernel, dim3(np2 / 256), dim3(256), 0, s, (const long long*)keys, (int)n, np2, w);
+    hipLaunchKernelGGL(store_index_chunk_kernel, dim3(np2 / C), dim3(1024), 0, s, w, 2);
+    for (int k = 2 * C; k <= np2; k <<= 1) {
+        for (int j = k >> 1; j >= C; j >>= 1)
+            hipLaunchKernelGGL(store_index_global_step_kernel, dim3(np2 / 512), dim3(256), 0, s, w, np2, k, j);
+        hipLaunchKernelGGL(store_index_chunk_kernel, dim3(np2 / C), dim3(1024), 0, s, w, k);
+    }
+    // the real tuples are the first n of the sorted array; blocks wholly behind them count and scatter nothing
+    hipLaunchKernelGGL(store_index_count_kernel, dim3(nb), dim3(256), 0, s, w, (int)n, sums);
+    hipLaunchKernelGGL(store_index_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, (long long*)n_unique);
+    hipLaunchKernelGGL(store_index_scatter_kernel, dim3(nb), dim3(256), 0, s, w, (int)n, (const int*)sums, (long long*)out_keys, (int*)out_rows);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 int segmm_pool_tokens(const float* U, int Lu, const float* V, int Lv, float* out, int B, int d, int bins, segmm_stream_t stream) {
     SEGMM_REQUIRE(U && V && out && Lu > 0 && Lv > 0 && bins > 0 && d % 4 == 0 && aligned16(U) && aligned16(V) && aligned16(out),
                   "pool_tokens: pointer/alignment");

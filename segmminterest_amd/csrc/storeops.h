@@ -249,4 +249,180 @@ __global__ __launch_bounds__(256) void store_head_bwd_kernel(const float* __rest
     }
 }
 
+
+// ---------------------------------------------------------------- the writer: one batch of the inference pass into the tables
+// keys[row0 + r] = (user[r], photo[r], time[r]); vals[row0 + r, :] = logits[r * ld .. + S), bit copies.  The work items are flat:
+// first the B * S / V value chunks (V = 4: one 16-byte access; the host picks it only when S % 4 == 0, ld % 4 == 0 and both bases
+// are 16-byte aligned), then the 3 B key words.  The host has checked row0 + B <= capacity: `kdst` / `vdst` are the tables at row0.
+typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
+template <int V>
+__global__ __launch_bounds__(256) void store_append_kernel(const long long* __restrict__ user, const long long* __restrict__ photo,
+                                                           const long long* __restrict__ time, const unsigned* __restrict__ logits, int ld,
+                                                           long long B, int S, long long* __restrict__ kdst, unsigned* __restrict__ vdst) {
+    const int nch = S / V;
+    const long long n_val = B * nch, total = n_val + 3 * B;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        if (i < n_val) {
+            const long long r = i / nch;
+            const int c = (int)(i - r * nch) * V;
+            if constexpr (V == 4) *(u32x4s*)(vdst + r * S + c) = *(const u32x4s*)(logits + r * ld + c);
+            else vdst[r * S + c] = logits[r * ld + c];
+        } else {
+            const long long w = i - n_val, r = w / 3;
+            const int col = (int)(w - 3 * r);
+            kdst[w] = (col == 0 ? user : col == 1 ? photo : time)[r];
+        }
+    }
+}
+
+// ---------------------------------------------------------------- the index of a store, built where the keys are
+// include/segmm_hip.h: segmm_store_index.  The keys' rows are sorted as 4-word tuples (user, item, time, row) by a bitonic network of
+// the shape of argsort_chunk_kernel / argsort_global_step_kernel (rowops.h), kept as four arrays in the caller's workspace:
+// k0, k1, k2 (int64 [np2]) and row (int32 [np2]), np2 = the power of two >= max(n, STORE_SORT_CHUNK).  The order (three signed words,
+// then the row) is total over the real tuples, so the result does not depend on the network.  A padding slot has row = -1 and compares
+// above every real tuple by that test alone -- never by a key value: (INT64_MAX, INT64_MAX, INT64_MAX) is a legal key.
+// Then: last-of-run flags counted per block (store_index_count_kernel), the block counts scanned by one workgroup
+// (store_index_scan_kernel, which also writes n_unique), and the scatter of every run's last tuple to its rank
+// (store_index_scatter_kernel).  No kernel waits for another workgroup.
+constexpr int STORE_SORT_CHUNK = 2048;          // tuples a workgroup sorts / merges in LDS (28 bytes each: 56 KB)
+constexpr int STORE_SCAN_BLOCK = 1024;          // tuples per workgroup of the count / scatter kernels (256 threads x 4 in a row)
+
+struct StoreTuple { long long a, b, c; int row; };
+// a sorts strictly above b
+__device__ __forceinline__ bool store_tuple_above(const StoreTuple& x, const StoreTuple& y) {
+    if (x.row < 0 || y.row < 0) return x.row < 0 && y.row >= 0;          // padding: above every real tuple, equal to other padding
+    if (x.a != y.a) return x.a > y.a;
+    if (x.b != y.b) return x.b > y.b;
+    if (x.c != y.c) return x.c > y.c;
+    return x.row > y.row;
+}
+struct StoreSortWs { long long *k0, *k1, *k2; int* row; };
+
+__global__ __launch_bounds__(256) void store_index_init_kernel(const long long* __restrict__ keys, int n, int np2, StoreSortWs ws) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= np2) return;
+    const bool real = i < n;
+    ws.k0[i] = real ? keys[3 * (long long)i] : 0;
+    ws.k1[i] = real ? keys[3 * (long long)i + 1] : 0;
+    ws.k2[i] = real ? keys[3 * (long long)i + 2] : 0;
+    ws.row[i] = real ? i : -1;
+}
+// one chunk per workgroup; kfirst == 2: the whole network up to k = STORE_SORT_CHUNK; kfirst > STORE_SORT_CHUNK: the strides
+// j < STORE_SORT_CHUNK of stage k = kfirst.  Directions come from the global index.
+__global__ __launch_bounds__(1024) void store_index_chunk_kernel(StoreSortWs ws, int kfirst) {
+    constexpr int C = STORE_SORT_CHUNK;
+    __shared__ long long s0[C], s1[C], s2[C];
+    __shared__ int sr[C];
+    const int base = blockIdx.x * C;
+    for (int i = threadIdx.x; i < C; i += blockDim.x) {
+        s0[i] = ws.k0[base + i]; s1[i] = ws.k1[base + i]; s2[i] = ws.k2[base + i]; sr[i] = ws.row[base + i];
+    }
+    __syncthreads();
+    const int klast = kfirst == 2 ? C : kfirst;
+    for (int k = kfirst; k <= klast; k <<= 1) {
+        for (int j = (k > C ? C : k) >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (C >> 1); t += blockDim.x) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const bool up = ((base + i) & k) == 0;
+                const StoreTuple x{s0[i], s1[i], s2[i], sr[i]}, y{s0[l], s1[l], s2[l], sr[l]};
+                const bool swap = up ? store_tuple_above(x, y) : store_tuple_above(y, x);
+                if (swap) {
+                    s0[i] = y.a; s1[i] = y.b; s2[i] = y.c; sr[i] = y.row;
+                    s0[l] = x.a; s1[l] = x.b; s2[l] = x.c; sr[l] = x.row;
+                }
+            }
+            __syncthreads();
+        }
+        if (k >= C) break;
+    }
+    for (int i = threadIdx.x; i < C; i += blockDim.x) {
+        ws.k0[base + i] = s0[i]; ws.k1[base + i] = s1[i]; ws.k2[base + i] = s2[i]; ws.row[base + i] = sr[i];
+    }
+}
+__global__ __launch_bounds__(256) void store_index_global_step_kernel(StoreSortWs ws, int np2, int k, int j) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= (np2 >> 1)) return;
+    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+    const int l = i | j;
+    const bool up = (i & k) == 0;
+    const StoreTuple x{ws.k0[i], ws.k1[i], ws.k2[i], ws.row[i]}, y{ws.k0[l], ws.k1[l], ws.k2[l], ws.row[l]};
+    const bool swap = up ? store_tuple_above(x, y) : store_tuple_above(y, x);
+    if (swap) {
+        ws.k0[i] = y.a; ws.k1[i] = y.b; ws.k2[i] = y.c; ws.row[i] = y.row;
+        ws.k0[l] = x.a; ws.k1[l] = x.b; ws.k2[l] = x.c; ws.row[l] = x.row;
+    }
+}
+// 1 when sorted tuple i < n is the last of its run of equal keys (the tuple with the largest row of that key)
+__device__ __forceinline__ int store_index_last(const StoreSortWs& ws, int i, int n) {
+    if (i >= n) return 0;
+    if (i == n - 1) return 1;
+    return (ws.k0[i] != ws.k0[i + 1] || ws.k1[i] != ws.k1[i + 1] || ws.k2[i] != ws.k2[i + 1]) ? 1 : 0;
+}
+// flags of the workgroup's STORE_SCAN_BLOCK tuples (thread t: tuples 4 t .. 4 t + 3 of the block) and, in `excl`, the number of flags
+// in front of the thread's first tuple inside the block; returns the block's total to every thread
+__device__ __forceinline__ int store_index_block_scan(const StoreSortWs& ws, int n, int (&f)[4], int& excl) {
+    __shared__ int s[256];
+    const int first = blockIdx.x * STORE_SCAN_BLOCK + 4 * threadIdx.x;
+    int mine = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { f[u] = store_index_last(ws, first + u, n); mine += f[u]; }
+    s[threadIdx.x] = mine;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int v = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    excl = s[threadIdx.x] - mine;
+    return s[255];
+}
+__global__ __launch_bounds__(256) void store_index_count_kernel(StoreSortWs ws, int n, int* __restrict__ sums) {
+    int f[4], excl;
+    const int total = store_index_block_scan(ws, n, f, excl);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+// sums[0 .. nb) -> their exclusive scan in place, by ONE workgroup (rounds of 1024 with a running carry); n_unique = the total
+__global__ __launch_bounds__(1024) void store_index_scan_kernel(int* __restrict__ sums, int nb, long long* __restrict__ n_unique) {
+    __shared__ int s[1024];
+    __shared__ int carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += 1024) {
+        const int i = b0 + threadIdx.x;
+        const int mine = i < nb ? sums[i] : 0;
+        s[threadIdx.x] = mine;
+        __syncthreads();
+        for (int o = 1; o < 1024; o <<= 1) {
+            const int v = threadIdx.x >= o ? s[threadIdx.x - o] : 0;
+            __syncthreads();
+            s[threadIdx.x] += v;
+            __syncthreads();
+        }
+        const int c = carry;
+        if (i < nb) sums[i] = c + s[threadIdx.x] - mine;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = c + s[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *n_unique = carry;
+}
+__global__ __launch_bounds__(256) void store_index_scatter_kernel(StoreSortWs ws, int n, const int* __restrict__ sums,
+                                                                  long long* __restrict__ out_keys, int* __restrict__ out_rows) {
+    int f[4], excl;
+    store_index_block_scan(ws, n, f, excl);
+    const int first = blockIdx.x * STORE_SCAN_BLOCK + 4 * threadIdx.x;
+    long long pos = (long long)sums[blockIdx.x] + excl;          // < n: a flagged tuple's rank among the flagged ones
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (f[u]) {
+            const int i = first + u;
+            out_keys[3 * pos] = ws.k0[i]; out_keys[3 * pos + 1] = ws.k1[i]; out_keys[3 * pos + 2] = ws.k2[i];
+            out_rows[pos] = ws.row[i];
+            ++pos;
+        }
+    }
+}
+
 }  // namespace segmm

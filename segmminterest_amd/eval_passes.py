@@ -180,13 +180,19 @@ class EvalPasses:
                      vid_id=batch["photo_identity_id"], vid_mask=vm, gt=batch["label"], mode=mode)
 
     @torch.no_grad()
-    def dump_logits(self, splits, store=None, ema: bool = False):
+    def dump_logits(self, splits, store=None, ema: bool = False, recorded: bool = False):
         """The dump loop of the reference's inference script (inference/save_logits_for_all_leave_SegMM.py:105-146): eval mode,
         ``mode="inference"`` over every batch of every split in order, ``test_logits["<user_id>-<photo_id>-<time_ms>"] = logits`` --
         into a :class:`bridge.DeviceLogitStore`, so the logits stay on the device and no batch synchronises with the host.  ``splits``:
         an iterable of batch iterables (train, valid, test; ``DeviceBatches`` yields the three key columns on the device).
-        ``ema=True`` (needs ``Trainer(ema=...)``): the logits of the averaged weights (``ema.applied()``)."""
+        ``ema=True`` (needs ``Trainer(ema=...)``): the logits of the averaged weights (``ema.applied()``).
+        ``recorded=True`` (opt-in; single process): the inference forward is replayed from one recorded launch sequence and every
+        batch ends in ONE ``segmm_store_append`` into a preallocated store (:meth:`_dump_recorded`); the same keys and values, bit
+        for bit."""
         from .bridge import DeviceLogitStore
+        if recorded:
+            with self._ema_scope(ema, "dump_logits"):
+                return self._dump_recorded(splits, store)
         with self._ema_scope(ema, "dump_logits"):
             self.opt.flush_tables()          # lazy tables: every row current before the forward reads them
             for batches in splits:
@@ -198,6 +204,120 @@ class EvalPasses:
         if store is None:
             store = DeviceLogitStore(device=next(self.model.parameters()).device)
         return store
+
+    # ---- a logit dump whose batches are replayed from C (recorded inference forward + ONE segmm_store_append)
+    _DUMP_WHO = "dump_logits(recorded=True)"
+    _DUMP_KEYS = ("user_id", "photo_id", "time_ms")
+
+    def _dump_refuse(self, batch):
+        """What the recorded dump cannot take of a batch, refused by name before anything of it is enqueued."""
+        self._refuse_unrecordable(batch, self._DUMP_WHO, "dump batch")
+        dev = next(self.model.parameters()).device
+        for k in self._DUMP_KEYS:
+            v = batch.get(k)
+            if not torch.is_tensor(v) or v.device != dev or v.dtype != torch.int64 or v.dim() != 1 or v.shape[0] != batch["label"].shape[0]:
+                got = "missing" if v is None else ("%s %s on %s" % (tuple(v.shape), v.dtype, v.device) if torch.is_tensor(v) else type(v).__name__)
+                raise RuntimeError("%s: batch[%r] is %s; the store's writer reads the three key columns (user_id, photo_id, time_ms) as int64 "
+                                   "[B] tensors on %s (DeviceBatches yields them so); use recorded=False" % (self._DUMP_WHO, k, got, dev))
+
+    def _dump_recorded(self, splits, store):
+        """The batch loop of ``dump_logits(recorded=True)``, after :meth:`valid_enqueue`: lazy tables are flushed and the weight planes
+        split (``ParamStore.ensure``) ahead of the pass; the FIRST batch of a shape runs launch by launch while it is recorded
+        (``recording.capture``, a private memory pool and a private header arena: the recording lives beside the validation recording
+        and a recorded training step), its tail ONE ``segmm_store_append``; every later batch of that shape, in this and in later
+        calls, is replayed with one C call per phase.  Per replay the append command's ``row0`` / ``capacity`` / ``keys`` / ``vals``
+        are rewritten by name (the store's tables may have grown in between) and the batch's feature, mask, id and key-column
+        pointers are re-based by the recorder.  A batch of another shape (the short last batch of a split) takes the eager forward
+        with the same append tail.  The evaluation forward keeps three GEMM products whatever ``mixed_precision`` says.
+        Refused by name: data parallelism (an active ``DPComm``), batches the recorder cannot take, a batch without the three key
+        columns on the device, a learnable position bias (its inference head adds the bias with torch kernels).
+        The recording keeps the input-stage buffers of the recorded batch alive (``held``): the trainer replaces them when a batch
+        of another shape is normalised, and a replay must never write memory that has gone back to the allocator."""
+        from .bridge import DeviceLogitStore
+        who = self._DUMP_WHO
+        if self.comm.active:
+            raise RuntimeError("%s is not supported under data parallelism (an active DPComm): every rank would record and fill a store "
+                               "of its own rows; use recorded=False" % who)
+        model, st = self.model, self.model._store
+        if getattr(model, "bias_weight", None) is not None:
+            raise RuntimeError("%s: the model has a learnable position bias, which the inference head adds with torch kernels a replay would "
+                               "drop; use recorded=False" % who)
+        self.opt.flush_tables()          # lazy tables: flushed ahead of the pass, never inside its recording
+        model.eval()
+        dev = next(model.parameters()).device
+        ensured = False
+        for batches in splits:
+            for batch in batches:
+                self._dump_refuse(batch)
+                B, S = batch["label"].shape
+                if store is None:
+                    store = DeviceLogitStore(S=S, device=dev, capacity=max(4 * B, 1024))
+                elif store.capacity is None:
+                    store.reserve(len(store) + max(4 * B, 1024))
+                if store.S != S:
+                    raise ValueError("logits have %d segments, store expects %d" % (S, store.S))
+                if not ensured:          # the weights of the moment: their planes are split here, ahead of the pass's first replay
+                    st.ensure()
+                    ensured = True
+                self._pf = None          # (like eval_step: a prefetched input stage is dropped)
+                store._room(B)           # growth happens here, on the stream, never inside the recording
+                r = self.__dict__.get("_dump_rec")
+                if r is None:
+                    self._dump_record(batch, store)
+                elif R.batch_shapes(batch) == r["spans"]:
+                    self._dump_replay(r, batch, store)
+                else:
+                    self._dump_tail(batch, self.eval_step(batch, mode="inference")["logits"], store)
+        if store is None:
+            store = DeviceLogitStore(device=dev)
+        return store
+
+    def _dump_tail(self, batch, logits, store):
+        """The device tail of a dump batch: ONE segmm_store_append at the store's row count.  No synchronisation."""
+        H.mark(H.PHASE_STEP_TAIL)
+        store.append(batch["user_id"], batch["photo_id"], batch["time_ms"], logits)
+
+    def _dump_record(self, batch, store):
+        """Runs a dump batch launch by launch while recording it (see :meth:`_dump_recorded`)."""
+        st = self.model._store
+        side, aux = st.side_stream(), st.aux_stream()          # both exist before the recorder maps their handles to slots
+        hold = self.__dict__.setdefault("_dump_hdr", {})
+        with R.capture(st, side.cuda_stream, aux.cuda_stream) as cap, st.hdr_private_arena(hold) as arena:
+            H.mark(H.PHASE_STEP_BEGIN)
+            H.fill_zero(arena[:1])          # (the arena is clean now; the replays clear what this batch drew: size patched below)
+            logits = self.eval_step(batch, mode="inference")["logits"]
+            self._dump_tail(batch, logits, store)
+        # What the recorded commands name must outlive the recording.  The trainer's normalised-feature buffers and their planes are
+        # kept per (input, slot) and REPLACED when a batch of another shape comes by (Trainer.normalize / _input_act): the short last
+        # batch of a split would free the buffers every replay writes, and the store's next table would be allocated over them.
+        held = (logits, dict(self.__dict__.get("_norm") or {}), dict(self.__dict__.get("_norm_planes") or {}))
+        r = R.finish(cap, (batch,))
+        ops = H.op_ids()
+        launches = [(ph, arr) for ph, arr in r["phases"] if arr is not None]
+        head, tail = launches[0], launches[-1]
+        fill = head[1][0]
+        appends = [arr[ci] for ph, arr in launches for ci in range(ph.n_cmds) if arr[ci].op == ops["segmm_store_append"]]
+        if (fill.op != ops["segmm_fill_zero"] or tail[0].kind != H.PHASE_STEP_TAIL or tail[0].n_cmds != 1 or len(appends) != 1
+                or tail[1][0].op != ops["segmm_store_append"]):
+            raise RuntimeError("%s: the recorded launch sequence does not have the expected head (header fill) and tail (one "
+                               "segmm_store_append)" % self._DUMP_WHO)
+        H.cmd_set_arg(fill, "segmm_fill_zero", "bytes", hold["used"] * H.SITE_FLOATS * 4)
+        r.update(append=appends[0], n_replays=0, held=held)
+        self._dump_rec = r
+
+    def _dump_replay(self, r, batch, store):
+        """Enqueues a dump batch from the recorded launch sequence: the append command's per-batch slots and the batch's addresses are
+        patched, then one C call per phase; the store's row count moves on the host."""
+        B = batch["label"].shape[0]
+        ap = r["append"]          # (slots that every replay rewrites: setting them ahead of a refused replay changes nothing)
+        H.cmd_set_arg(ap, "segmm_store_append", "row0", store._n)
+        H.cmd_set_arg(ap, "segmm_store_append", "capacity", store._ktab.shape[0])
+        H.cmd_set_arg(ap, "segmm_store_append", "keys", store._ktab.data_ptr())
+        H.cmd_set_arg(ap, "segmm_store_append", "vals", store._vtab.data_ptr())
+        R.replay(r, self._DUMP_WHO, "dump batch", batch)
+        store._n += B
+        store._index = None
+        r["n_replays"] += 1
 
     @torch.no_grad()
     def valid_model(self, batches, metrics=("valid_loss", "HR@1", "HR@3", "HR@5", "HR@10", "NDCG@1", "NDCG@3", "NDCG@5", "NDCG@10"),

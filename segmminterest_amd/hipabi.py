@@ -1633,6 +1633,71 @@ def store_head_bwd(g, S, rowidx=None, vals=None, neg_vals=None, weight=None, dur
     return dpred
 
 
+def store_append(user, photo, time_ms, logits, row0, keys, vals):
+    """``segmm_store_append``: the batch's key columns (device int64 [B] each) and its logits (float32 [B, S], rows ``logits.stride(0)``
+    floats apart) into rows [row0, row0 + B) of the tables keys (int64 [capacity, 3]) / vals (float32 [capacity, S]).  One launch, a
+    recordable command; an overflow is refused by the library."""
+    _dev(user, photo, time_ms, logits, keys, vals)
+    if (logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[1] < 1 or (logits.shape[1] > 1 and logits.stride(1) != 1)
+            or (logits.shape[0] > 1 and logits.stride(0) < logits.shape[1])):
+        raise RuntimeError("store_append: logits must be float32 [B, S] with unit column stride and a row stride >= S (got %s %s, strides %s)"
+                           % (logits.dtype, list(logits.shape), list(logits.stride())))
+    B, S = logits.shape
+    ld = logits.stride(0) if B > 1 else S
+    for t, nm in ((user, "user"), (photo, "photo"), (time_ms, "time_ms")):
+        _i64c(t, "store_append: " + nm, (B,))
+    cap = keys.shape[0]
+    _i64c(keys, "store_append: keys", (cap, 3))
+    if vals.dtype != torch.float32 or not vals.is_contiguous() or tuple(vals.shape) != (cap, S):
+        raise RuntimeError("store_append: vals must be contiguous float32 [%d, %d] (got %s %s)" % (cap, S, vals.dtype, list(vals.shape)))
+    if B == 0:          # (an empty batch has no addresses to pass: nothing is launched)
+        if not 0 <= int(row0) <= cap:
+            raise RuntimeError("store_append: row0 = %d outside the capacity of %d rows" % (row0, cap))
+        return
+    with _kprof("store_append", B * (8 * S + 48)):
+        _check(lib().segmm_store_append(_ptr(user), _ptr(photo), _ptr(time_ms), _ptr(logits), int(ld), int(B), int(S), int(row0), int(cap), _ptr(keys),
+                                        _ptr(vals), _stream()), "segmm_store_append")
+
+
+STORE_INDEX_MAX = _K["SEGMM_STORE_INDEX_MAX"]          # keys segmm_store_index is built for
+
+
+def store_index_ws_bytes(n):
+    """Bytes of workspace ``segmm_store_index`` needs for ``n`` keys (refused by name beyond STORE_INDEX_MAX)."""
+    nb = _i64(0)
+    _check(_lib_real().segmm_store_index_ws(C.byref(nb), int(n)), "segmm_store_index_ws")
+    return int(nb.value)
+
+
+def store_index(keys, ws=None, out_keys=None, out_rows=None, n_unique=None):
+    """``segmm_store_index``: keys (device int64 [n, 3], unsorted, duplicates allowed) -> (out_keys int64 [n, 3], out_rows int32 [n],
+    n_unique int64 [1]) on the device: the first n_unique entries are the index ``segmm_store_lookup`` takes (sorted unique keys, the
+    row of each key's last occurrence).  Never synchronises; ``ws``: a uint8 tensor of ``store_index_ws_bytes(n)`` bytes (allocated
+    here when not given)."""
+    _dev(keys)
+    n = keys.shape[0]
+    _i64c(keys, "store_index: keys", (n, 3))
+    need = store_index_ws_bytes(n)
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=keys.device)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise RuntimeError("store_index: %d keys need a contiguous uint8 workspace of %d bytes" % (n, need))
+    if out_keys is None:
+        out_keys = torch.empty((n, 3), dtype=torch.int64, device=keys.device)
+    if out_rows is None:
+        out_rows = torch.empty((n,), dtype=torch.int32, device=keys.device)
+    if n_unique is None:
+        n_unique = torch.empty((1,), dtype=torch.int64, device=keys.device)
+    _i64c(out_keys, "store_index: out_keys", (n, 3)), _i64c(n_unique, "store_index: n_unique", (1,))
+    if out_rows.dtype != torch.int32 or not out_rows.is_contiguous() or tuple(out_rows.shape) != (n,):
+        raise RuntimeError("store_index: out_rows must be contiguous int32 [%d]" % n)
+    _dev(ws, out_keys, out_rows, n_unique)
+    with _kprof("store_index", 56 * n):
+        _check(lib().segmm_store_index(_ptr(keys) if n else None, n, _ptr(ws) if n else None, ws.numel(), _ptr(out_keys) if n else None,
+                                       _ptr(out_rows) if n else None, _ptr(n_unique), _stream()), "segmm_store_index")
+    return out_keys, out_rows, n_unique
+
+
 def pool_tokens(U, Lu, V, Lv, out, B, d, bins):
     """AdaptiveAvgPool1d(bins) over the tokens of cat(U[B,Lu,d], V[B,Lv,d]) (CrossMLP ablation)."""
     _dev(U, V, out)
