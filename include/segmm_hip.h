@@ -773,6 +773,19 @@ int segmm_colsum3(const float* X0, const float* X1, const float* X2, int ld, int
 int segmm_pool_tokens(const float* U, int Lu, const float* V, int Lv, float* out, int B, int d, int bins, segmm_stream_t stream);
 int segmm_pool_tokens_bwd(const float* dOut, float* dU, int Lu, float* dV, int Lv, int B, int d, int bins, segmm_stream_t stream);
 
+/* Spatial-reduction attention (sr_ratio r > 1, encoder.py:23-31,84-102; added under ABI version 30: nothing that existed changed).
+ * The reducing Conv1d(d, d, r, stride = r, padding = p = (r - 1) / 2) has non-overlapping windows: packed side by side they make the
+ * conv one NT GEMM with the weight [d, d, r] read, as stored, as a row-major [d, r d] matrix (K index c r + t).
+ * Ls = S / r must equal the conv length (S + 2 p - r) / r + 1 and be >= 1; 2 <= r <= 8; d % 4 == 0: anything else is refused by name.
+ * segmm_sr_pack:   A[b Ls + j, c r + t] = x[(b S + j r - p + t) ldx + c] if 0 <= j r - p + t < S else 0   (A: [B Ls, r d], dense);
+ *   amax: optional zeroed [SEGMM_AMAX_SLOTS] array receiving the partial maxima of |A|; m_sr (optional, needs m [B, S]):
+ *   m_sr[b, j] = OR over t < r of m[b, j r + t] -- the pooled key mask, NOT shifted by p (the reference's max_pool1d).
+ * segmm_sr_unpack: G[b, i, c] = res[b, i, c] + dA[b Ls + (i + p) / r, c r + (i + p) % r] if (i + p) / r < Ls, else res[b, i, c]; res may
+ *   be NULL (then the dA element itself, or 0).  G, res: [B S, d] dense; one fp32 add per element: deterministic.  G is neither operand. */
+int segmm_sr_pack(const float* x, int ldx, const uint8_t* m, float* A, uint8_t* m_sr, float* amax, int B, int S, int d, int r,
+                  segmm_stream_t stream);
+int segmm_sr_unpack(const float* dA, const float* res, float* G, int B, int S, int d, int r, segmm_stream_t stream);
+
 /* ---- Recorded launch sequences: the training step (main_for_seq_leave_earlystop_SegMM.py:265-300) enqueued from C -----------
  * SURVEY.md 8(b) asks for coarse entry points (embedding, encoder layer, head + loss, optimizer tail) so that a host language
  * does not pay a foreign-function call per kernel.  A PHASE is the resolved launch list of one such part of the step: an array

@@ -22,6 +22,7 @@
 #include "rowops.h"
 #include "assemble.h"
 #include "storeops.h"
+#include "srops.h"
 
 // compute units of the current device (cached; persistent kernels launch one workgroup per CU)
 static int num_cus() {
@@ -2331,6 +2332,54 @@ int segmm_pool_tokens_bwd(const float* dOut, float* dU, int Lu, float* dV, int L
     if (B <= 0) return 0;
     hipLaunchKernelGGL(pool_tokens_bwd_kernel, dim3((unsigned)(B * (Lu + Lv))), dim3(256), 0, (hipStream_t)stream, dOut, dU, Lu, dV, Lv,
                        d, bins);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- spatial-reduction attention (csrc/srops.h): window pack / unpack around the conv-as-GEMM
+static int sr_len(const char* who, int S, int r, int d, int* Ls) {
+    SEGMM_REQUIRE(r >= 2 && r <= 8, "%s: sr_ratio r=%d not built (2 <= r <= 8)", who, r);
+    SEGMM_REQUIRE(d > 0 && d % 4 == 0, "%s: d=%d not built (d %% 4 == 0: a lane moves 4 channels)", who, d);
+    const int p = (r - 1) / 2, Lc = S + 2 * p >= r ? (S + 2 * p - r) / r + 1 : 0, Lm = S / r;
+    SEGMM_REQUIRE(S > 0 && Lc == Lm && Lm >= 1, "%s: S=%d with sr_ratio r=%d gives conv length %d != mask-pool length %d (or none): "
+                  "the reference fails there too", who, S, r, Lc, Lm);
+    *Ls = Lm;
+    return 0;
+}
+
+int segmm_sr_pack(const float* x, int ldx, const uint8_t* m, float* A, uint8_t* m_sr, float* amax, int B, int S, int d, int r,
+                  segmm_stream_t stream) {
+    int Ls = 0;
+    if (int rc = sr_len("sr_pack", S, r, d, &Ls)) return rc;
+    SEGMM_REQUIRE(x && A && ldx >= d && ldx % 4 == 0 && aligned16(x) && aligned16(A) && (m_sr == nullptr || m != nullptr),
+                  "sr_pack: pointer/alignment (x, A 16-byte aligned, ldx >= d, ldx %% 4 == 0, m_sr needs m)");
+    if (B <= 0) return 0;
+    const long long items = (long long)B * Ls * (d / 4);
+    const dim3 grid((unsigned)((items + 255) / 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (r) {
+#define SR_CASE(R) case R: hipLaunchKernelGGL(sr_pack_kernel<R>, grid, block, 0, s, x, (long long)ldx, m, A, m_sr, amax, items, S, Ls, d / 4); break;
+        SR_CASE(2) SR_CASE(3) SR_CASE(4) SR_CASE(5) SR_CASE(6) SR_CASE(7) SR_CASE(8)
+#undef SR_CASE
+    }
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int segmm_sr_unpack(const float* dA, const float* res, float* G, int B, int S, int d, int r, segmm_stream_t stream) {
+    int Ls = 0;
+    if (int rc = sr_len("sr_unpack", S, r, d, &Ls)) return rc;
+    SEGMM_REQUIRE(dA && G && G != res && G != dA && aligned16(dA) && aligned16(G) && aligned16(res),
+                  "sr_unpack: pointer/alignment (dA, res, G 16-byte aligned; G is neither operand)");
+    if (B <= 0) return 0;
+    const long long items = (long long)B * (Ls + 1) * (d / 4);
+    const dim3 grid((unsigned)((items + 255) / 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (r) {
+#define SR_CASE(R) case R: hipLaunchKernelGGL(sr_unpack_kernel<R>, grid, block, 0, s, dA, res, G, items, S, Ls, d / 4); break;
+        SR_CASE(2) SR_CASE(3) SR_CASE(4) SR_CASE(5) SR_CASE(6) SR_CASE(7) SR_CASE(8)
+#undef SR_CASE
+    }
     LAUNCH_CHECK();
     return 0;
 }

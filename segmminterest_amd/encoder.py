@@ -56,10 +56,13 @@ class MLP(_FusedOnly):
 class SegFormerXAttention(_FusedOnly):
     """Parameter container of encoder.py:12-42."""
 
-    def __init__(self, d_model, num_head, sr_ratio=1, dropout=0.1, ablation_type="ours"):
+    def __init__(self, d_model, num_head, sr_ratio=1, dropout=0.1, ablation_type="ours", sr_attn=0):
         super().__init__()
-        if sr_ratio != 1:
-            raise NotImplementedError("sr_ratio > 1 is unused by the reference trainers (main...SegMM.py:94)")
+        check_sr_ratio(sr_ratio, sr_attn)
+        if sr_ratio > 1:
+            # encoder.py:23-31: the strided conv that shortens the video-key sequence; kernel_size == stride, so the engine runs it
+            # as one GEMM over packed windows (csrc/srops.h) with this weight, as stored, as the [d, r d] matrix
+            self.sr = nn.Conv1d(d_model, d_model, sr_ratio, stride=sr_ratio, padding=(sr_ratio - 1) // 2)
         self.t2v_proj = clones(nn.Linear(d_model, d_model), 3)
         self.v2v_proj = clones(nn.Linear(d_model, d_model), 3)
         self.t2t_proj = clones(nn.Linear(d_model, d_model), 3)
@@ -78,9 +81,9 @@ class SegFormerXAttention(_FusedOnly):
 class SegFormerXEncoderLayer(_FusedOnly):
     """Parameter container of encoder.py:178-187."""
 
-    def __init__(self, d_model, num_head, ff_dim, sr_ratio, dropout, ablation_type="ours"):
+    def __init__(self, d_model, num_head, ff_dim, sr_ratio, dropout, ablation_type="ours", sr_attn=0):
         super().__init__()
-        self.cross_attn = SegFormerXAttention(d_model, num_head, sr_ratio, dropout, ablation_type)
+        self.cross_attn = SegFormerXAttention(d_model, num_head, sr_ratio, dropout, ablation_type, sr_attn)
         self.ff_usr = MLP([d_model, ff_dim, d_model], activation="gelu")
         self.ff_vid = MLP([d_model, ff_dim, d_model], activation="gelu")
         self.ln_usr = nn.LayerNorm(d_model, eps=1e-12)
@@ -93,11 +96,11 @@ class SegFormerXEncoder(_FusedOnly):
     checkpoint compatibility; the reference never gives them a gradient either)."""
 
     def __init__(self, d_model_in, d_model_lvls, num_head_lvls, sr_ratio_lvls, ff_dim_lvls, use_patch_merge, dropout,
-                 ablation_type="ours"):
+                 ablation_type="ours", sr_attn=0):
         super().__init__()
         assert len(d_model_lvls) == len(num_head_lvls) == len(sr_ratio_lvls) == len(ff_dim_lvls)
         self.layers = nn.ModuleList([
-            SegFormerXEncoderLayer(d, h, ff, sr, dropout, ablation_type)
+            SegFormerXEncoderLayer(d, h, ff, sr, dropout, ablation_type, sr_attn)
             for d, h, sr, ff in zip(d_model_lvls, num_head_lvls, sr_ratio_lvls, ff_dim_lvls)])
         dims = [d_model_in] + list(d_model_lvls)
         self.pe_lns = nn.ModuleList([nn.LayerNorm(d, 1e-12) for d in d_model_lvls])
@@ -169,13 +172,29 @@ def check_ff_dim_lvls(ff_dim_lvls, n_layers):
     return ff
 
 
+def check_sr_ratio(sr_ratio, sr_attn):
+    """The ONE statement of which spatial-reduction ratios run.  Without the opt-in (``model_cfg.sr_attn = 1``) any ratio but 1 is
+    refused, as it always was; with it, 2 <= sr_ratio <= 8 builds the reference's ``cross_attn.sr`` conv (encoder.py:23-31) and runs
+    on the window-pack kernels (csrc/srops.h: one template instance per tap count)."""
+    r = int(sr_ratio)
+    if r == 1:
+        return r
+    if not sr_attn:
+        raise NotImplementedError("sr_ratio > 1 is disabled in the reference trainers (main...SegMM.py:94); model_cfg.sr_attn = 1 "
+                                  "opts in to spatial-reduction attention")
+    if not 2 <= r <= 8:
+        raise NotImplementedError("sr_ratio = %d is not built: 1, or 2 <= sr_ratio <= 8 with model_cfg.sr_attn = 1" % r)
+    return r
+
+
 class SegFormerX(nn.Module):
     """Drop-in for encoder.py:327-520.  ``forward(usr_feat, usr_mask, vid_feat, vid_mask)`` returns
     ``([vid_state[B,S,d]], usr_embedding[B,Lt,d])`` exactly like the reference with output_layers=[-1].
 
     ``ff_dim_lvls`` gives every encoder layer its own feed-forward width (``check_ff_dim_lvls``: positive multiples of 4; state
     dict keys and shapes are the reference's, so its checkpoints load unchanged).  Still refused, each with its own message:
-    ``d_model_lvls`` other than ``[d_model_in] * N``, more than one head count, ``sr_ratio > 1``, patch merging and
+    ``d_model_lvls`` other than ``[d_model_in] * N``, more than one head count, ``sr_ratio > 1`` without ``model_cfg.sr_attn = 1``
+    (with it: ratios 2 .. 8, the reference's ``cross_attn.sr`` conv, run as window pack + GEMM by the engine), patch merging and
     ``output_layers`` other than ``[-1]``.  The MLP ablations (SelfMLP, CrossMLP, w/oAtt) build no encoder layers and ignore
     ``ff_dim_lvls``, as the reference does."""
 
@@ -188,8 +207,11 @@ class SegFormerX(nn.Module):
         d = d_model_in
         if any(x != d for x in d_model_lvls):
             raise NotImplementedError("d_model_lvls must be [d_model_in] * N: one model width per backbone (main...SegMM.py:88-96)")
-        if any(sr != 1 for sr in sr_ratio_lvls):
-            raise NotImplementedError("sr_ratio > 1 is disabled in the reference trainers (main...SegMM.py:94)")
+        # opt-in: layers with sr_ratio > 1 shorten their video-key sequence with a strided conv (check_sr_ratio; engine.py)
+        self.sr_attn = int(getattr(model_cfg, "sr_attn", 0) or 0)
+        for sr in sr_ratio_lvls:
+            check_sr_ratio(sr, self.sr_attn)
+        self.sr_ratio_lvls = [int(sr) for sr in sr_ratio_lvls]
         if any(use_patch_merge):
             raise NotImplementedError("patch merging is disabled in the reference trainers (main...SegMM.py:94)")
         if len(set(num_head_lvls)) != 1:
@@ -227,7 +249,7 @@ class SegFormerX(nn.Module):
         else:
             self.encoder = SegFormerXEncoder(d, lvls, list(num_head_lvls), list(sr_ratio_lvls),
                                              check_ff_dim_lvls(ff_dim_lvls, len(lvls)), list(use_patch_merge), dropout,
-                                             self.ablation_type)
+                                             self.ablation_type, self.sr_attn)
         self.output_layers = list(range(len(sr_ratio_lvls))) if output_layers is None else list(output_layers)
         if self.output_layers != [-1]:
             raise NotImplementedError("output_layers must be [-1] as in the reference trainers (main...SegMM.py:95)")

@@ -73,6 +73,25 @@ def layer_plan(mode: str, full: bool) -> Tuple[List[str], List[str]]:
     return vid, usr
 
 
+def layer_sr(bb, i: int, vidP: List[str]) -> int:
+    """Spatial-reduction ratio IN FORCE at layer ``i`` whose live video-token projections are ``vidP``: the layer's
+    ``sr_ratio_lvls`` entry when some live key / value projection reads video tokens (xxx_proj.1 / .2), else 1 -- a layer that
+    projects no video keys (the last live layer under 'CrossAtt') never runs its ``sr`` conv: the reference leaves it without a
+    gradient, here it is dead."""
+    lv = getattr(bb, "sr_ratio_lvls", None)
+    r = int(lv[i]) if lv is not None and i < len(lv) else 1
+    return r if r > 1 and any(not n.endswith(".0") for n in vidP) else 1
+
+
+def split_vid_plan(vidP: List[str]) -> Tuple[List[str], List[str]]:
+    """(query projections, key / value projections) of a reduced layer's video-token plan: the queries read the layer input at full
+    resolution, the keys and values read the reduced sequence -- two fused GEMMs, two adjacent groups.  ``layer_plan`` lists the
+    queries first."""
+    nq = sum(1 for n in vidP if n.endswith(".0"))
+    assert all(n.endswith(".0") for n in vidP[:nq]) and not any(n.endswith(".0") for n in vidP[nq:])
+    return vidP[:nq], vidP[nq:]
+
+
 def mlp_linears(bb) -> List[str]:
     """Names (relative to the backbone) of the Linears of the ablation ``encoder_mlp`` in forward order; the last one is the
     output Linear, the others are followed by ReLU (+ Dropout when dropout > 0) -- encoder.py:210-252."""
@@ -104,7 +123,13 @@ def backbone_layout(prefix: str, bb) -> Tuple[List[Tuple[str, List[List[str]]]],
             singles = [ca + "ff_vid", ca + "ln_vid", L + "ff_vid.layers.0", L + "ff_vid.layers.1", L + "ln_vid"]
             if full:
                 singles += [ca + "ff_usr", ca + "ln_usr", L + "ff_usr.layers.0", L + "ff_usr.layers.1", L + "ln_usr"]
-            groups = [[ca + n + ".weight" for n in vidP], [ca + n + ".bias" for n in vidP]]
+            if layer_sr(bb, i, vidP) > 1:          # reduced layer: queries read Xv, keys / values read Xsr; the conv is live
+                groups = []
+                for part in split_vid_plan(vidP):
+                    groups += [[ca + n + ".weight" for n in part], [ca + n + ".bias" for n in part]]
+                singles = [ca + "sr"] + singles
+            else:
+                groups = [[ca + n + ".weight" for n in vidP], [ca + n + ".bias" for n in vidP]]
             if usrP:
                 groups += [[ca + n + ".weight" for n in usrP], [ca + n + ".bias" for n in usrP]]
             for s in singles:
@@ -575,8 +600,8 @@ class ParamStore:
             for grp in groups:
                 n0 = grp[0]
                 if n0.endswith(".weight") and (".encoder.layers." in "." + n0 or ".encoder_mlp.mlp." in "." + n0) \
-                        and params[n0].dim() == 2 and "ln_" not in n0:
-                    self._transposes.append((self.index[n0][0], sum(params[n].shape[0] for n in grp), params[n0].shape[1]))
+                        and _gemm_cols(n0, params[n0]) and "ln_" not in n0:
+                    self._transposes.append((self.index[n0][0], sum(params[n].shape[0] for n in grp), _gemm_cols(n0, params[n0])))
         # flat ranges read by GEMMs as the weight operand: the encoder-layer buckets and the input
         # projections when they are Linears (image mode); Embedding tables, positional tables and the head are not
         ranges = [(s0, e0 - s0) for bname, s0, e0 in buckets
@@ -607,13 +632,13 @@ class ParamStore:
         for bname, groups in self._layout():
             for grp in groups:
                 n0 = grp[0]
-                if not n0.endswith(".weight") or params[n0].dim() != 2 or "ln_" in n0 or "_pe." in n0 or bname == "head":
+                if not n0.endswith(".weight") or not _gemm_cols(n0, params[n0]) or "ln_" in n0 or "_pe." in n0 or bname == "head":
                     continue
                 in_layer = ".encoder.layers." in "." + n0 or ".encoder_mlp.mlp." in "." + n0
                 is_lin = isinstance(mods.get(n0.rsplit(".", 1)[0]), torch.nn.Linear)
                 if not (in_layer or (is_lin and (n0.endswith("vid_proj.weight") or n0.endswith("usr_proj.weight")))):
                     continue
-                R, Cc = sum(params[n].shape[0] for n in grp), params[n0].shape[1]
+                R, Cc = sum(params[n].shape[0] for n in grp), _gemm_cols(n0, params[n0])
                 o = self.index[n0][0]
                 tr = o in tr_offs
                 if Cc % 32 == 0 and (not tr or R % 32 == 0):
@@ -650,6 +675,16 @@ class ParamStore:
         if t is None:
             t = self.scratch[k] = torch.empty(shape, dtype=dtype, device=self.flat.device)
         return t
+
+
+def _gemm_cols(name: str, p) -> int:
+    """Columns of parameter ``name`` as a GEMM's weight matrix, 0 when it is none: a 2-D weight as it is, and the reducing conv
+    ``cross_attn.sr.weight`` [d, d, r] as the row-major [d, d r] matrix it is stored as (K index c r + t: csrc/srops.h)."""
+    if p.dim() == 2:
+        return int(p.shape[1])
+    if p.dim() == 3 and name.endswith("cross_attn.sr.weight"):
+        return int(p.shape[1] * p.shape[2])
+    return 0
 
 
 def _empty(ref, *shape, dtype=torch.float32):
@@ -1029,6 +1064,20 @@ class BackboneRun:
             H.absmax(t, rows, cols, cols, out=a.slots)
         return finish_act(st, a)
 
+    # ---------------------------------------------------------------- spatial reduction (sr_ratio > 1), per layer
+    def _layer_r(self, i):
+        """The spatial-reduction ratio in force at layer ``i`` (``layer_sr``): 1 unless the model opted in and the layer projects video keys."""
+        full = i < self.N - 2 and self.mode != "self"
+        return layer_sr(self.__dict__.get("bb"), i, layer_plan(self.mode, full)[0])
+
+    def _layer_keys(self, i, S):
+        """Video keys of layer ``i``: S, or the reduced length Ls (``hipabi.sr_len`` refuses an (S, r) the reference fails on, by name)."""
+        r = self._layer_r(i)
+        return S if r == 1 else H.sr_len(S, r)
+
+    def _any_reduced(self):
+        return any(self._layer_r(i) > 1 for i in range(max(self.N - 1, 0)))
+
     # ---------------------------------------------------------------- forward
     def _require_attn_keys(self, S, Lt):
         """The held attention kernels keep the keys of both blocks, each padded to a multiple of 16, in at most 12 tiles.  Checked
@@ -1038,14 +1087,17 @@ class BackboneRun:
         if self.abl in MLP_VARIANTS or self.N < 2:
             return
         pad16 = lambda n: (n + 15) & ~15
+        keys_v = [self._layer_keys(i, S) for i in range(self.N - 1)]          # (a reduced layer's keys; refuses conv length != pool length)
         if self.__dict__.get("attn_stream", 0):          # (read this way: the check also serves an object that was never initialised)
             if pad16(S) > 256 or pad16(Lt) > 256:
                 raise RuntimeError("attn: S=%d video segments / Lt=%d user tokens not built: the streamed attention kernels take at "
                                    "most 256 of each" % (S, Lt))
             return
-        calls = [(0 if self.mode == "cross" else S, 0 if self.mode == "self" else Lt)]
-        if self.N >= 3 and self.mode != "self":
-            calls.append((S, 0 if self.mode == "cross" else Lt))
+        calls = []
+        for i, Lv in enumerate(keys_v):          # video queries of every live layer; user queries of the full layers 0 .. N-3
+            calls.append((0 if self.mode == "cross" else Lv, 0 if self.mode == "self" else Lt))
+            if i < self.N - 2 and self.mode != "self":
+                calls.append((Lv, 0 if self.mode == "cross" else Lt))
         keys = max(pad16(La) + pad16(Lb) for La, Lb in calls)
         if keys > 192:
             raise RuntimeError("attn: S=%d video segments and Lt=%d user tokens make %d padded keys > 192 not built "
@@ -1090,7 +1142,8 @@ class BackboneRun:
         self.vm, self.um = vm, um
         sv = self.sv
         ref = vm
-        am = self.am = AmaxArena(st, 8 + 14 * max(self.N - 1, 0) + 2 * (self.n_mlp + 1))
+        n_red = sum(1 for i in range(max(self.N - 1, 0)) if self._layer_r(i) > 1) if self.abl not in MLP_VARIANTS else 0
+        am = self.am = AmaxArena(st, 8 + 14 * max(self.N - 1, 0) + 2 * (self.n_mlp + 1) + 2 * n_red)          # (+ packed windows, Xsr)
         layered = self.abl not in MLP_VARIANTS and self.N >= 2
         use_pe = bool(getattr(bb, "use_pe", 1))          # --use_pe 0: no positional-embedding add (encoder.py:450-471)
         usr_is_operand = (layered and self.mode != "self") or self.abl == "CrossMLP"      # does any GEMM read the user embedding?
@@ -1279,30 +1332,43 @@ class BackboneRun:
         finish_act(st, produced(X2))
         return X2, dict(A=A, R1=R1, X1=X1, m1=m1, r1=r1, G=G, Hh=Hh, R2=R2, m2=m2, r2=r2)
 
-    def _attn_views(self, full, Yv, Yu, nv, nu):
+    def _attn_views(self, full, Yv, Yu, nv, nu, sr=None):
         """Column slices of the fused projection buffers (or of their gradients) as the attention kernels take them:
-        for the video queries and, when the layer is full, for the user queries.  An empty key block is (None, ..., 0)."""
+        for the video queries and, when the layer is full, for the user queries.  An empty key block is (None, ..., 0).
+        ``sr`` = (Ykv, Ls) on a reduced layer: ``Yv`` then holds the video-token QUERY projections alone, ``Ykv`` ([B Ls, .]) the key /
+        value projections of the reduced sequence, and the video key block has Ls keys."""
         d, S, Lt, mode = self.d, self.S, self.Lt, self.mode
         vidP, usrP = layer_plan(mode, full)
-        cv = {n: (Yv, k * d) for k, n in enumerate(vidP)}
+        if sr is None:
+            cv = {n: (Yv, k * d) for k, n in enumerate(vidP)}
+            ldv = ldkv = nv * d
+            Lv = S
+        else:
+            qP, kvP = split_vid_plan(vidP)
+            cv = {n: (Yv, k * d) for k, n in enumerate(qP)}
+            cv.update({n: (sr[0], k * d) for k, n in enumerate(kvP)})
+            ldv, ldkv, Lv = len(qP) * d, len(kvP) * d, sr[1]
         cu = {n: (Yu, k * d) for k, n in enumerate(usrP)}
-        ldv, ldu = nv * d, max(nu, 1) * d
+        ldu = max(nu, 1) * d
         g = lambda c, n: c.get(n)
-        vq = dict(Qa=g(cv, "v2v_proj.0"), Qb=g(cv, "t2v_proj.0"), ldq=ldv, Ka=g(cv, "v2v_proj.1"), Va=g(cv, "v2v_proj.2"), ldka=ldv,
-                  Kb=g(cu, "t2v_proj.1"), Vb=g(cu, "t2v_proj.2"), ldkb=ldu, La=0 if mode == "cross" else S, Lb=0 if mode == "self" else Lt)
+        vq = dict(Qa=g(cv, "v2v_proj.0"), Qb=g(cv, "t2v_proj.0"), ldq=ldv, Ka=g(cv, "v2v_proj.1"), Va=g(cv, "v2v_proj.2"), ldka=ldkv,
+                  Kb=g(cu, "t2v_proj.1"), Vb=g(cu, "t2v_proj.2"), ldkb=ldu, La=0 if mode == "cross" else Lv, Lb=0 if mode == "self" else Lt)
         uq = None
         if full:
-            uq = dict(Qa=g(cu, "v2t_proj.0"), Qb=g(cu, "t2t_proj.0"), ldq=ldu, Ka=g(cv, "v2t_proj.1"), Va=g(cv, "v2t_proj.2"), ldka=ldv,
-                      Kb=g(cu, "t2t_proj.1"), Vb=g(cu, "t2t_proj.2"), ldkb=ldu, La=S, Lb=0 if mode == "cross" else Lt)
+            uq = dict(Qa=g(cu, "v2t_proj.0"), Qb=g(cu, "t2t_proj.0"), ldq=ldu, Ka=g(cv, "v2t_proj.1"), Va=g(cv, "v2t_proj.2"), ldka=ldkv,
+                      Kb=g(cu, "t2t_proj.1"), Vb=g(cu, "t2t_proj.2"), ldkb=ldu, La=Lv, Lb=0 if mode == "cross" else Lt)
         return vq, uq
 
     def _attn_calls(self):
         """(Lq, La, Lb) of every attention call a pass of this backbone makes (video queries of every live layer; user queries
         of the full layers) -- what ``attn_fwd_pl_takes`` / the planes-in backward of ``capi.hip`` are asked with."""
         S, Lt, mode = self.S, self.Lt, self.mode
-        calls = [(S, 0 if mode == "cross" else S, 0 if mode == "self" else Lt)]
-        if self.N >= 3 and mode != "self":          # layers 0 .. N-3 are full: the user tokens query too
-            calls.append((Lt, S, 0 if mode == "cross" else Lt))
+        calls = []
+        for i in range(max(self.N - 1, 0)):
+            Lv = self._layer_keys(i, S)          # (S, or Ls on a reduced layer)
+            calls.append((S, 0 if mode == "cross" else Lv, 0 if mode == "self" else Lt))
+            if i < self.N - 2 and mode != "self":          # layers 0 .. N-3 are full: the user tokens query too
+                calls.append((Lt, Lv, 0 if mode == "cross" else Lt))
         return calls
 
     def _attn_planes_in(self):
@@ -1315,6 +1381,8 @@ class BackboneRun:
         if not (self.delayed and st.engine_p and st.attn_pl and self.dh % 16 == 0 and self.dh <= 48 and self.d % 32 == 0):
             return False
         if H.knob("ATT_FWD_PL") == 0:
+            return False
+        if self._any_reduced():          # a pass with a reduced layer keeps the fp32 projection buffers (README "Open")
             return False
         return all(Lq <= 112 and La + Lb <= 192 and La % 4 == 0 and Lb % 4 == 0 and not _attn_streamed(La, Lb)
                    for (Lq, La, Lb) in self._attn_calls())
@@ -1361,11 +1429,33 @@ class BackboneRun:
         nv, nu = len(vidP), len(usrP)
         L = "%sencoder.layers.%d." % (P, i)
         ca = L + "cross_attn."
-        Yv_a = self._proj_act(i, "Yv", Mv, nv * d)
-        _lin_fwd(st, Mv, nv * d, d, Xv, ca + vidP[0] + ".weight", Yv_a.t, nv * d, bias=st.p(ca + vidP[0] + ".bias"),
-                 c_act=Yv_a if Yv_a.planes is not None else None)
-        if Yv_a.po is None:
-            Yv_a.planes = None
+        r = self._layer_r(i)
+        sr = srec = None
+        kmask = self.vm          # mask of the video key block
+        if r > 1:
+            # reduced layer (encoder.py:84-102): Xsr = conv(Xv) as pack + one GEMM over the windows; the queries read Xv, the keys and
+            # values Xsr; fp32 projection buffers, as a streamed layer has them
+            Ls = H.sr_len(S, r)
+            Ms = B * Ls
+            qP, kvP = split_vid_plan(vidP)
+            Apk = new_act(st, am, Ms, r * d)
+            kmask = torch.empty((B, Ls), dtype=torch.uint8, device=st.flat.device)
+            H.sr_pack(Xv.t, d, self.vm, Apk.t, kmask, Apk.slots, B, S, d, r)
+            finish_act(st, Apk)
+            Xsr = new_act(st, am, Ms, d, site="%sL%d.Xsr" % (P, i), delayed=self.delayed)
+            _lin_fwd(st, Ms, d, r * d, Apk, ca + "sr.weight", Xsr.t, d, bias=st.p(ca + "sr.bias"), c_act=Xsr)
+            finish_act(st, Xsr)
+            Yq, Ykv = _empty(Xv.t, Mv, len(qP) * d), _empty(Xv.t, Ms, len(kvP) * d)
+            _lin_fwd(st, Mv, len(qP) * d, d, Xv, ca + qP[0] + ".weight", Yq, len(qP) * d, bias=st.p(ca + qP[0] + ".bias"))
+            _lin_fwd(st, Ms, len(kvP) * d, d, Xsr, ca + kvP[0] + ".weight", Ykv, len(kvP) * d, bias=st.p(ca + kvP[0] + ".bias"))
+            Yv_a = Act(Yq, None, Mv, len(qP) * d)
+            sr, srec = (Ykv, Ls), dict(r=r, Ls=Ls, Apk=Apk, Xsr=Xsr, Ykv=Ykv, kmask=kmask)
+        else:
+            Yv_a = self._proj_act(i, "Yv", Mv, nv * d)
+            _lin_fwd(st, Mv, nv * d, d, Xv, ca + vidP[0] + ".weight", Yv_a.t, nv * d, bias=st.p(ca + vidP[0] + ".bias"),
+                     c_act=Yv_a if Yv_a.planes is not None else None)
+            if Yv_a.po is None:
+                Yv_a.planes = None
         Yu_a = None
         if Yu_ready is not None:      # computed on the side stream together with the user embedding (forward())
             Yu_a = Yu_ready
@@ -1374,7 +1464,7 @@ class BackboneRun:
             Yu_a = self._proj_act(i, "Yu", Mu, nu * d)
             self._usr_proj_fwd(i, Xu, Yu_a)
         Yv, Yu = Yv_a.t, (Yu_a.t if Yu_a is not None else None)
-        vq, uq = self._attn_views(full, Yv, Yu, nv, nu)
+        vq, uq = self._attn_views(full, Yv, Yu, nv, nu, sr=sr)
         # input planes of the attention forward: the producer GEMMs wrote them (delayed scales); the kernel judges the site headers
         # itself and stages an unusable site from the fp32 views
         pl_v = (Yv_a.planes, Yv_a.hdr, 2 * nv * d) if Yv_a.po is not None else None
@@ -1386,7 +1476,7 @@ class BackboneRun:
             pin_u = dict(q=pl_u, a=pl_v, b=pl_u if uq["Lb"] else None)
         lse_v = _empty(Xv.t, 2, B, Hh, S)
         Av = new_act(st, am, Mv, d, site="%sL%d.vid.A" % (P, i), delayed=self.delayed)
-        rec = dict(full=full, Xv=Xv, Xu=Xu, Yv=Yv, Yu=Yu, lse_v=lse_v, pin_v=pin_v, pin_u=pin_u)
+        rec = dict(full=full, Xv=Xv, Xu=Xu, Yv=Yv, Yu=Yu, lse_v=lse_v, pin_v=pin_v, pin_u=pin_u, sr=srec)
         if (Yv is None or (nu and Yu is None)) and (pin_v is None or (full and pin_u is None)):
             raise RuntimeError("planes-only projection outputs without input planes for every attention call of the layer")
         X2u = None
@@ -1398,7 +1488,7 @@ class BackboneRun:
 
             def usr_chain():
                 H.attn_fwd(B, Hh, dh, Lt, uq["La"], uq["Lb"], uq["Qa"], uq["Qb"], uq["ldq"], uq["Ka"], uq["Va"], uq["ldka"], uq["Kb"],
-                           uq["Vb"], uq["ldkb"], self.um, self.vm, self.um, Au.t, d, lse_u, drop_p=self.p_drop,
+                           uq["Vb"], uq["ldkb"], self.um, kmask, self.um, Au.t, d, lse_u, drop_p=self.p_drop,
                            seed=self.seed, site=_site(self.bi, i, K_ATT_U), amax_o=Au.slots, po=Au.po, pin=pin_u)
                 finish_act(st, produced(Au))
                 return self._side_post(i, L, "usr", Xu, Au, Mu, (K_AO_U, K_MI_U, K_MO_U), out_is_operand=True, bufs=bufs_u)
@@ -1406,7 +1496,7 @@ class BackboneRun:
                 with side_work(st):          # (both fused projections are enqueued on the main stream: the fork orders the chain behind them)
                     X2u, sv_u = usr_chain()
         H.attn_fwd(B, Hh, dh, S, vq["La"], vq["Lb"], vq["Qa"], vq["Qb"], vq["ldq"], vq["Ka"], vq["Va"], vq["ldka"], vq["Kb"], vq["Vb"],
-                   vq["ldkb"], self.vm, self.vm, self.um, Av.t, d, lse_v, drop_p=self.p_drop, seed=self.seed,
+                   vq["ldkb"], self.vm, kmask, self.um, Av.t, d, lse_v, drop_p=self.p_drop, seed=self.seed,
                    site=_site(self.bi, i, K_ATT_V), amax_o=Av.slots, po=Av.po, pin=pin_v)
         finish_act(st, produced(Av))
         hd = self.__dict__.get("_head_dot") if i == self.N - 2 else None          # last live layer: its video-side output IS the backbone's
@@ -1475,13 +1565,22 @@ class BackboneRun:
         L = "%sencoder.layers.%d." % (P, i)
         ca = L + "cross_attn."
         Yv, Yu = rec["Yv"], rec["Yu"]
+        srec = rec.get("sr")          # reduced layer: dYv holds the query projections' gradients, dYkv ([B Ls, .]) the keys' and values'
+        kmask = self.vm if srec is None else srec["kmask"]
         # one site per fused dY buffer: both attentions fold into it; the fused backward kernel writes its planes itself
-        dYv = new_act(st, self.amb, Mv, nv * d, key="dYv%d" % i, site="%sdYv%d" % (P, i), delayed=self.delayed)
+        if srec is None:
+            dYv = new_act(st, self.amb, Mv, nv * d, key="dYv%d" % i, site="%sdYv%d" % (P, i), delayed=self.delayed)
+            dYkv = dYv
+        else:
+            qP, kvP = split_vid_plan(vidP)
+            nq, nkv, Ms = len(qP), len(kvP), B * srec["Ls"]
+            dYv = new_act(st, self.amb, Mv, nq * d, key="dYq%d" % i, site="%sdYq%d" % (P, i), delayed=self.delayed)
+            dYkv = new_act(st, self.amb, Ms, nkv * d, key="dYkv%d" % i, site="%sdYkv%d" % (P, i), delayed=self.delayed)
         dYu = new_act(st, self.amb, Mu, nu * d, key="dYu%d" % i, site="%sdYu%d" % (P, i), delayed=self.delayed) if nu else None
-        vq, uq = self._attn_views(full, Yv, Yu, nv, nu)
-        dvq, duq = self._attn_views(full, dYv.t, dYu.t if nu else None, nv, nu)
+        vq, uq = self._attn_views(full, Yv, Yu, nv, nu, sr=None if srec is None else (srec["Ykv"], srec["Ls"]))
+        dvq, duq = self._attn_views(full, dYv.t, dYu.t if nu else None, nv, nu, sr=None if srec is None else (dYkv.t, srec["Ls"]))
         Dv = st.buf("attnD", (B * Hh * max(S, Lt),))
-        sl_v, sl_u = dYv.slots, (dYu.slots if nu else None)
+        sl_v, sl_u, sl_kv = dYv.slots, (dYu.slots if nu else None), dYkv.slots
 
         # planes only: dQ / dK / dV are read by the projection GEMMs alone, as planes; their fp32 copies only ever fed the consumers'
         # overflow fallback (0.57 GB of stores per step at config 2).  Without them, a REPAIR pass of the same launches follows
@@ -1495,7 +1594,7 @@ class BackboneRun:
         # and the planes-only / repair protocol for both; the dY planes then come from the split pass of finish_act.
         st_v = _attn_streamed(vq["La"], vq["Lb"])
         st_u = full and _attn_streamed(uq["La"], uq["Lb"])
-        streamed = st_v or st_u
+        streamed = st_v or st_u or srec is not None          # (a reduced layer runs like a streamed one: fp32 views, planes from the split pass)
         ponly = ponly and not streamed
 
         def planes_of(dq, dka_, dkb_, views, pflags=0):
@@ -1529,10 +1628,10 @@ class BackboneRun:
 
                 def attn_u_(pflags):
                     H.attn_bwd(B, Hh, dh, Lt, uq["La"], uq["Lb"], uq["Qa"], uq["Qb"], uq["ldq"], uq["Ka"], uq["Va"], uq["ldka"], uq["Kb"],
-                               uq["Vb"], uq["ldkb"], self.um, self.vm, self.um, rec["lse_u"], rec["u"]["A"].t, d, dAu, d, Dv_u,
+                               uq["Vb"], uq["ldkb"], self.um, kmask, self.um, rec["lse_u"], rec["u"]["A"].t, d, dAu, d, Dv_u,
                                duq["Qa"], duq["Qb"], duq["ldq"], duq["Ka"], duq["Va"], duq["ldka"], duq["Kb"], duq["Vb"], duq["ldkb"],
                                drop_p=self.p_drop, seed=self.seed, site=_site(self.bi, i, K_ATT_U),
-                               amax_q=sl_u, amax_ka=sl_v, amax_kb=sl_u, phase=0 if st_u else 4, planes=planes_of(dYu, dYv, dYu, duq, pflags), pin=rec.get("pin_u"))
+                               amax_q=sl_u, amax_ka=sl_kv, amax_kb=sl_u, phase=0 if st_u else 4, planes=planes_of(dYu, dYv, dYu, duq, pflags), pin=rec.get("pin_u"))
                 attn_u_(H.ATTN_PLANES_ONLY if ponly else 0)
                 return dR1u_, attn_u_
             if usr_on_side:
@@ -1545,9 +1644,9 @@ class BackboneRun:
         flush_deferred(st, deferred)          # the three weight-gradient GEMMs of this side run under the attention backward
         def attn_v(pflags):
             H.attn_bwd(B, Hh, dh, S, vq["La"], vq["Lb"], vq["Qa"], vq["Qb"], vq["ldq"], vq["Ka"], vq["Va"], vq["ldka"], vq["Kb"], vq["Vb"],
-                       vq["ldkb"], self.vm, self.vm, self.um, rec["lse_v"], rec["v"]["A"].t, d, dAv, d, Dv, dvq["Qa"], dvq["Qb"], dvq["ldq"],
+                       vq["ldkb"], self.vm, kmask, self.um, rec["lse_v"], rec["v"]["A"].t, d, dAv, d, Dv, dvq["Qa"], dvq["Qb"], dvq["ldq"],
                        dvq["Ka"], dvq["Va"], dvq["ldka"], dvq["Kb"], dvq["Vb"], dvq["ldkb"], drop_p=self.p_drop, seed=self.seed,
-                       site=_site(self.bi, i, K_ATT_V), amax_q=sl_v, amax_ka=sl_v, amax_kb=sl_u, phase=0 if st_v else 4,
+                       site=_site(self.bi, i, K_ATT_V), amax_q=sl_v, amax_ka=sl_kv, amax_kb=sl_u, phase=0 if st_v else 4,
                        planes=planes_of(dYv, dYv, dYu, dvq, pflags), pin=rec.get("pin_v"))
         attn_v(H.ATTN_PLANES_ONLY if ponly else 0)
         if full:
@@ -1571,6 +1670,10 @@ class BackboneRun:
         finish_act(st, dYv)
         if nu:
             finish_act(st, dYu)
+        if srec is not None:
+            finish_act(st, dYkv)
+            dR1v = self._sr_bwd(i, srec, dYkv, dR1v, gbuf)          # the residual gradient + what the keys and values send back through the conv
+            nv, vidP = nq, qP          # (what is left of the video-token group: the query projections, reading Xv)
         # fused projection weights / inputs
         with side_work(st):
             _wgrad(st, dYv, 0, rec["Xv"], 0, Mv, nv * d, d, _group_view(st, ca + vidP[0] + ".weight", nv * d * d, gbuf),
@@ -1588,6 +1691,32 @@ class BackboneRun:
             else:
                 _lin_dgrad(st, Mu, d, nu * d, dYu, ca + usrP[0] + ".weight", dXu_in)
         return dXv_in, dXu_in
+
+    def _sr_bwd(self, i, srec, dYkv, dR1v, gbuf):
+        """Backward of a reduced layer's key path: dXsr = dYkv . Wkv, dA = dXsr . W2, and the window unpack that adds dA to the
+        residual gradient ``dR1v`` -- returns that sum [B S, d], the ``residual=`` operand of the query projections' input-gradient
+        GEMM.  Weight gradients (Wkv against Xsr, W2 against the packed windows kept by the forward; biases as column sums) on the
+        side stream."""
+        st, d, P, B, S = self.store, self.d, self.pre, self.B, self.S
+        r, Ls = srec["r"], srec["Ls"]
+        Ms = B * Ls
+        ca = "%sencoder.layers.%d.cross_attn." % (P, i)
+        full = i < self.N - 2 and self.mode != "self"
+        kvP = split_vid_plan(layer_plan(self.mode, full)[0])[1]
+        nkv = len(kvP)
+        with side_work(st):
+            _wgrad(st, dYkv, 0, srec["Xsr"], 0, Ms, nkv * d, d, _group_view(st, ca + kvP[0] + ".weight", nkv * d * d, gbuf),
+                   gb=_group_view(st, ca + kvP[0] + ".bias", nkv * d, gbuf))
+        dXsr = new_act(st, self.amb, Ms, d, key="dXsr%d" % i, site="%sdXsr%d" % (P, i), delayed=self.delayed)
+        _lin_dgrad(st, Ms, d, nkv * d, dYkv, ca + kvP[0] + ".weight", dXsr.t, c_act=dXsr)
+        finish_act(st, dXsr)
+        with side_work(st):
+            _wgrad(st, dXsr, 0, srec["Apk"], 0, Ms, d, r * d, st.g(ca + "sr.weight", gbuf).view(d, r * d), gb=st.g(ca + "sr.bias", gbuf))
+        dA = st.buf("dApk%d" % i, (Ms, r * d))
+        _lin_dgrad(st, Ms, r * d, d, dXsr, ca + "sr.weight", dA)
+        G = st.buf("dXv_sr%d" % i, (B * S, d))
+        H.sr_unpack(dA, dR1v, G, B, S, d, r)
+        return G
 
     def backward(self, d_vid_out: torch.Tensor, gbuf: Optional[torch.Tensor] = None, on_bucket=None):
         """Fills the gradients of every live parameter of this backbone (views of ``gbuf``/store.gflat).
@@ -1612,7 +1741,8 @@ class BackboneRun:
             st.defer_wgrad = S > 32 and st.engine_p
         if st.ln_side_forced is None:
             st.ln_side = S > 32 and st.engine_p
-        self.amb = AmaxArena(st, 4 + 8 * max(self.N - 1, 0) + 2 * (self.n_mlp + 2))
+        n_red = sum(1 for i in range(max(self.N - 1, 0)) if self._layer_r(i) > 1) if self.abl not in MLP_VARIANTS else 0
+        self.amb = AmaxArena(st, 4 + 8 * max(self.N - 1, 0) + 2 * (self.n_mlp + 2) + 2 * n_red)          # (+ dYkv, dXsr)
         if self.abl in MLP_VARIANTS:
             if self.abl == "CrossMLP":
                 dZu, dZv = st.buf("pool_du", (Mu, d)), st.buf("pool_dv", (Mv, d))

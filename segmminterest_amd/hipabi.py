@@ -1709,6 +1709,33 @@ def pool_tokens_bwd(dOut, dU, Lu, dV, Lv, B, d, bins):
     _check(lib().segmm_pool_tokens_bwd(_ptr(dOut), _ptr(dU), Lu, _ptr(dV), Lv, B, d, bins, _stream()), "segmm_pool_tokens_bwd")
 
 
+def sr_len(S, r):
+    """Reduced key length of ``S`` video segments under sr_ratio ``r`` (encoder.py:23-31,84-102): the conv length
+    (S + 2p - r) // r + 1, p = (r - 1) // 2, must equal the mask-pool length S // r and be >= 1 -- the reference raises where they
+    differ; refused here, by name."""
+    S, r = int(S), int(r)
+    if not 2 <= r <= 8:
+        raise NotImplementedError("sr_ratio = %d is not built (1, or 2 <= sr_ratio <= 8)" % r)
+    p = (r - 1) // 2
+    Lc, Lm = ((S + 2 * p - r) // r + 1 if S + 2 * p >= r else 0), S // r
+    if Lc != Lm or Lm < 1:
+        raise RuntimeError("S=%d video segments with sr_ratio=%d: the reducing conv gives %d keys and the mask pool %d (the reference "
+                           "fails there too; r = 4 and 8 need S %% r in {0, 1})" % (S, r, Lc, Lm))
+    return Lm
+
+
+def sr_pack(x, ldx, m, A, m_sr, amax, B, S, d, r):
+    """A[b Ls + j, c r + t] = x[b, j r - p + t, c] (0 outside the sequence) + partial maxima of |A| + pooled mask m_sr (csrc/srops.h)."""
+    _dev(x, A)
+    _check(lib().segmm_sr_pack(_ptr(x), ldx, _ptr(m), _ptr(A), _ptr(m_sr), _ptr(amax), B, S, d, r, _stream()), "segmm_sr_pack")
+
+
+def sr_unpack(dA, res, G, B, S, d, r):
+    """G[b, i, c] = res[b, i, c] + dA[b Ls + (i + p) // r, c r + (i + p) % r] (rows in no window: res, or 0); ``res`` may be None."""
+    _dev(dA, G)
+    _check(lib().segmm_sr_unpack(_ptr(dA), _ptr(res), _ptr(G), B, S, d, r, _stream()), "segmm_sr_unpack")
+
+
 def colsum3(Xs, ld, M, N, outs, ws):
     """Column sums of up to three same-shaped [M, N] matrices in one launch pair; ws: 3 * colsum_chunks(M) * N floats."""
     X = list(Xs) + [None] * (3 - len(Xs))

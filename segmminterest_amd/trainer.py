@@ -44,13 +44,16 @@ from .optim import (GROUP_KEYS, FusedAdamW, LRSchedule, PlateauLR, WeightEMA, gr
 
 # ------------------------------------------------------------------------------------------------ model factory
 def init_model(args, reader=None, n_users: Optional[int] = None, n_items: Optional[int] = None,
-               input_dim: int = 1024, max_vid_len: int = 40, max_usr_len: int = 100, ff_dim=None):
+               input_dim: int = 1024, max_vid_len: int = 40, max_usr_len: int = 100, ff_dim=None, sr_ratio=None):
     """init_model(args, reader) of the reference trainer (main_for_seq_leave_earlystop_SegMM.py:60-130).
     ``reader`` only needs ``n_users`` / ``n_items``; feature width and lengths default to the
     reference's hard-coded 1024 / 40 / 100 and are overridable for synthetic configs.
     ``ff_dim``: the encoder layers' feed-forward width, an int (every layer) or a list of ``num_layers_enc`` ints.  ``None`` is
     the reference's behaviour: ``[d_model] * N`` whatever ``args.ff_dim`` says (main...SegMM.py:91 never reads that option, whose
-    default is 512 for every d_model: honouring it implicitly would change existing runs)."""
+    default is 512 for every d_model: honouring it implicitly would change existing runs).
+    ``sr_ratio``: the encoder layers' spatial-reduction ratio, an int (every layer) or a list of ``num_layers_enc`` ints; ``None`` is
+    the reference trainers' ``[1] * N`` (main...SegMM.py:94).  A ratio above 1 needs ``args.sr_attn = 1`` (encoder.check_sr_ratio);
+    the MLP ablations build no encoder and ignore it."""
     n_users = reader.n_users if reader is not None else n_users
     n_items = reader.n_items if reader is not None else n_items
     N, d, h = args.num_layers_enc, args.d_model, args.nhead
@@ -62,11 +65,19 @@ def init_model(args, reader=None, n_users: Optional[int] = None, n_items: Option
         ff = [int(f) for f in ff_dim]
         if len(ff) != N:
             raise ValueError("ff_dim lists %d widths for num_layers_enc = %d" % (len(ff), N))
+    if sr_ratio is None or getattr(args, "ablation_type", "ours") in E.MLP_VARIANTS:
+        sr = [1] * N
+    elif isinstance(sr_ratio, int):
+        sr = [sr_ratio] * N
+    else:
+        sr = [int(r) for r in sr_ratio]
+        if len(sr) != N:
+            raise ValueError("sr_ratio lists %d ratios for num_layers_enc = %d" % (len(sr), N))
 
     def backbone(user_id_max, video_id_max, usr_len):
         return SegFormerX(d_model_in=d, d_model_lvls=[d] * N, num_head_lvls=[h] * N, ff_dim_lvls=ff,
                           input_vid_dim=input_dim, input_usr_dim=input_dim, max_vid_len=max_vid_len, max_usr_len=usr_len,
-                          sr_ratio_lvls=[1] * N, use_patch_merge=[False] * N, output_layers=[-1], model_cfg=args,
+                          sr_ratio_lvls=sr, use_patch_merge=[False] * N, output_layers=[-1], model_cfg=args,
                           user_id_max=user_id_max, video_id_max=video_id_max, use_pe=getattr(args, "use_pe", 1))
 
     u, p = args.input_type["user"], args.input_type["photo"]
