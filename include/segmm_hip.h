@@ -565,6 +565,38 @@ int segmm_step_schedule(int kind, float base_lr, int warmup_steps, float start_f
                         int step_size, segmm_stream_t stream);
 int segmm_step_set_base_lr(float base_lr, segmm_stream_t stream);
 int segmm_step_get_lr(float* lr, float* base_lr, segmm_stream_t stream);
+/* THE NON-FINITE GUARD (added under ABI version 30: additive exports keep the version; nothing that existed changed, and no older entry point reads or writes the two
+ * words below).  Two words of the step state that were spare -- its size is unchanged -- hold `skip`, the verdict of the current
+ * step (1: the global 2-norm of its gradient is NaN or +-inf), and `skipped`, the number of steps skipped so far: the int32 words
+ * SEGMM_STEP_SKIP_WORD and SEGMM_STEP_SKIP_WORD + 1 of the state.  The state's step count goes on counting ATTEMPTED steps, and with
+ * it the scheduled rate, the EMA warm-up and the dropout seed words (torch: sched.step() runs every iteration); the bias
+ * corrections of step t are those of the APPLIED index t - skipped (torch: GradScaler.step leaves state["step"] alone when it skips).
+ * A guarded step: segmm_step_advance_guarded at its head; segmm_grad_norm / segmm_grad_norm_groups and then segmm_step_guard on the
+ * stream that holds the complete gradient; every update of the step through a *_guarded entry point behind them on that stream.
+ * segmm_step_advance_guarded: segmm_step_advance with the corrections of t - skipped; clears skip.  skipped == 0: the same bits.
+ * segmm_step_guard: one thread; skip = !finite(out2[0]), skipped += skip.  out2: the {norm, coef} the norm wrote.  The norm is
+ *   finite iff every element that enters it is: its fp64 partials of fp32 squares cannot overflow.
+ * segmm_step_set_skipped: skipped = the argument, skip = 0 (a loaded checkpoint).  segmm_step_get_skipped reads {skip, skipped}
+ *   back (either pointer may be null); like segmm_step_get it takes HOST pointers and synchronises the stream.
+ * segmm_adamw_guarded (coef may be null: segmm_adamw; else segmm_adamw_scaled), segmm_adamw_groups_guarded,
+ *   segmm_adamw_table_lrs_guarded (both phases; a skipped phase 0 marks no row) and segmm_ema_update_guarded: the arguments, checks
+ *   and arithmetic of the entry point they are named after, bit for bit, behind ONE wave-uniform read of skip in the bound state: a
+ *   workgroup of a skipped step returns before it loads anything, so p, m, v, the shadow and the flags keep every bit.  They read
+ *   the LIVE state: step must be -1, anything else is refused. */
+#define SEGMM_STEP_SKIP_WORD 14
+int segmm_step_advance_guarded(float beta1, float beta2, segmm_stream_t stream);
+int segmm_step_guard(const float* out2, segmm_stream_t stream);
+int segmm_step_set_skipped(uint32_t skipped, segmm_stream_t stream);
+int segmm_step_get_skipped(uint32_t* skip, uint32_t* skipped, segmm_stream_t stream);
+int segmm_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, const float* coef, segmm_stream_t stream);
+int segmm_adamw_groups_guarded(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end,
+                               const float* seg_lr_scale, const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr,
+                               float beta1, float beta2, float eps, int step, const float* coef, segmm_stream_t stream);
+int segmm_adamw_table_lrs_guarded(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                  uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay,
+                                  int step, int phase, const float* coef, segmm_stream_t stream);
+int segmm_ema_update_guarded(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream);
 
 
 /* ---- the callers either side of the training step -------------------------------------------

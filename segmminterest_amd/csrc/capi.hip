@@ -594,6 +594,25 @@ __global__ void step_advance_kernel(StepState* st, float b1, float b2) {
     st->bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)t));
     st->lr = (float)segmm_lr_at(*st, t - 1);          // step t runs at the rate of t - 1 completed steps: double, rounded once
 }
+// step_advance_kernel under the non-finite guard: the count, the seed words and the rate move with every ATTEMPTED step (torch:
+// sched.step() runs every iteration), the bias corrections are those of the APPLIED index t - skipped (torch: state["step"] moves
+// on applied steps only), and the verdict of the step before is cleared.  skipped = 0: the bits of step_advance_kernel.
+__global__ void step_advance_guarded_kernel(StepState* st, float b1, float b2) {
+    const int t = st->step + 1;
+    st->step = t;
+    const uint32_t lo = mix32(st->seed_lo + 0x9E3779B9u * (uint32_t)t);
+    st->seed_hi = mix32(st->seed_hi ^ lo ^ 0x85EBCA6Bu) & 0x7fffffffu;
+    st->seed_lo = lo;
+    const int ta = t - (int)st->skipped;          // (>= 1: at most the t - 1 steps before this one were skipped)
+    st->bc1 = ta > 0 ? (float)(1.0 - pow((double)b1, (double)ta)) : 1.f;
+    st->bc2_sqrt = ta > 0 ? (float)sqrt(1.0 - pow((double)b2, (double)ta)) : 1.f;
+    st->lr = (float)segmm_lr_at(*st, t - 1);
+    st->skip = 0u;
+}
+__global__ void step_set_skipped_kernel(StepState* st, uint32_t skipped) {
+    st->skip = 0u;
+    st->skipped = skipped;
+}
 __global__ void step_schedule_kernel(StepState* st, int kind, float base_lr, int warmup_steps, float start_factor, int decay_steps,
                                      float eta_min, float gamma, int step_size) {
     st->kind = kind; st->base_lr = base_lr; st->warmup_steps = warmup_steps; st->start_factor = start_factor;
@@ -1665,13 +1684,21 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
 }
 
 static int adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                      int step, const float* coef, hipStream_t stream) {
+                      int step, const float* coef, hipStream_t stream, bool guard = false) {
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     long long blocks = ((n >> 2) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    if (coef)
+    if (guard) {          // (segmm_adamw_guarded: step == -1, so the state is live)
+        SEGMM_REQUIRE(live, "adamw_guarded: no device-side step state");
+        if (coef)
+            hipLaunchKernelGGL((adamw_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
+                               beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
+        else
+            hipLaunchKernelGGL((adamw_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
+                               beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
+    } else if (coef)
         hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
                            beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
     else
@@ -1700,10 +1727,21 @@ int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, 
     return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream);
 }
 
+// the guarded entry points read the verdict in the LIVE step state: refused by value
+#define SEGMM_GUARD_LIVE(who) SEGMM_REQUIRE(step == -1, who ": step=%d (the guarded form reads the live device-side step state: step == -1)", step)
+
+int segmm_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
+    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_guarded: pointer/alignment");
+    SEGMM_GUARD_LIVE("adamw_guarded");
+    if (n <= 0) return 0;
+    return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream, true);
+}
+
 // segmm_adamw_table / segmm_adamw_table_scaled / segmm_adamw_table_lrs: one body (`who`: the entry point's name in the messages)
 static int adamw_table_impl(const char* who, float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                             uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
-                            const float* coef, segmm_stream_t stream) {
+                            const float* coef, segmm_stream_t stream, bool guard = false) {
     SEGMM_REQUIRE(p && m && v && flags && (ids || n_ids == 0) && aligned16(p) && aligned16(m) && aligned16(v), "%s: pointer/alignment", who);
     SEGMM_REQUIRE(phase == 0 || (phase == 1 && g && aligned16(g)), "%s: phase %d (0: rows without a gradient, 1: the listed rows; needs g)", who, phase);
     SEGMM_REQUIRE(!coef || phase == 1, "%s: a scaled update is phase 1 only (phase 0 has g = 0)", who);
@@ -1716,6 +1754,32 @@ static int adamw_table_impl(const char* who, float* p, const float* g, float* m,
     hipStream_t s = (hipStream_t)stream;
     const int w4 = width / 4;
     const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    if (guard) {          // (segmm_adamw_table_lrs_guarded: step == -1, the state is live) the launches below with the verdict read first
+        SEGMM_REQUIRE(live, "%s: no device-side step state", who);
+        if (phase == 0) {
+            if (n_ids > 0) {
+                hipLaunchKernelGGL(table_mark_guarded_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, s, (const long long*)ids, n_ids, (long long)n_rows,
+                                   flags, live);
+                LAUNCH_CHECK();
+            }
+            long long blocks = (n_rows * w4 + 255) / 256;
+            if (blocks > 4096) blocks = 4096;
+            hipLaunchKernelGGL(adamw_table_rest_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4,
+                               (const unsigned int*)flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, lr_scale);
+            LAUNCH_CHECK();
+            return 0;
+        }
+        if (n_ids == 0) return 0;
+        if (coef)
+            hipLaunchKernelGGL((adamw_table_rows_kernel<true, true>), dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4,
+                               (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
+        else
+            hipLaunchKernelGGL((adamw_table_rows_kernel<false, true>), dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4,
+                               (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live,
+                               (const float*)nullptr, lr_scale);
+        LAUNCH_CHECK();
+        return 0;
+    }
     if (phase == 0) {
         if (n_ids > 0) {
             hipLaunchKernelGGL(table_mark_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, s, (const long long*)ids, n_ids, (long long)n_rows, flags);
@@ -1723,7 +1787,7 @@ static int adamw_table_impl(const char* who, float* p, const float* g, float* m,
         }
         long long blocks = (n_rows * w4 + 255) / 256;
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(adamw_table_rest_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4, (const unsigned int*)flags,
+        hipLaunchKernelGGL(adamw_table_rest_kernel<>, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4, (const unsigned int*)flags,
                            lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, lr_scale);
         LAUNCH_CHECK();
         return 0;
@@ -1760,6 +1824,14 @@ int segmm_adamw_table_lrs(float* p, const float* g, float* m, float* v, int64_t 
                           const float* coef, segmm_stream_t stream) {
     return adamw_table_impl("adamw_table_lrs", p, g, m, v, n_rows, width, ids, n_ids, flags, lr, lr_scale, beta1, beta2, eps, weight_decay, step, phase,
                             coef, stream);
+}
+
+int segmm_adamw_table_lrs_guarded(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                  uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step,
+                                  int phase, const float* coef, segmm_stream_t stream) {
+    SEGMM_GUARD_LIVE("adamw_table_lrs_guarded");
+    return adamw_table_impl("adamw_table_lrs_guarded", p, g, m, v, n_rows, width, ids, n_ids, flags, lr, lr_scale, beta1, beta2, eps, weight_decay, step,
+                            phase, coef, stream, true);
 }
 
 int segmm_adamw_hist_push(float* hist, int cap, float lr, float beta1, float beta2, int step, segmm_stream_t stream) {
@@ -1841,32 +1913,54 @@ int segmm_adamw_table_lazy_rows(float* p, const float* g, float* m, float* v, in
     return 0;
 }
 
-int segmm_adamw_groups(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end, const float* seg_lr_scale,
-                       const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1, float beta2, float eps, int step,
-                       const float* coef, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_groups: pointer/alignment");
+// segmm_adamw_groups / segmm_adamw_groups_guarded: one body (`who`: the entry point's name in the messages)
+static int adamw_groups_impl(const char* who, float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end,
+                             const float* seg_lr_scale, const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1,
+                             float beta2, float eps, int step, const float* coef, segmm_stream_t stream, bool guard) {
+    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "%s: pointer/alignment", who);
     SEGMM_REQUIRE(seg_end && seg_lr_scale && seg_weight_decay && n_seg >= 1 && (((uintptr_t)seg_end) & 7u) == 0 &&
-                  (((uintptr_t)seg_lr_scale) & 3u) == 0 && (((uintptr_t)seg_weight_decay) & 3u) == 0, "adamw_groups: segment table (n_seg=%d)", n_seg);
-    SEGMM_REQUIRE(start >= 0 && start % 4 == 0 && n >= 0, "adamw_groups: start=%lld (>= 0, a multiple of 4), n=%lld", (long long)start, (long long)n);
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_groups: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_groups: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
+                  (((uintptr_t)seg_lr_scale) & 3u) == 0 && (((uintptr_t)seg_weight_decay) & 3u) == 0, "%s: segment table (n_seg=%d)", who, n_seg);
+    SEGMM_REQUIRE(start >= 0 && start % 4 == 0 && n >= 0, "%s: start=%lld (>= 0, a multiple of 4), n=%lld", who, (long long)start, (long long)n);
+    SEGMM_REQUIRE(step >= 1 || step == -1, "%s: step=%d (>= 1, or -1: the device-side step state)", who, step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "%s: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", who, (double)lr);
     if (n <= 0) return 0;
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     long long blocks = ((n >> 2) + 255) / 256;          // the grid of segmm_adamw
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-#define SEGMM_ADAMW_GROUPS(SCALED, FROZEN)                                                                                                        \
-    hipLaunchKernelGGL((adamw_groups_kernel<SCALED, FROZEN>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)start, \
-                       (long long)n, (const long long*)seg_end, seg_lr_scale, seg_weight_decay, (const unsigned char*)seg_frozen, n_seg, lr, beta1,   \
-                       beta2, eps, (float)bc1, (float)sqrt(bc2), live, coef)
-    if (coef && seg_frozen) SEGMM_ADAMW_GROUPS(true, true);
-    else if (coef) SEGMM_ADAMW_GROUPS(true, false);
-    else if (seg_frozen) SEGMM_ADAMW_GROUPS(false, true);
-    else SEGMM_ADAMW_GROUPS(false, false);
+    SEGMM_REQUIRE(!guard || live, "%s: no device-side step state", who);
+#define SEGMM_ADAMW_GROUPS(SCALED, FROZEN, GUARD)                                                                                                 \
+    hipLaunchKernelGGL((adamw_groups_kernel<SCALED, FROZEN, GUARD>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,       \
+                       (long long)start, (long long)n, (const long long*)seg_end, seg_lr_scale, seg_weight_decay, (const unsigned char*)seg_frozen,   \
+                       n_seg, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), live, coef)
+    if (guard) {
+        if (coef && seg_frozen) SEGMM_ADAMW_GROUPS(true, true, true);
+        else if (coef) SEGMM_ADAMW_GROUPS(true, false, true);
+        else if (seg_frozen) SEGMM_ADAMW_GROUPS(false, true, true);
+        else SEGMM_ADAMW_GROUPS(false, false, true);
+    } else if (coef && seg_frozen) SEGMM_ADAMW_GROUPS(true, true, false);
+    else if (coef) SEGMM_ADAMW_GROUPS(true, false, false);
+    else if (seg_frozen) SEGMM_ADAMW_GROUPS(false, true, false);
+    else SEGMM_ADAMW_GROUPS(false, false, false);
 #undef SEGMM_ADAMW_GROUPS
     LAUNCH_CHECK();
     return 0;
+}
+
+int segmm_adamw_groups(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end, const float* seg_lr_scale,
+                       const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1, float beta2, float eps, int step,
+                       const float* coef, segmm_stream_t stream) {
+    return adamw_groups_impl("adamw_groups", p, g, m, v, start, n, seg_end, seg_lr_scale, seg_weight_decay, seg_frozen, n_seg, lr, beta1, beta2, eps,
+                             step, coef, stream, false);
+}
+
+int segmm_adamw_groups_guarded(float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end,
+                               const float* seg_lr_scale, const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1,
+                               float beta2, float eps, int step, const float* coef, segmm_stream_t stream) {
+    SEGMM_GUARD_LIVE("adamw_groups_guarded");
+    return adamw_groups_impl("adamw_groups_guarded", p, g, m, v, start, n, seg_end, seg_lr_scale, seg_weight_decay, seg_frozen, n_seg, lr, beta1, beta2,
+                             eps, step, coef, stream, true);
 }
 
 int segmm_grad_norm_groups(const float* g, int64_t n, const int64_t* seg_end, const uint8_t* seg_frozen, int n_seg, float max_norm, double* scratch,
@@ -1917,6 +2011,8 @@ int segmm_grad_norm(const float* g, int64_t n, float max_norm, double* scratch, 
     return 0;
 }
 
+static_assert(offsetof(StepState, skip) == 4 * SEGMM_STEP_SKIP_WORD && offsetof(StepState, skipped) == 4 * (SEGMM_STEP_SKIP_WORD + 1),
+              "StepState: the header names the words of skip and skipped");
 int segmm_step_state_bytes(void) { return (int)sizeof(StepState); }
 int segmm_step_bind(void* state) {
     SEGMM_REQUIRE(!state || aligned16(state), "step_bind: the state must be 16-byte aligned device memory");
@@ -1936,6 +2032,40 @@ int segmm_step_advance(float beta1, float beta2, segmm_stream_t stream) {
     SEGMM_REQUIRE(st, "step_advance: no step state");
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st, beta1, beta2);
     LAUNCH_CHECK();
+    return 0;
+}
+int segmm_step_advance_guarded(float beta1, float beta2, segmm_stream_t stream) {
+    StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_advance_guarded: no step state");
+    hipLaunchKernelGGL(step_advance_guarded_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st, beta1, beta2);
+    LAUNCH_CHECK();
+    return 0;
+}
+int segmm_step_guard(const float* out2, segmm_stream_t stream) {
+    SEGMM_REQUIRE(out2 && (((uintptr_t)out2) & 3u) == 0, "step_guard: out2 (the {norm, coef} segmm_grad_norm wrote) pointer/alignment");
+    StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_guard: no step state");
+    hipLaunchKernelGGL(step_guard_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st, out2);
+    LAUNCH_CHECK();
+    return 0;
+}
+int segmm_step_set_skipped(uint32_t skipped, segmm_stream_t stream) {
+    SEGMM_REQUIRE(skipped <= 0x7fffffffu, "step_set_skipped: skipped=%u", skipped);
+    StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_set_skipped: no step state");
+    hipLaunchKernelGGL(step_set_skipped_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, st, skipped);
+    LAUNCH_CHECK();
+    return 0;
+}
+int segmm_step_get_skipped(uint32_t* skip, uint32_t* skipped, segmm_stream_t stream) {
+    const StepState* st = segmm_step_current();
+    SEGMM_REQUIRE(st, "step_get_skipped: no step state");
+    StepState h;
+    hipError_t e = hipMemcpyAsync(&h, st, sizeof(StepState), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    SEGMM_CHECK_HIP(e);
+    if (skip) *skip = h.skip;
+    if (skipped) *skipped = h.skipped;
     return 0;
 }
 int segmm_step_get(uint64_t* seed, int* step, float* bias_corrections, segmm_stream_t stream) {
@@ -2504,6 +2634,23 @@ static unsigned flat_pair_blocks(long long n4) {
     const long long cap = (long long)num_cus() * VEC_ADD_WG_PER_CU;          // one round of resident workgroups
     const long long blocks = (n4 + 255) / 256;
     return (unsigned)(blocks > cap ? cap : blocks < 1 ? 1 : blocks);
+}
+
+int segmm_ema_update_guarded(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream) {
+    if (const int rc = flat_pair_check("ema_update_guarded", shadow, p, n)) return rc;
+    SEGMM_REQUIRE(weight > 0.f && weight <= 1.f, "ema_update_guarded: weight=%g (0 < weight <= 1; weight = 1 - decay)", (double)weight);
+    SEGMM_GUARD_LIVE("ema_update_guarded");
+    if (n == 0) return 0;
+    const StepState* live = (const StepState*)segmm_step_current();          // (read for the verdict whether or not there is a warm-up)
+    SEGMM_REQUIRE(live, "ema_update_guarded: no device-side step state");
+    const long long n4 = n >> 2;
+    const int tail = (int)(n & 3);
+    if (knob(K_EMA_NT) != 0)
+        hipLaunchKernelGGL((ema_update_kernel<true, true>), dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
+    else
+        hipLaunchKernelGGL((ema_update_kernel<false, true>), dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
+    LAUNCH_CHECK();
+    return 0;
 }
 
 int segmm_ema_update(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream) {

@@ -192,8 +192,13 @@ struct StepState {
     float lr;                                  // rate of step `step` (of step 1 while step = 0), fp32(schedule in double)
     int kind;                                  // SEGMM_LR_* (0: no schedule)
     float base_lr; int warmup_steps; float start_factor; int decay_steps; float eta_min, gamma; int step_size;
-    uint32_t pad_[2];
+    // The non-finite guard (segmm_step_guard and the *_guarded entry points; every other kernel leaves these two words alone and never
+    // reads them: a caller of the older entry points was never promised that they are zero).  `step` goes on counting ATTEMPTED steps;
+    // the bias corrections of a guarded step are those of the applied index step - skipped (segmm_step_advance_guarded).
+    uint32_t skip;                             // this step's verdict: 1 = its gradient norm is NaN or inf, the guarded launches return
+    uint32_t skipped;                          // the steps skipped so far
 };
+static_assert(sizeof(StepState) == 64, "StepState: its size is part of the ABI (segmm_step_state_bytes)");
 static_assert(sizeof(StepState) % 16 == 0, "StepState: a multiple of 16 bytes");
 extern StepState* g_segmm_step;          // host: the bound state (capi.hip)
 StepState* segmm_step_current();         // host: the bound state, or the library's default one (allocated on first use)

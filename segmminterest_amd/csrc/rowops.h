@@ -932,10 +932,15 @@ __device__ __forceinline__ f32x4 adamw_grad4(f32x4 gg, const float* coef) {
 // ---------------------------------------------------------------- fused AdamW over a flat range (a13 / K9)
 // torch.optim.AdamW single-tensor update order (decoupled decay first), bias corrections passed in.
 // SCALED: the gradient is multiplied by *coef first (segmm_adamw_scaled: the clip coefficient segmm_grad_norm wrote)
-template <bool SCALED>
+// GUARD (the *_guarded entry points; `live` is then never null): one wave-uniform read of the live state's verdict -- a scalar load --
+// and the workgroup of a skipped step returns before it loads anything else.  GUARD = false is the kernel as it always was: it does
+// not read the word.  The same parameter, with the same meaning, on the groups, id-table and EMA kernels below.
+__device__ __forceinline__ bool step_skipped(const StepState* live) { return live->skip != 0u; }
+template <bool SCALED, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
                              float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
+    if constexpr (GUARD) { if (step_skipped(live)) return; }
     // bias corrections of the device-side step count; lr < 0 (SEGMM_LIVE_LR): the scheduled rate of that step as well
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     const long long n4 = n >> 2;
@@ -980,13 +985,14 @@ __device__ __forceinline__ int seg_find(const long long* __restrict__ seg_end, i
 // with a frozen flag to honour, a wave must have read the table before it may touch its elements, one dependent round trip more than
 // adamw_kernel has and at a cache-resident size (a wave runs one or two iterations) about half a microsecond of a 28 us launch
 // (profiles/param_groups/adamw_groups_bench.txt and profiles/README.md).
-template <bool SCALED, bool FROZEN>
+template <bool SCALED, bool FROZEN, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, long long start, long long n, const long long* __restrict__ seg_end,
                              const float* __restrict__ seg_lr_scale, const float* __restrict__ seg_wd,
                              const unsigned char* __restrict__ seg_frozen, int n_seg, float lr, float b1, float b2, float eps,
                              float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
 #pragma clang fp contract(off)
+    if constexpr (GUARD) { if (step_skipped(live)) return; }
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     const long long n4 = n >> 2;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1045,12 +1051,24 @@ __global__ __launch_bounds__(256) void table_mark_kernel(const long long* __rest
         if (id >= 0 && id < n_rows) flags[id] = 1u;
     }
 }
+// the same under the guard: a skipped step marks nothing (its phase 1 returns as well and would leave the marks standing)
+__global__ __launch_bounds__(256) void table_mark_guarded_kernel(const long long* __restrict__ ids, int n, long long n_rows, unsigned int* __restrict__ flags,
+                                                                 const StepState* live) {
+    if (step_skipped(live)) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) {
+        const long long id = ids[k];
+        if (id >= 0 && id < n_rows) flags[id] = 1u;
+    }
+}
 // every row WITHOUT a mark, g = 0
+template <bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_table_rest_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long n_rows,
                                                                int w4, const unsigned int* __restrict__ flags, float lr, float b1, float b2,
                                                                float eps, float wd, float bc1, float bc2_sqrt, const StepState* live,
                                                                float lr_scale) {
 #pragma clang fp contract(off)
+    if constexpr (GUARD) { if (step_skipped(live)) return; }
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     lr = lr * lr_scale;
     const float step = lr / bc1;
@@ -1064,13 +1082,14 @@ __global__ __launch_bounds__(256) void adamw_table_rest_kernel(float* __restrict
     }
 }
 // the marked rows, each once: one wave per list entry; lane 0 claims (and clears) the row's mark
-template <bool SCALED>
+template <bool SCALED, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                                float* __restrict__ v, long long n_rows, int w4, const long long* __restrict__ ids,
                                                                int n_ids, unsigned int* __restrict__ flags, float lr, float b1, float b2, float eps,
                                                                float wd, float bc1, float bc2_sqrt, const StepState* live,
                                                                const float* __restrict__ coef, float lr_scale) {
 #pragma clang fp contract(off)
+    if constexpr (GUARD) { if (step_skipped(live)) return; }
     if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
     lr = lr * lr_scale;
     const float step = lr / bc1;
@@ -1292,6 +1311,15 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
         out2[1] = c;
     }
 }
+// segmm_step_guard: the verdict of the step, one thread behind grad_norm_finish_kernel on the same stream.  The norm is finite iff
+// every live, non-frozen gradient element is (fp64 partials of fp32 squares cannot overflow), so NaN or inf here is the whole test.
+// Ordinary stores, as the other one-thread state kernels make them.
+__global__ void step_guard_kernel(StepState* st, const float* __restrict__ out2) {
+    const float t = out2[0];
+    const uint32_t bad = (__builtin_isnan(t) || __builtin_isinf(t)) ? 1u : 0u;
+    st->skip = bad;
+    st->skipped = st->skipped + bad;
+}
 
 // ---------------------------------------------------------------- out = a + b over a flat range (segmm_vec_add)
 // The gradient sum of a micro-batched step (Trainer(micro_batch=m)): one IEEE fp32 add per element, nothing to contract.  12 bytes of
@@ -1373,10 +1401,11 @@ __device__ __forceinline__ f32x4 ema_lerp(f32x4 s, f32x4 p, float w) {
     const f32x4 dw = d * w;
     return s + dw;
 }
-template <bool NT>
+template <bool NT, bool GUARD = false>
 __global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void ema_update_kernel(float* __restrict__ shadow, const float* __restrict__ p, long long n4, int tail,
                                                                             float weight, int warmup, int step, const StepState* live) {
 #pragma clang fp contract(off)
+    if constexpr (GUARD) { if (step_skipped(live)) return; }
     const long long stride = (long long)gridDim.x * blockDim.x;
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     f32x4* s4 = (f32x4*)shadow;

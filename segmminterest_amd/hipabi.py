@@ -295,10 +295,11 @@ def vec_add(out: torch.Tensor, a: torch.Tensor, b: torch.Tensor, n=None, out_off
         _check(lib().segmm_vec_add(out.data_ptr() + 4 * out_off, a.data_ptr() + 4 * a_off, b.data_ptr() + 4 * b_off, n, _stream()), "segmm_vec_add")
 
 
-def ema_update(shadow: torch.Tensor, p: torch.Tensor, n, weight, warmup, step, shadow_off=0, p_off=0):
+def ema_update(shadow: torch.Tensor, p: torch.Tensor, n, weight, warmup, step, shadow_off=0, p_off=0, guard=False):
     """segmm_ema_update: ``shadow[i] += (p[i] - shadow[i]) * w`` for i < n over contiguous float32 tensors (offsets in floats), three
     rounded fp32 operations per element.  ``w`` = ``weight`` or, with ``warmup``, max(weight, fp32(9 / (10 + t))), t = ``step`` (>= 1)
-    or, with step = -1, the bound device step state's count.  16-byte aligned, disjoint ranges.  A recordable command."""
+    or, with step = -1, the bound device step state's count.  16-byte aligned, disjoint ranges.  A recordable command.
+    ``guard``: segmm_ema_update_guarded (step = -1): nothing is written in a step the non-finite guard skipped."""
     _f32c(shadow, "ema_update: shadow")
     _f32c(p, "ema_update: p")
     _dev(shadow, p)
@@ -306,8 +307,9 @@ def ema_update(shadow: torch.Tensor, p: torch.Tensor, n, weight, warmup, step, s
     if n < 0 or min(shadow_off, p_off) < 0 or shadow_off + n > shadow.numel() or p_off + n > p.numel():
         raise RuntimeError("ema_update: %d elements from offsets %d / %d do not fit tensors of %d / %d" % (n, shadow_off, p_off, shadow.numel(), p.numel()))
     with _kprof("ema_update", 12 * n):
-        _check(lib().segmm_ema_update(shadow.data_ptr() + 4 * shadow_off, p.data_ptr() + 4 * p_off, n, float(weight), int(bool(warmup)), int(step),
-                                      _stream()), "segmm_ema_update")
+        fn = "segmm_ema_update_guarded" if guard else "segmm_ema_update"
+        _check(getattr(lib(), fn)(shadow.data_ptr() + 4 * shadow_off, p.data_ptr() + 4 * p_off, n, float(weight), int(bool(warmup)), int(step),
+                                  _stream()), fn)
 
 
 def vec_swap(a: torch.Tensor, b: torch.Tensor, n=None, a_off=0, b_off=0):
@@ -679,6 +681,33 @@ def step_set(seed, step, beta1=0.9, beta2=0.999):
 
 def step_advance(beta1=0.9, beta2=0.999):
     _check(lib().segmm_step_advance(float(beta1), float(beta2), _stream()), "segmm_step_advance")
+
+
+# ---- the non-finite guard (include/segmm_hip.h "THE NON-FINITE GUARD"): two words of the step state, skip and skipped
+STEP_SKIP_WORD = _K["SEGMM_STEP_SKIP_WORD"]          # int32 index of ``skip`` in the step state; ``skipped`` is the word behind it
+
+
+def step_advance_guarded(beta1=0.9, beta2=0.999):
+    """segmm_step_advance_guarded: :func:`step_advance` with the bias corrections of the applied index; clears the verdict."""
+    _check(lib().segmm_step_advance_guarded(float(beta1), float(beta2), _stream()), "segmm_step_advance_guarded")
+
+
+def step_guard(out2):
+    """segmm_step_guard: the verdict of the step from ``out2`` = the {norm, coef} :func:`grad_norm` wrote on this stream."""
+    if out2.dtype != torch.float32 or out2.numel() < 2:
+        raise RuntimeError("step_guard: out2 must be the two float32 of grad_norm")
+    _check(lib().segmm_step_guard(out2.data_ptr(), _stream()), "segmm_step_guard")
+
+
+def step_set_skipped(skipped):
+    _check(lib().segmm_step_set_skipped(int(skipped), _stream()), "segmm_step_set_skipped")
+
+
+def step_get_skipped():
+    """(skip, skipped) of the device-side step state: the last step's verdict and the count of skipped steps; synchronises."""
+    out = (C.c_uint32 * 2)()
+    _check(_lib_real().segmm_step_get_skipped(C.addressof(out), C.addressof(out) + 4, _stream()), "segmm_step_get_skipped")
+    return int(out[0]), int(out[1])
 
 
 def step_get():
@@ -1089,11 +1118,16 @@ def loss_fwd_bwd(B, S, logits, gt, bias_w, bias_b, exposure, coef, enabled, rew_
                                     _ptr(dlogits), _ptr(parts), _stream()), "segmm_loss_fwd_bwd")
 
 
-def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0, coef=None):
+def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off=0, coef=None, guard=False):
     """segmm_adamw over [p_off, p_off + n) of the flat buffers; ``coef``: a device float the gradient is multiplied by first
-    (segmm_adamw_scaled, the clip coefficient of :func:`grad_norm`)."""
+    (segmm_adamw_scaled, the clip coefficient of :func:`grad_norm`).  ``guard``: segmm_adamw_guarded (step = -1), with or without
+    ``coef``: nothing is read or written in a step the non-finite guard skipped."""
     with _kprof("adamw", 28 * int(n)):
-        _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off, coef)
+        if guard:
+            _check(lib().segmm_adamw_guarded(p.data_ptr() + 4 * p_off, g.data_ptr() + 4 * p_off, m.data_ptr() + 4 * p_off, v.data_ptr() + 4 * p_off, n,
+                                             lr, beta1, beta2, eps, weight_decay, step, _ptr(coef), _stream()), "segmm_adamw_guarded")
+        else:
+            _adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, p_off, coef)
 
 
 def adamw_table(p, g, m, v, off, n_rows, width, ids, flags, lr, beta1, beta2, eps, weight_decay, step, phase, coef=None):
@@ -1133,26 +1167,29 @@ def _segs(segs):
     return ends.data_ptr(), scale.data_ptr(), wd.data_ptr(), _ptr(frozen), n_seg
 
 
-def adamw_groups(p, g, m, v, start, n, segs, lr, beta1, beta2, eps, step, coef=None):
+def adamw_groups(p, g, m, v, start, n, segs, lr, beta1, beta2, eps, step, coef=None, guard=False):
     """segmm_adamw_groups over [start, start + n) of the flat buffers, ``segs`` = (ends, lr_scale, weight_decay, frozen) the
-    segment table (:func:`_segs`; ends counted from the buffers' first element); ``coef`` as in :func:`adamw`."""
+    segment table (:func:`_segs`; ends counted from the buffers' first element); ``coef`` and ``guard`` (segmm_adamw_groups_guarded)
+    as in :func:`adamw`."""
     start, n = int(start), int(n)
     if start < 0 or start % 4 or n < 0 or start + n > min(p.numel(), g.numel(), m.numel(), v.numel()):
         raise RuntimeError("adamw_groups: range [%d, %d) (start a multiple of 4) outside buffers of %d / %d / %d / %d elements"
                            % (start, start + n, p.numel(), g.numel(), m.numel(), v.numel()))
     e, s, w, f, n_seg = _segs(segs)
     with _kprof("adamw", 28 * n):
-        _check(lib().segmm_adamw_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), start, n, e, s, w, f, n_seg, float(lr), float(beta1),
-                                        float(beta2), float(eps), int(step), _ptr(coef), _stream()), "segmm_adamw_groups")
+        fn = "segmm_adamw_groups_guarded" if guard else "segmm_adamw_groups"
+        _check(getattr(lib(), fn)(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), start, n, e, s, w, f, n_seg, float(lr), float(beta1),
+                                  float(beta2), float(eps), int(step), _ptr(coef), _stream()), fn)
 
 
-def adamw_table_lrs(p, g, m, v, off, n_rows, width, ids, flags, lr, lr_scale, beta1, beta2, eps, weight_decay, step, phase, coef=None):
-    """segmm_adamw_table_lrs: :func:`adamw_table` at the rate fp32(lr * lr_scale)."""
+def adamw_table_lrs(p, g, m, v, off, n_rows, width, ids, flags, lr, lr_scale, beta1, beta2, eps, weight_decay, step, phase, coef=None, guard=False):
+    """segmm_adamw_table_lrs: :func:`adamw_table` at the rate fp32(lr * lr_scale).  ``guard``: segmm_adamw_table_lrs_guarded (step = -1)."""
     with _kprof("adamw", (24 if phase == 0 else 28) * int(n_rows if phase == 0 else ids.numel()) * int(width)):
-        _check(lib().segmm_adamw_table_lrs(p.data_ptr() + 4 * off, None if g is None else g.data_ptr() + 4 * off, m.data_ptr() + 4 * off,
-                                           v.data_ptr() + 4 * off, int(n_rows), int(width), ids.data_ptr(), ids.numel(), flags.data_ptr(), float(lr),
-                                           float(lr_scale), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), int(phase),
-                                           _ptr(coef), _stream()), "segmm_adamw_table_lrs")
+        fn = "segmm_adamw_table_lrs_guarded" if guard else "segmm_adamw_table_lrs"
+        _check(getattr(lib(), fn)(p.data_ptr() + 4 * off, None if g is None else g.data_ptr() + 4 * off, m.data_ptr() + 4 * off,
+                                  v.data_ptr() + 4 * off, int(n_rows), int(width), ids.data_ptr(), ids.numel(), flags.data_ptr(), float(lr),
+                                  float(lr_scale), float(beta1), float(beta2), float(eps), float(weight_decay), int(step), int(phase),
+                                  _ptr(coef), _stream()), fn)
 
 
 # ---- lazy exact AdamW of an id table (include/segmm_hip.h "Lazy exact AdamW"): stamps int32 [n_rows], hist float32 [cap, 4]

@@ -132,6 +132,8 @@ def fit(trainer: "Trainer", train_batches, valid_batches, epochs: int, valid_ste
                     log("Base learning rate: %g, Global_step: %d" % (trainer.opt.lr, global_step))
                 if log is not None:
                     log("Valid_loss: %s, %s: %s, Global_step: %d" % (hist["valid_loss"][-1] if "valid_loss" in hist else None, main_metric, avg, global_step))
+                    if getattr(trainer.opt, "skip_nonfinite", False):         # (one read-back, where the validation has synchronised already)
+                        log("Skipped_steps: %d (non-finite gradient norm), Global_step: %d" % (trainer.opt.skipped_steps, global_step))
                 if ckpt is not None and trainer.comm.rank == 0:
                     ckpt.save_checkpoint(model=trainer.model, optimizer=trainer.opt, num_epochs=epoch, metric_vals={"main_metric": avg},
                                          **({"ema": trainer.ema} if trainer.ema is not None else {}))

@@ -266,6 +266,20 @@ class PlateauLR:
         return None
 
 
+def parse_skip_nonfinite(spec, device_state, lazy_tables):
+    """``skip_nonfinite=`` of FusedAdamW / Trainer -> bool.  Refused by name: a value that is no bool; the guard without the device
+    step state (``device_state``: True / False, or None when the caller cannot know yet -- FusedAdamW on its own checks at its first
+    step); the guard beside ``lazy_tables`` (a skipped step has no g = 0 replay in the ring: a follow-up)."""
+    if not isinstance(spec, bool):
+        raise ValueError("skip_nonfinite must be a bool, not %r" % (spec,))
+    if spec and device_state is not None and not device_state:
+        raise ValueError("skip_nonfinite=True needs device_state=True: the verdict and the count of skipped steps live in the device step state")
+    if spec and lazy_tables is not None:
+        raise ValueError("skip_nonfinite=True with lazy_tables is not supported: a skipped step has no g = 0 replay in the lazy tables' "
+                         "history ring (a follow-up); use one of the two")
+    return spec
+
+
 EMA_KEYS = ("decay", "warmup")
 
 
@@ -437,7 +451,8 @@ class WeightEMA:
         pos, step = 0, -1 if live else opt.step_count
         tail = opt.__dict__.get("_lazy_tail")
         if not tail:
-            H.ema_update(self.shadow, st.flat, st.n_live, self.weight, self.warmup, step)
+            # (skip_nonfinite: the guarded form -- the shadow of a skipped step keeps its bits)
+            H.ema_update(self.shadow, st.flat, st.n_live, self.weight, self.warmup, step, **opt._guard_kw())
             return
         for o, n in sorted(tail.values()):
             if o > pos:
@@ -578,11 +593,26 @@ class FusedAdamW:
     batch's own ids -- (segmm_adamw_table_lazy_rows_ema) and the EMA's update around the table; no phase 1, no stamp launch, no flags.
     ``flush_tables()`` brings the shadow up with the rows; ``ema.applied()`` / ``ema.state_dict()`` / ``ema.load_state_dict()`` flush
     first, so evaluation on the averaged weights and ``"model_ema"`` in a checkpoint are the dense trainer's, bit for bit.  Without
-    an EMA the key changes nothing."""
+    an EMA the key changes nothing.
+
+    ``skip_nonfinite`` (False = every launch and every bit as ever; True): the NON-FINITE GUARD, what torch.cuda.amp.GradScaler.step
+    does for torch's optimizers.  When the global 2-norm of a step's live, non-frozen gradient is NaN or +-inf -- it is finite iff
+    every such element is -- the step changes no parameter, no moment and no EMA shadow, and is counted as skipped; training goes on
+    with the next batch.  No host round trip, eager or recorded: the norm of ``max_grad_norm`` (run as ``max_grad_norm=inf`` when none
+    is set: coefficient 1, ``grad_norm`` reports the norm) is followed by a one-thread launch (segmm_step_guard) that leaves the
+    verdict and the count in the device step state, and every update of the step takes its *_guarded entry point, whose workgroups
+    read the verdict first and return.  An applied step has the bits of the unguarded step.  ``step_count`` goes on counting
+    ATTEMPTED steps, and the scheduled rate, the EMA warm-up and the dropout streams follow it (torch: ``sched.step()`` runs every
+    iteration); the bias corrections of step t are those of the applied index t - skipped (torch: ``state["step"]`` moves on applied
+    steps only).  ``skipped_steps`` reads the count (a sync), ``applied_steps`` = ``step_count`` - ``skipped_steps``;
+    ``state_dict()`` writes ``"step"`` = applied steps and ``segmm_skipped_steps`` into every ``param_groups`` entry, and
+    ``load_state_dict`` restores both (a checkpoint without the key: 0 skipped).  Needs the device step state
+    (``Trainer(device_state=True)``); refused beside ``lazy_tables``.  ``.grad`` keeps what the backward delivered."""
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lr_schedule=None,
-                 param_groups=None, ema=None, lazy_tables=None):
+                 param_groups=None, ema=None, lazy_tables=None, skip_nonfinite=False):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
+        self.skip_nonfinite = parse_skip_nonfinite(skip_nonfinite, None, lazy_tables)
         ema = parse_ema(ema)
         self.ema = None if ema is None else WeightEMA(self, *ema)
         # flush_every (= the ring's capacity) or None; _lazy: name -> dict(stamps, flags, o, rows, width) of the tables stepped lazily
@@ -672,7 +702,40 @@ class FusedAdamW:
     @property
     def grad_norm(self) -> Optional[torch.Tensor]:
         """The 2-norm of the last step's gradients (before clipping) as a 0-dim device tensor, None without ``max_grad_norm``."""
-        return None if self.max_grad_norm is None or self._clip_out is None else self._clip_out[0]
+        return None if (self.max_grad_norm is None and not self.skip_nonfinite) or self._clip_out is None else self._clip_out[0]
+
+    # ---- the non-finite guard (skip_nonfinite=True)
+    def _guard_state(self, what):
+        """Binds the device step state for a call of the guard; refuses, by name, an optimizer that has none."""
+        if not self.__dict__.get("device_state", False) or self.__dict__.get("_step_state") is None:
+            raise RuntimeError("%s: skip_nonfinite needs the device step state -- build the optimizer through Trainer(device_state=True)" % what)
+        H.step_bind(self._step_state)
+
+    def _guard_kw(self):
+        """What the step's update launches get on top of their arguments: ``guard=True`` under skip_nonfinite, else nothing."""
+        return {"guard": True} if self.__dict__.get("skip_nonfinite", False) else {}
+
+    @property
+    def skipped_steps(self):
+        """The steps the non-finite guard has skipped (the device's count: synchronises); 0 without the guard."""
+        if not self.skip_nonfinite:
+            return 0
+        self._guard_state("skipped_steps")
+        return H.step_get_skipped()[1]
+
+    @property
+    def applied_steps(self):
+        """``step_count`` - ``skipped_steps``: torch's ``state["step"]``."""
+        return self.step_count - self.skipped_steps
+
+    @property
+    def skipped(self):
+        """This step's verdict as a 0-dim int32 device tensor (1: skipped), a view of the device step state: valid until the head of
+        the next step.  None without the guard."""
+        if not self.skip_nonfinite:
+            return None
+        self._guard_state("skipped")
+        return self._step_state[H.STEP_SKIP_WORD]
 
     def _coef(self):
         return None if self.max_grad_norm is None else self._clip_out[1:2]
@@ -926,6 +989,9 @@ class FusedAdamW:
         on the current stream (the trainer calls this at the head of the step on a stream of its own: the forward and backward
         only read the listed rows).  ``step()`` then updates the listed rows and skips the table's range.  Element for element
         the arithmetic of the one-launch dense update."""
+        if self.skip_nonfinite:
+            raise RuntimeError("table_early(%s) under skip_nonfinite: the early pass runs before the step's verdict exists; the guarded "
+                               "step takes the table densely at its tail (step() without an early entry)" % name)
         st = self._state()
         if self.ema is not None:
             self.ema.step_head(st)          # this pass is the step's first parameter write
@@ -956,16 +1022,21 @@ class FusedAdamW:
         self.step_count += 1
         if not st.__dict__.get("direct_grads", False):
             self._sync_grads(st)
-        if self.max_grad_norm is not None:
+        if self.skip_nonfinite:
+            self._guard_state("step")
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            max_norm = math.inf if self.max_grad_norm is None else self.max_grad_norm          # (the guard alone: the norm, never a clip)
             # the global norm reads every live gradient: the caller enqueues this once all of them are complete (train_step: the
             # tail stream, after the side / auxiliary streams have joined and, under data parallelism, every bucket is reduced)
             if self._clip_out is None or self._clip_out.device != st.flat.device:
                 self._clip_out = torch.zeros(2, dtype=torch.float32, device=st.flat.device)
                 self._clip_scratch = torch.zeros(H.GRAD_NORM_SCRATCH, dtype=torch.float64, device=st.flat.device)
             if self.groups is not None and self._any_frozen:          # frozen gradients stay out of the norm (torch: grad = None)
-                H.grad_norm_groups(st.gflat if gbuf is None else gbuf, st.n_live, self._segs, self.max_grad_norm, self._clip_scratch, self._clip_out)
+                H.grad_norm_groups(st.gflat if gbuf is None else gbuf, st.n_live, self._segs, max_norm, self._clip_scratch, self._clip_out)
             else:
-                H.grad_norm(st.gflat if gbuf is None else gbuf, st.n_live, self.max_grad_norm, self._clip_scratch, self._clip_out)
+                H.grad_norm(st.gflat if gbuf is None else gbuf, st.n_live, max_norm, self._clip_scratch, self._clip_out)
+            if self.skip_nonfinite:          # the verdict, behind the norm's finish on this stream and ahead of every update of the step
+                H.step_guard(self._clip_out)
 
     def _sync_grads(self, st):
         """The kernel reads the FLAT gradient buffer.  After Trainer.train_step the parameters' ``.grad`` ARE views of it
@@ -989,11 +1060,11 @@ class FusedAdamW:
         step = -1 if self.__dict__.get("device_state", False) else self.step_count
         if end > start and self.groups is not None:
             H.adamw_groups(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, start, end - start, self._segs_arg, self._lr_arg(), self.betas[0],
-                           self.betas[1], self.eps, step, coef=self._coef())
+                           self.betas[1], self.eps, step, coef=self._coef(), **self._guard_kw())
         elif end > start:
             # device_state: the bias corrections come from the device-side step count (segmm_step_advance), step = -1
             H.adamw(st.flat, st.gflat if gbuf is None else gbuf, self.m, self.v, end - start, self._lr_arg(), self.betas[0], self.betas[1],
-                    self.eps, self.wd, step, p_off=start, coef=self._coef())
+                    self.eps, self.wd, step, p_off=start, coef=self._coef(), **self._guard_kw())
 
     def end_step(self):
         if self.ema is not None:
@@ -1010,11 +1081,13 @@ class FusedAdamW:
         st = self._state()
         names = [n for n, _ in self.model.named_parameters()]
         state = {}
+        # skip_nonfinite: "step" is the APPLIED count, as torch keeps it (one read-back; state_dict synchronises already)
+        skipped = self.skipped_steps
         for i, n in enumerate(names):
             if n in st.live_names and not self._frozen(n):
                 o, k = st.index[n]
                 shape = st._params[n].shape
-                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.m[o:o + k].view(shape).clone(),
+                state[i] = {"step": torch.tensor(float(self.step_count - skipped)), "exp_avg": self.m[o:o + k].view(shape).clone(),
                             "exp_avg_sq": self.v[o:o + k].view(shape).clone()}
         group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
@@ -1023,6 +1096,8 @@ class FusedAdamW:
             # torch's schedulers keep the base rate in "initial_lr" and the running one in "lr"; the descriptor is an extra key
             # torch.optim.AdamW.load_state_dict carries along untouched
             group.update(lr=self.current_lr(), initial_lr=self.lr, segmm_lr_schedule=dataclasses.asdict(self.schedule))
+        if self.skip_nonfinite:          # (an extra key like segmm_lr_scale: step_count = "step" + this)
+            group["segmm_skipped_steps"] = skipped
         if self.groups is None:
             return {"state": state, "param_groups": [group]}
         # one torch-format entry per group, the default group first (scale 1: its "lr" / "initial_lr" are the optimizer's own, as in
@@ -1070,6 +1145,14 @@ class FusedAdamW:
         names = [n for n, _ in self.model.named_parameters()]
         if self.groups is not None or len(sd["param_groups"]) > 1:
             self._check_grouping(sd, names)
+        skipped = sd["param_groups"][0].get("segmm_skipped_steps", 0)          # (a checkpoint without the key: nothing was skipped)
+        if isinstance(skipped, bool) or not isinstance(skipped, int) or skipped < 0:
+            raise ValueError("load_state_dict: segmm_skipped_steps must be an int >= 0, not %r" % (skipped,))
+        if skipped and not self.skip_nonfinite:
+            raise ValueError("load_state_dict: the checkpoint counts %d skipped steps (segmm_skipped_steps); it resumes under "
+                             "skip_nonfinite=True, where the attempted and the applied count are kept apart" % skipped)
+        if self.skip_nonfinite:          # (refused before anything is overwritten)
+            self._guard_state("load_state_dict")
         st = self._state()
         self.m.zero_()
         self.v.zero_()
@@ -1081,7 +1164,7 @@ class FusedAdamW:
                 self.m[o:o + k].copy_(s["exp_avg"].reshape(-1))
                 self.v[o:o + k].copy_(s["exp_avg_sq"].reshape(-1))
                 steps.add(int(float(s["step"])))
-        self.step_count = max(steps) if steps else 0
+        self.step_count = (max(steps) if steps else 0) + skipped          # "step" holds the applied count; the host's counts attempts
         self._lazy_restamp()          # lazy tables: the loaded moments are every row's, at the loaded count; nothing stays pending
         g = sd["param_groups"][0]
         self.lr, self.wd, self.betas, self.eps = g["lr"], g["weight_decay"], tuple(g["betas"]), g["eps"]
@@ -1099,5 +1182,7 @@ class FusedAdamW:
             H.step_bind(self._step_state)
             seed, _, _ = H.step_get()
             H.step_set(seed, self.step_count, *self.betas)
+            if self.skip_nonfinite:          # (the next step's head takes its corrections from step_count + 1 - skipped)
+                H.step_set_skipped(skipped)
             if self.schedule is not None:
                 self._install_schedule()

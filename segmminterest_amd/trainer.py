@@ -39,7 +39,7 @@ from .encoder import SegFormerX
 from .eval_passes import EvalPasses
 from .loop import CheckPointer, compute_final_result, early_stop_reached, fit  # noqa: F401
 from .optim import (GROUP_KEYS, FusedAdamW, LRSchedule, PlateauLR, WeightEMA, group_segments, no_decay_groups, parse_ema,  # noqa: F401
-                    parse_lazy_data_parallel, parse_lazy_ema, parse_lazy_tables, resolve_param_groups)
+                    parse_lazy_data_parallel, parse_lazy_ema, parse_lazy_tables, parse_skip_nonfinite, resolve_param_groups)
 
 
 # ------------------------------------------------------------------------------------------------ model factory
@@ -127,13 +127,18 @@ class Trainer(EvalPasses):
     the reference's hot loop (main_for_seq_leave_earlystop_SegMM.py:269-300) minus its host syncs.
     Gradient clipping is a no-op in the reference (exhausted generator at :298), so the default ``max_grad_norm=None`` does not
     clip; ``max_grad_norm=m`` clips to global norm m on the device before AdamW (see FusedAdamW; ``trainer.opt.grad_norm`` is the
-    norm the reference logs), in the eager, recorded and data-parallel steps."""
+    norm the reference logs), in the eager, recorded and data-parallel steps.
+    ``skip_nonfinite=True`` (needs ``device_state=True``; see FusedAdamW): a step whose gradient norm is NaN or inf changes no
+    parameter, moment or EMA shadow and is counted as skipped, without a host round trip -- ``out["skipped"]`` of ``train_step`` /
+    ``run_recorded`` is this step's verdict (a 0-dim device tensor, 0 or 1, valid until the next step), ``opt.skipped_steps`` the count."""
 
 
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, comm: Optional[DPComm] = None, overlap=True, dropout=True,
                  feature_table=None, sparse_tables=True, device_state=False, max_grad_norm=None, lr_schedule=None, micro_batch=None,
-                 param_groups=None, ema=None, lazy_tables=None, mixed_precision=None):
+                 param_groups=None, ema=None, lazy_tables=None, mixed_precision=None, skip_nonfinite=False):
         self.model = model
+        # skip_nonfinite=True: the non-finite guard (FusedAdamW).  A bool; needs the device step state; refused beside lazy_tables
+        parse_skip_nonfinite(skip_nonfinite, bool(device_state), lazy_tables)
         # mixed_precision=None | False | True | dict(forward=True, dgrad=True, wgrad=True): the plane GEMMs of the named roles multiply
         # ONE product (hi . hi: fp16 operands, fp32 accumulate) in the passes of the optimisation step; master weights, AdamW and
         # every evaluation pass are untouched.  Lives on the model's ParamStore, where the GEMM helpers of engine.py read it.
@@ -185,7 +190,7 @@ class Trainer(EvalPasses):
         self.feature_table = feature_table
         self.dropout = dropout      # False: run the step in eval mode (deterministic; used by the DP equivalence tests)
         self.opt = FusedAdamW(model, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule,
-                              param_groups=param_groups, ema=ema, lazy_tables=lazy_tables)          # per-group rate scale, decay and freezing: see FusedAdamW
+                              param_groups=param_groups, ema=ema, lazy_tables=lazy_tables, skip_nonfinite=skip_nonfinite)          # per-group rate scale, decay and freezing: see FusedAdamW
         # ema=None | decay | dict(decay=0.999, warmup=True): a device-side moving average of the weights (WeightEMA), or None
         self.ema = self.opt.ema
         self.comm = comm if comm is not None else DPComm()
@@ -232,6 +237,11 @@ class Trainer(EvalPasses):
             if self.opt.schedule is not None:
                 self.opt._install_schedule()
             st.live_seed = H.LIVE_SEED | 0x5E6D0001          # the (constant) seed argument of every dropout launch
+
+    @property
+    def _guard(self) -> bool:
+        """The optimizer's non-finite guard (``skip_nonfinite=True``) is on."""
+        return bool(getattr(self.opt, "skip_nonfinite", False))
 
     @property
     def mixed_precision(self):
@@ -373,6 +383,10 @@ class Trainer(EvalPasses):
                 H.step_bind(self._step_state)
                 seed, _, _ = H.step_get()
                 H.step_set(seed, self.opt.step_count + 1, *self.opt.betas)
+        if self._guard:
+            # the early pass would run before the step's verdict exists: under the guard the tables are stepped densely at the tail,
+            # with the rest of the live range (FusedAdamW.step without an early entry)
+            return
         lazy = self.opt.lazy_flush_every is not None
         self._lazy_own = {}          # name -> the batch's own id list, of the tables whose head runs below with mark=False, single process
         if lazy and self._param_hooks():
@@ -557,7 +571,8 @@ class Trainer(EvalPasses):
         self.opt.zero_grad()
         H.mark(H.PHASE_STEP_BEGIN)
         if self.device_state:          # first launches of the step: advance the device-side step state (ONE count and one rate per
-            H.step_advance(*self.opt.betas)          # optimizer step), fresh header rows
+            # optimizer step), fresh header rows.  skip_nonfinite: the guarded form -- corrections of the applied index, verdict cleared
+            (H.step_advance_guarded if self._guard else H.step_advance)(*self.opt.betas)
             st.hdr_step_begin()
         st._trusted = False
         st.in_train_step = True          # (the step's passes take Trainer(mixed_precision=...); evaluation passes never run in here)
@@ -707,6 +722,8 @@ class Trainer(EvalPasses):
             res = {}
             for key in keys:
                 res[key] = logits if key == "logits" else batch["label"] if key == "gt" else sums[12] if key == "loss" else sums[_LIDX[key]]
+            if self._guard:
+                res["skipped"] = self.opt.skipped
             return res
         except BaseException:
             if self.device_state and self.opt.__dict__.get("_early") is None:
@@ -778,6 +795,8 @@ class Trainer(EvalPasses):
         """The tail of the plain step: the data-parallel reductions still outstanding, then AdamW."""
         st = self.model._store
         lazy_rows = self._lazy_rows(st)
+        if self._guard:
+            out["skipped"] = self.opt.skipped          # (a view of the device step state: the verdict the step's tail leaves there)
         if self.comm.active and self.overlap:
             H.host_action(self._flush_bucket)          # the tail of the backward (embedding gradients) that stayed below the merge threshold
         if self.comm.active and self.overlap and self.per_bucket_adamw and self._covers_live(st):
@@ -788,7 +807,9 @@ class Trainer(EvalPasses):
             # completed early (a contiguous prefix of the flat buffer: head | layers ...) are stepped together, then the last one
             H.mark(H.PHASE_STEP_TAIL)
             works = self._bucket_works
-            if self.opt.max_grad_norm is not None:
+            if self.opt.max_grad_norm is not None or self._guard:
+                # (skip_nonfinite: the verdict is the norm's -- a per-bucket AdamW would run before it; every rank takes the norm of
+                # the same all-reduced gradient, hence the same verdict, without a collective)
                 # a global norm needs every bucket reduced: no per-bucket overlap, one norm over the reduced live range (each rank
                 # computes it from its own, identical copy of the all-reduced gradient), then one AdamW launch
                 H.host_action(functools.partial(self._wait_buckets, range(len(works))))
@@ -957,6 +978,8 @@ class Trainer(EvalPasses):
         lr = self.opt.lr if self.opt.schedule is None else H.LIVE_LR
         # (the recorded segmm_ema_update carries the EMA's weight and warm-up flag by value)
         return (lr, self.opt.wd, tuple(self.opt.betas), self.opt.eps, self.opt.max_grad_norm, self.opt.group_table(),
+                # (the recorded step carries the guard as its commands: segmm_step_guard and the *_guarded updates)
+                self._guard,
                 # (... and beside lazy tables the recorded *_ema launches stand for the key lazy_tables=dict(ema=True))
                 None if self.ema is None else self.ema.hyper() + (bool(getattr(self.opt, "lazy_ema", False)),),
                 # (the recorded plane GEMMs carry their product count in the command: segmm_gemm_p or segmm_gemm_pq(..., 1))
