@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/segmm_hip.h"
@@ -624,6 +625,13 @@ __global__ void step_base_lr_kernel(StepState* st, float base_lr) {
     st->lr = (float)segmm_lr_at(*st, st->step - 1);
 }
 }  // namespace segmm
+
+// Run-time bools -> template arguments: f is called once, with the std::bool_constants that match, in the order of the bools.
+template <class F> static void with_bools(F&& f) { f(); }
+template <class F, class... Bs> static void with_bools(F&& f, bool b, Bs... bs) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, bs...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, bs...);
+}
 
 extern "C" {
 
@@ -1683,122 +1691,129 @@ int segmm_loss_fwd_bwd(int B, int S, const float* logits, const int64_t* gt, con
     return 0;
 }
 
-static int adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                      int step, const float* coef, hipStream_t stream, bool guard = false) {
+// ---------------------------------------------------------------- the AdamW / EMA family (rowops.h)
+// What its entry points share, each stated once (`who`: the entry point's name in the messages).
+#define SEGMM_TRY(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
+
+// The step arguments: step >= 1 by value, with the host's double-precision bias corrections, or -1: the device-side step state
+// (the kernels then read its count and corrections, and for lr < 0 its rate)
+struct StepArgs { float bc1, bc2_sqrt; const StepState* live; };
+static int step_args(const char* who, float lr, float beta1, float beta2, int step, StepArgs* a) {
+    SEGMM_REQUIRE(step >= 1 || step == -1, "%s: step=%d (>= 1, or -1: the device-side step state)", who, step);
+    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "%s: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", who, (double)lr);
     const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
+    a->bc1 = (float)bc1; a->bc2_sqrt = (float)sqrt(bc2);
+    a->live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    SEGMM_REQUIRE(step > 0 || a->live, "%s: no device-side step state", who);
+    return 0;
+}
+// the guarded entry points read the verdict in the LIVE step state: refused by value
+#define SEGMM_GUARD_LIVE(who) SEGMM_REQUIRE(step == -1, "%s: step=%d (the guarded form reads the live device-side step state: step == -1)", who, step)
+
+static int ptrs16(const char* who, std::initializer_list<const void*> ps) {
+    for (const void* q : ps) SEGMM_REQUIRE(q && aligned16(q), "%s: pointer/alignment", who);
+    return 0;
+}
+// an id table of n_rows x width floats, a list of n_ids rows, and (cap != NULL) the ring of the lazy forms
+static int table_shape_check(const char* who, int width, int64_t n_rows, int n_ids, const int* cap) {
+    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && (!cap || *cap >= 1), "%s: width %% 4, sizes%s", who, cap ? ", cap >= 1" : "");
+    return 0;
+}
+static int lr_scale_check(const char* who, float lr_scale) {
+    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "%s: lr_scale=%g (finite, >= 0)", who, (double)lr_scale);
+    return 0;
+}
+// target of the stamp and the catch-up: the step count itself (relative == 0, target >= 0), or the bound device step count plus
+// target (relative != 0, target 0 or -1; *live is then that state)
+static int lazy_target(const char* who, int target, int relative, const StepState** live) {
+    SEGMM_REQUIRE(relative ? (target == 0 || target == -1) : target >= 0,
+                  "%s: target=%d (relative=%d: >= 0 by value; 0 or -1 from the device-side step count)", who, target, relative);
+    *live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
+    SEGMM_REQUIRE(!relative || *live, "%s: no device-side step state", who);
+    return 0;
+}
+// the shadow of a lazy table: 16-byte aligned and disjoint from the n_rows x width floats at p
+static int lazy_shadow_check(const char* who, const float* shadow, const float* p, int64_t n_rows, int width) {
+    SEGMM_REQUIRE(shadow && aligned16(shadow), "%s: shadow pointer/alignment", who);
+    const uintptr_t nb = (uintptr_t)n_rows * (uintptr_t)width * 4u, ps = (uintptr_t)shadow, pp = (uintptr_t)p;
+    SEGMM_REQUIRE(ps + nb <= pp || pp + nb <= ps, "%s: shadow overlaps p (they must be disjoint)", who);
+    return 0;
+}
+
+// segmm_adamw / _scaled / _guarded behind their pointer checks
+static int adamw_flat(const char* who, float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int step, const float* coef, segmm_stream_t stream, bool guard) {
+    StepArgs a;
+    SEGMM_TRY(step_args(who, lr, beta1, beta2, step, &a));
+    if (n <= 0) return 0;
     long long blocks = ((n >> 2) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    if (guard) {          // (segmm_adamw_guarded: step == -1, so the state is live)
-        SEGMM_REQUIRE(live, "adamw_guarded: no device-side step state");
-        if (coef)
-            hipLaunchKernelGGL((adamw_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
-                               beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
-        else
-            hipLaunchKernelGGL((adamw_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
-                               beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
-    } else if (coef)
-        hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
-                           beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
-    else
-        hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, (long long)n, lr, beta1,
-                           beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef);
+    with_bools([&](auto SCALED, auto GUARD) {
+        hipLaunchKernelGGL((adamw_kernel<SCALED(), GUARD()>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, lr,
+                           beta1, beta2, eps, weight_decay, a.bc1, a.bc2_sqrt, a.live, coef);
+    }, coef != nullptr, guard);
     LAUNCH_CHECK();
     return 0;
 }
 
 int segmm_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                 float eps, float weight_decay, int step, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw: pointer/alignment");
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    if (n <= 0) return 0;
-    return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, (hipStream_t)stream);
+    SEGMM_TRY(ptrs16("adamw", {p, g, m, v}));
+    return adamw_flat("adamw", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, stream, false);
 }
 
 int segmm_adamw_scaled(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_scaled: pointer/alignment");
+    SEGMM_TRY(ptrs16("adamw_scaled", {p, g, m, v}));
     SEGMM_REQUIRE(coef, "adamw_scaled: null coef (use segmm_adamw for an unscaled step)");
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_scaled: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_scaled: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    if (n <= 0) return 0;
-    return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream);
+    return adamw_flat("adamw_scaled", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, stream, false);
 }
-
-// the guarded entry points read the verdict in the LIVE step state: refused by value
-#define SEGMM_GUARD_LIVE(who) SEGMM_REQUIRE(step == -1, who ": step=%d (the guarded form reads the live device-side step state: step == -1)", step)
 
 int segmm_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_guarded: pointer/alignment");
+    SEGMM_TRY(ptrs16("adamw_guarded", {p, g, m, v}));
     SEGMM_GUARD_LIVE("adamw_guarded");
-    if (n <= 0) return 0;
-    return adamw_flat(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, (hipStream_t)stream, true);
+    return adamw_flat("adamw_guarded", p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, coef, stream, true);
 }
 
-// segmm_adamw_table / segmm_adamw_table_scaled / segmm_adamw_table_lrs: one body (`who`: the entry point's name in the messages)
+// segmm_adamw_table / _scaled / _lrs / _lrs_guarded: one body
 static int adamw_table_impl(const char* who, float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                             uint32_t* flags, float lr, float lr_scale, float beta1, float beta2, float eps, float weight_decay, int step, int phase,
                             const float* coef, segmm_stream_t stream, bool guard = false) {
-    SEGMM_REQUIRE(p && m && v && flags && (ids || n_ids == 0) && aligned16(p) && aligned16(m) && aligned16(v), "%s: pointer/alignment", who);
+    SEGMM_TRY(ptrs16(who, {p, m, v}));
+    SEGMM_REQUIRE(flags && (ids || n_ids == 0), "%s: pointer/alignment", who);
     SEGMM_REQUIRE(phase == 0 || (phase == 1 && g && aligned16(g)), "%s: phase %d (0: rows without a gradient, 1: the listed rows; needs g)", who, phase);
     SEGMM_REQUIRE(!coef || phase == 1, "%s: a scaled update is phase 1 only (phase 0 has g = 0)", who);
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0, "%s: width %% 4, sizes", who);
-    SEGMM_REQUIRE(step >= 1 || step == -1, "%s: step=%d (>= 1, or -1: the device-side step state)", who, step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "%s: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", who, (double)lr);
-    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "%s: lr_scale=%g (finite, >= 0)", who, (double)lr_scale);
+    SEGMM_TRY(table_shape_check(who, width, n_rows, n_ids, nullptr));
+    StepArgs a;
+    SEGMM_TRY(step_args(who, lr, beta1, beta2, step, &a));
+    SEGMM_TRY(lr_scale_check(who, lr_scale));
     if (n_rows == 0) return 0;
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     hipStream_t s = (hipStream_t)stream;
     const int w4 = width / 4;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    if (guard) {          // (segmm_adamw_table_lrs_guarded: step == -1, the state is live) the launches below with the verdict read first
-        SEGMM_REQUIRE(live, "%s: no device-side step state", who);
-        if (phase == 0) {
-            if (n_ids > 0) {
-                hipLaunchKernelGGL(table_mark_guarded_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, s, (const long long*)ids, n_ids, (long long)n_rows,
-                                   flags, live);
-                LAUNCH_CHECK();
-            }
-            long long blocks = (n_rows * w4 + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(adamw_table_rest_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4,
-                               (const unsigned int*)flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, lr_scale);
-            LAUNCH_CHECK();
-            return 0;
-        }
-        if (n_ids == 0) return 0;
-        if (coef)
-            hipLaunchKernelGGL((adamw_table_rows_kernel<true, true>), dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4,
-                               (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
-        else
-            hipLaunchKernelGGL((adamw_table_rows_kernel<false, true>), dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4,
-                               (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live,
-                               (const float*)nullptr, lr_scale);
-        LAUNCH_CHECK();
-        return 0;
-    }
     if (phase == 0) {
         if (n_ids > 0) {
-            hipLaunchKernelGGL(table_mark_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, s, (const long long*)ids, n_ids, (long long)n_rows, flags);
+            with_bools([&](auto GUARD) {
+                hipLaunchKernelGGL(table_mark_kernel<GUARD()>, dim3((n_ids + 255) / 256), dim3(256), 0, s, (const long long*)ids, n_ids,
+                                   (long long)n_rows, flags, a.live);
+            }, guard);
             LAUNCH_CHECK();
         }
         long long blocks = (n_rows * w4 + 255) / 256;
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(adamw_table_rest_kernel<>, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4, (const unsigned int*)flags,
-                           lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, lr_scale);
+        with_bools([&](auto GUARD) {
+            hipLaunchKernelGGL(adamw_table_rest_kernel<GUARD()>, dim3((unsigned)blocks), dim3(256), 0, s, p, m, v, (long long)n_rows, w4,
+                               (const unsigned int*)flags, lr, beta1, beta2, eps, weight_decay, a.bc1, a.bc2_sqrt, a.live, lr_scale);
+        }, guard);
         LAUNCH_CHECK();
         return 0;
     }
     if (n_ids == 0) return 0;
-    if (coef)
-        hipLaunchKernelGGL(adamw_table_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids,
-                           n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
-    else
-        hipLaunchKernelGGL(adamw_table_rows_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4, (const long long*)ids,
-                           n_ids, flags, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), live, (const float*)nullptr, lr_scale);
+    with_bools([&](auto SCALED, auto GUARD) {
+        hipLaunchKernelGGL((adamw_table_rows_kernel<SCALED(), GUARD()>), dim3((n_ids + 3) / 4), dim3(256), 0, s, p, g, m, v, (long long)n_rows, w4,
+                           (const long long*)ids, n_ids, flags, lr, beta1, beta2, eps, weight_decay, a.bc1, a.bc2_sqrt, a.live, coef, lr_scale);
+    }, coef != nullptr, guard);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1813,7 +1828,7 @@ int segmm_adamw_table(float* p, const float* g, float* m, float* v, int64_t n_ro
 int segmm_adamw_table_scaled(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                              uint32_t* flags, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* coef,
                              segmm_stream_t stream) {
-    SEGMM_REQUIRE(g && aligned16(g), "adamw_table_scaled: pointer/alignment");
+    SEGMM_TRY(ptrs16("adamw_table_scaled", {g}));
     SEGMM_REQUIRE(coef, "adamw_table_scaled: null coef (use segmm_adamw_table for an unscaled step)");
     return adamw_table_impl("adamw_table_scaled", p, g, m, v, n_rows, width, ids, n_ids, flags, lr, 1.0f, beta1, beta2, eps, weight_decay, step, 1, coef,
                             stream);
@@ -1834,34 +1849,65 @@ int segmm_adamw_table_lrs_guarded(float* p, const float* g, float* m, float* v, 
                             phase, coef, stream, true);
 }
 
-int segmm_adamw_hist_push(float* hist, int cap, float lr, float beta1, float beta2, int step, segmm_stream_t stream) {
-    SEGMM_REQUIRE(hist && aligned16(hist) && cap >= 1, "adamw_hist_push: ring pointer/alignment, cap=%d (>= 1)", cap);
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_hist_push: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_hist_push: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    hipLaunchKernelGGL(adamw_hist_push_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamwHist*)hist, cap, step, lr, (float)bc1, (float)sqrt(bc2),
-                       live);
+// segmm_adamw_hist_push / _ema: one body (ema: the entry's fourth float is the step's EMA weight, 0 otherwise)
+static int adamw_hist_push_impl(const char* who, float* hist, int cap, float lr, float beta1, float beta2, int step, bool ema, float ema_weight,
+                                int ema_warmup, segmm_stream_t stream) {
+    SEGMM_REQUIRE(hist && aligned16(hist) && cap >= 1, "%s: ring pointer/alignment, cap=%d (>= 1)", who, cap);
+    StepArgs a;
+    SEGMM_TRY(step_args(who, lr, beta1, beta2, step, &a));
+    SEGMM_REQUIRE(!ema || (ema_weight > 0.f && ema_weight <= 1.f), "%s: ema_weight=%g (0 < weight <= 1; weight = 1 - decay)", who, (double)ema_weight);
+    with_bools([&](auto EMA) {
+        hipLaunchKernelGGL(adamw_hist_push_kernel<EMA()>, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamwHist*)hist, cap, step, lr, a.bc1, a.bc2_sqrt,
+                           ema_weight, ema_warmup ? 1 : 0, a.live);
+    }, ema);
     LAUNCH_CHECK();
     return 0;
 }
 
-// target of the two launches below: the step count itself (relative == 0, target >= 0), or the bound device step count plus
-// target (relative != 0, target 0 or -1)
-#define SEGMM_LAZY_TARGET_CHECK(who)                                                                                                     \
-    SEGMM_REQUIRE(relative ? (target == 0 || target == -1) : target >= 0,                                                                \
-                  who ": target=%d (relative=%d: >= 0 by value; 0 or -1 from the device-side step count)", target, relative)
+int segmm_adamw_hist_push(float* hist, int cap, float lr, float beta1, float beta2, int step, segmm_stream_t stream) {
+    return adamw_hist_push_impl("adamw_hist_push", hist, cap, lr, beta1, beta2, step, false, 0.f, 0, stream);
+}
+
+int segmm_adamw_hist_push_ema(float* hist, int cap, float lr, float beta1, float beta2, int step, float ema_weight, int ema_warmup,
+                              segmm_stream_t stream) {
+    return adamw_hist_push_impl("adamw_hist_push_ema", hist, cap, lr, beta1, beta2, step, true, ema_weight, ema_warmup, stream);
+}
 
 int segmm_adamw_table_stamp(const int64_t* ids, int n_ids, int64_t n_rows, int32_t* stamps, int target, int relative, segmm_stream_t stream) {
     SEGMM_REQUIRE(stamps && n_rows >= 0 && n_ids >= 0, "adamw_table_stamp: arguments");
-    SEGMM_LAZY_TARGET_CHECK("adamw_table_stamp");
+    const StepState* live;
+    SEGMM_TRY(lazy_target("adamw_table_stamp", target, relative, &live));
     const long long n = ids ? (long long)n_ids : (long long)n_rows;
     if (n == 0) return 0;
     long long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    const StepState* live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
     hipLaunchKernelGGL(table_stamp_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, n, (long long)n_rows,
                        (int*)stamps, target, live);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// segmm_adamw_table_catchup / _ema: one body (ema: with the rows' shadow, and no flags)
+static int adamw_table_catchup_impl(const char* who, float* p, float* m, float* v, float* shadow, bool ema, int64_t n_rows, int width,
+                                    const int64_t* ids, int n_ids, int32_t* stamps, uint32_t* flags, const float* hist, int cap, int target,
+                                    int relative, float lr_scale, float beta1, float beta2, float eps, float weight_decay, segmm_stream_t stream) {
+    SEGMM_TRY(ptrs16(who, {p, m, v, hist}));
+    SEGMM_REQUIRE(stamps, "%s: pointer/alignment", who);
+    SEGMM_TRY(table_shape_check(who, width, n_rows, n_ids, &cap));
+    SEGMM_REQUIRE(!flags || ids, "%s: flags mark LISTED rows (the flush, ids == NULL, takes none)", who);
+    if (ema) SEGMM_TRY(lazy_shadow_check(who, shadow, p, n_rows, width));
+    const StepState* live;
+    SEGMM_TRY(lazy_target(who, target, relative, &live));
+    SEGMM_TRY(lr_scale_check(who, lr_scale));
+    const long long n = ids ? (long long)n_ids : (long long)n_rows;
+    if (n == 0 || n_rows == 0) return 0;
+    long long blocks = (n + 3) / 4;          // one wave per row; the flush strides over a capped grid like adamw_table_rest_kernel's
+    if (blocks > 4096) blocks = 4096;
+    with_bools([&](auto EMA) {
+        hipLaunchKernelGGL(adamw_table_catchup_kernel<EMA()>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, m, v, shadow,
+                           (long long)n_rows, width, (const long long*)ids, n, (int*)stamps, (const AdamwHist*)hist, cap, target, live, lr_scale,
+                           beta1, beta2, eps, weight_decay, (unsigned int*)flags);
+    }, ema);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1869,81 +1915,71 @@ int segmm_adamw_table_stamp(const int64_t* ids, int n_ids, int64_t n_rows, int32
 int segmm_adamw_table_catchup(float* p, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids, int32_t* stamps,
                               uint32_t* flags, const float* hist, int cap, int target, int relative, float lr_scale, float beta1, float beta2,
                               float eps, float weight_decay, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && m && v && stamps && hist && aligned16(p) && aligned16(m) && aligned16(v) && aligned16(hist), "adamw_table_catchup: pointer/alignment");
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_catchup: width %% 4, sizes, cap >= 1");
-    SEGMM_REQUIRE(!flags || ids, "adamw_table_catchup: flags mark LISTED rows (the flush, ids == NULL, takes none)");
-    SEGMM_LAZY_TARGET_CHECK("adamw_table_catchup");
-    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_catchup: lr_scale=%g (finite, >= 0)", (double)lr_scale);
-    const long long n = ids ? (long long)n_ids : (long long)n_rows;
-    if (n == 0 || n_rows == 0) return 0;
-    const StepState* live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    long long blocks = (n + 3) / 4;          // one wave per row; the flush strides over a capped grid like adamw_table_rest_kernel's
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adamw_table_catchup_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, m, v, (long long)n_rows, width,
-                       (const long long*)ids, n, (int*)stamps, (unsigned int*)flags, (const AdamwHist*)hist, cap, target, live, lr_scale, beta1,
-                       beta2, eps, weight_decay);
+    return adamw_table_catchup_impl("adamw_table_catchup", p, m, v, nullptr, false, n_rows, width, ids, n_ids, stamps, flags, hist, cap, target, relative,
+                                    lr_scale, beta1, beta2, eps, weight_decay, stream);
+}
+
+int segmm_adamw_table_catchup_ema(float* p, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids, int n_ids,
+                                  int32_t* stamps, const float* hist, int cap, int target, int relative, float lr_scale, float beta1,
+                                  float beta2, float eps, float weight_decay, segmm_stream_t stream) {
+    return adamw_table_catchup_impl("adamw_table_catchup_ema", p, m, v, shadow, true, n_rows, width, ids, n_ids, stamps, nullptr, hist, cap, target,
+                                    relative, lr_scale, beta1, beta2, eps, weight_decay, stream);
+}
+
+// segmm_adamw_table_lazy_rows / _ema: one body (ema: with the rows' shadow)
+static int adamw_table_lazy_rows_impl(const char* who, float* p, const float* g, float* m, float* v, float* shadow, bool ema, int64_t n_rows,
+                                      int width, const int64_t* ids, int n_ids, int32_t* stamps, const float* hist, int cap, float lr, float lr_scale,
+                                      float beta1, float beta2, float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
+    SEGMM_TRY(ptrs16(who, {p, g, m, v, hist}));
+    SEGMM_REQUIRE(stamps && (ids || n_ids == 0), "%s: pointer/alignment", who);
+    SEGMM_TRY(table_shape_check(who, width, n_rows, n_ids, &cap));
+    if (ema) SEGMM_TRY(lazy_shadow_check(who, shadow, p, n_rows, width));
+    StepArgs a;
+    SEGMM_TRY(step_args(who, lr, beta1, beta2, step, &a));
+    SEGMM_TRY(lr_scale_check(who, lr_scale));
+    if (n_rows == 0 || n_ids == 0) return 0;
+    with_bools([&](auto SCALED, auto EMA) {
+        hipLaunchKernelGGL((adamw_table_lazy_rows_kernel<SCALED(), EMA()>), dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow,
+                           (long long)n_rows, width / 4, (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2,
+                           eps, weight_decay, a.bc1, a.bc2_sqrt, a.live, coef, lr_scale);
+    }, coef != nullptr, ema);
     LAUNCH_CHECK();
     return 0;
 }
-#undef SEGMM_LAZY_TARGET_CHECK
 
 int segmm_adamw_table_lazy_rows(float* p, const float* g, float* m, float* v, int64_t n_rows, int width, const int64_t* ids, int n_ids,
                                 int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2, float eps,
                                 float weight_decay, int step, const float* coef, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && stamps && hist && (ids || n_ids == 0) && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) &&
-                      aligned16(hist),
-                  "adamw_table_lazy_rows: pointer/alignment");
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_lazy_rows: width %% 4, sizes, cap >= 1");
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_lazy_rows: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table_lazy_rows: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_lazy_rows: lr_scale=%g (finite, >= 0)", (double)lr_scale);
-    if (n_rows == 0 || n_ids == 0) return 0;
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    const int w4 = width / 4;
-    if (coef)
-        hipLaunchKernelGGL(adamw_table_lazy_rows_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, w4,
-                           (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps, weight_decay,
-                           (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
-    else
-        hipLaunchKernelGGL(adamw_table_lazy_rows_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n_rows, w4,
-                           (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps, weight_decay,
-                           (float)bc1, (float)sqrt(bc2), live, (const float*)nullptr, lr_scale);
-    LAUNCH_CHECK();
-    return 0;
+    return adamw_table_lazy_rows_impl("adamw_table_lazy_rows", p, g, m, v, nullptr, false, n_rows, width, ids, n_ids, stamps, hist, cap, lr, lr_scale,
+                                      beta1, beta2, eps, weight_decay, step, coef, stream);
 }
 
-// segmm_adamw_groups / segmm_adamw_groups_guarded: one body (`who`: the entry point's name in the messages)
+int segmm_adamw_table_lazy_rows_ema(float* p, const float* g, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids,
+                                    int n_ids, int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
+    return adamw_table_lazy_rows_impl("adamw_table_lazy_rows_ema", p, g, m, v, shadow, true, n_rows, width, ids, n_ids, stamps, hist, cap, lr, lr_scale,
+                                      beta1, beta2, eps, weight_decay, step, coef, stream);
+}
+
+// segmm_adamw_groups / segmm_adamw_groups_guarded: one body
 static int adamw_groups_impl(const char* who, float* p, const float* g, float* m, float* v, int64_t start, int64_t n, const int64_t* seg_end,
                              const float* seg_lr_scale, const float* seg_weight_decay, const uint8_t* seg_frozen, int n_seg, float lr, float beta1,
                              float beta2, float eps, int step, const float* coef, segmm_stream_t stream, bool guard) {
-    SEGMM_REQUIRE(p && g && m && v && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "%s: pointer/alignment", who);
+    SEGMM_TRY(ptrs16(who, {p, g, m, v}));
     SEGMM_REQUIRE(seg_end && seg_lr_scale && seg_weight_decay && n_seg >= 1 && (((uintptr_t)seg_end) & 7u) == 0 &&
                   (((uintptr_t)seg_lr_scale) & 3u) == 0 && (((uintptr_t)seg_weight_decay) & 3u) == 0, "%s: segment table (n_seg=%d)", who, n_seg);
     SEGMM_REQUIRE(start >= 0 && start % 4 == 0 && n >= 0, "%s: start=%lld (>= 0, a multiple of 4), n=%lld", who, (long long)start, (long long)n);
-    SEGMM_REQUIRE(step >= 1 || step == -1, "%s: step=%d (>= 1, or -1: the device-side step state)", who, step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "%s: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", who, (double)lr);
+    StepArgs a;
+    SEGMM_TRY(step_args(who, lr, beta1, beta2, step, &a));
     if (n <= 0) return 0;
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
     long long blocks = ((n >> 2) + 255) / 256;          // the grid of segmm_adamw
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    SEGMM_REQUIRE(!guard || live, "%s: no device-side step state", who);
-#define SEGMM_ADAMW_GROUPS(SCALED, FROZEN, GUARD)                                                                                                 \
-    hipLaunchKernelGGL((adamw_groups_kernel<SCALED, FROZEN, GUARD>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,       \
-                       (long long)start, (long long)n, (const long long*)seg_end, seg_lr_scale, seg_weight_decay, (const unsigned char*)seg_frozen,   \
-                       n_seg, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), live, coef)
-    if (guard) {
-        if (coef && seg_frozen) SEGMM_ADAMW_GROUPS(true, true, true);
-        else if (coef) SEGMM_ADAMW_GROUPS(true, false, true);
-        else if (seg_frozen) SEGMM_ADAMW_GROUPS(false, true, true);
-        else SEGMM_ADAMW_GROUPS(false, false, true);
-    } else if (coef && seg_frozen) SEGMM_ADAMW_GROUPS(true, true, false);
-    else if (coef) SEGMM_ADAMW_GROUPS(true, false, false);
-    else if (seg_frozen) SEGMM_ADAMW_GROUPS(false, true, false);
-    else SEGMM_ADAMW_GROUPS(false, false, false);
-#undef SEGMM_ADAMW_GROUPS
+    with_bools([&](auto SCALED, auto FROZEN, auto GUARD) {
+        hipLaunchKernelGGL((adamw_groups_kernel<SCALED(), FROZEN(), GUARD()>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                           (long long)start, (long long)n, (const long long*)seg_end, seg_lr_scale, seg_weight_decay, (const unsigned char*)seg_frozen,
+                           n_seg, lr, beta1, beta2, eps, a.bc1, a.bc2_sqrt, a.live, coef);
+    }, coef != nullptr, seg_frozen != nullptr, guard);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1962,6 +1998,7 @@ int segmm_adamw_groups_guarded(float* p, const float* g, float* m, float* v, int
     return adamw_groups_impl("adamw_groups_guarded", p, g, m, v, start, n, seg_end, seg_lr_scale, seg_weight_decay, seg_frozen, n_seg, lr, beta1, beta2,
                              eps, step, coef, stream, true);
 }
+
 
 int segmm_grad_norm_groups(const float* g, int64_t n, const int64_t* seg_end, const uint8_t* seg_frozen, int n_seg, float max_norm, double* scratch,
                            float* out2, segmm_stream_t stream) {
@@ -2636,112 +2673,33 @@ static unsigned flat_pair_blocks(long long n4) {
     return (unsigned)(blocks > cap ? cap : blocks < 1 ? 1 : blocks);
 }
 
-int segmm_ema_update_guarded(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream) {
-    if (const int rc = flat_pair_check("ema_update_guarded", shadow, p, n)) return rc;
-    SEGMM_REQUIRE(weight > 0.f && weight <= 1.f, "ema_update_guarded: weight=%g (0 < weight <= 1; weight = 1 - decay)", (double)weight);
-    SEGMM_GUARD_LIVE("ema_update_guarded");
+// segmm_ema_update / _guarded: one body.  No rate and no moments here: of the step arguments only the step rule and the live state
+// (which the kernel reads for the warm-up's count and, guarded, for the verdict).
+static int ema_update_impl(const char* who, float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream,
+                           bool guard) {
+    SEGMM_TRY(flat_pair_check(who, shadow, p, n));
+    SEGMM_REQUIRE(weight > 0.f && weight <= 1.f, "%s: weight=%g (0 < weight <= 1; weight = 1 - decay)", who, (double)weight);
+    if (guard) SEGMM_GUARD_LIVE(who);
+    StepArgs a;
+    SEGMM_TRY(step_args(who, 0.f, 0.f, 0.f, step, &a));
     if (n == 0) return 0;
-    const StepState* live = (const StepState*)segmm_step_current();          // (read for the verdict whether or not there is a warm-up)
-    SEGMM_REQUIRE(live, "ema_update_guarded: no device-side step state");
     const long long n4 = n >> 2;
-    const int tail = (int)(n & 3);
-    if (knob(K_EMA_NT) != 0)
-        hipLaunchKernelGGL((ema_update_kernel<true, true>), dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
-    else
-        hipLaunchKernelGGL((ema_update_kernel<false, true>), dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
+    with_bools([&](auto NT, auto GUARD) {
+        hipLaunchKernelGGL((ema_update_kernel<NT(), GUARD()>), dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4,
+                           (int)(n & 3), weight, warmup ? 1 : 0, step, a.live);
+    }, knob(K_EMA_NT) != 0, guard);
     LAUNCH_CHECK();
     return 0;
+}
+
+int segmm_ema_update_guarded(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream) {
+    return ema_update_impl("ema_update_guarded", shadow, p, n, weight, warmup, step, stream, true);
 }
 
 int segmm_ema_update(float* shadow, const float* p, int64_t n, float weight, int warmup, int step, segmm_stream_t stream) {
-    if (const int rc = flat_pair_check("ema_update", shadow, p, n)) return rc;
-    SEGMM_REQUIRE(weight > 0.f && weight <= 1.f, "ema_update: weight=%g (0 < weight <= 1; weight = 1 - decay)", (double)weight);
-    SEGMM_REQUIRE(step >= 1 || step == -1, "ema_update: step=%d (>= 1, or -1: the device-side step state)", step);
-    if (n == 0) return 0;
-    const StepState* live = (warmup && step < 0) ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    SEGMM_REQUIRE(!(warmup && step < 0) || live, "ema_update: no device-side step state");
-    const long long n4 = n >> 2;
-    const int tail = (int)(n & 3);
-    if (knob(K_EMA_NT) != 0)
-        hipLaunchKernelGGL(ema_update_kernel<true>, dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
-    else
-        hipLaunchKernelGGL(ema_update_kernel<false>, dim3(flat_pair_blocks(n4)), dim3(256), 0, (hipStream_t)stream, shadow, p, n4, tail, weight, warmup ? 1 : 0, step, live);
-    LAUNCH_CHECK();
-    return 0;
+    return ema_update_impl("ema_update", shadow, p, n, weight, warmup, step, stream, false);
 }
 
-// ---- lazy exact AdamW with the EMA shadow replayed beside it (rowops.h; the checks of the three entry points they extend)
-int segmm_adamw_hist_push_ema(float* hist, int cap, float lr, float beta1, float beta2, int step, float ema_weight, int ema_warmup,
-                              segmm_stream_t stream) {
-    SEGMM_REQUIRE(hist && aligned16(hist) && cap >= 1, "adamw_hist_push_ema: ring pointer/alignment, cap=%d (>= 1)", cap);
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_hist_push_ema: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_hist_push_ema: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    SEGMM_REQUIRE(ema_weight > 0.f && ema_weight <= 1.f, "adamw_hist_push_ema: ema_weight=%g (0 < weight <= 1; weight = 1 - decay)", (double)ema_weight);
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    SEGMM_REQUIRE(step > 0 || live, "adamw_hist_push_ema: no device-side step state");
-    hipLaunchKernelGGL(adamw_hist_push_ema_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamwHist*)hist, cap, step, lr, (float)bc1, (float)sqrt(bc2),
-                       ema_weight, ema_warmup ? 1 : 0, live);
-    LAUNCH_CHECK();
-    return 0;
-}
-
-// the shadow of a lazy table: 16-byte aligned and disjoint from the n_rows x width floats at p
-static int lazy_shadow_check(const char* who, const float* shadow, const float* p, int64_t n_rows, int width) {
-    SEGMM_REQUIRE(shadow && aligned16(shadow), "%s: shadow pointer/alignment", who);
-    const uintptr_t nb = (uintptr_t)n_rows * (uintptr_t)width * 4u, ps = (uintptr_t)shadow, pp = (uintptr_t)p;
-    SEGMM_REQUIRE(ps + nb <= pp || pp + nb <= ps, "%s: shadow overlaps p (they must be disjoint)", who);
-    return 0;
-}
-
-int segmm_adamw_table_catchup_ema(float* p, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids, int n_ids,
-                                  int32_t* stamps, const float* hist, int cap, int target, int relative, float lr_scale, float beta1,
-                                  float beta2, float eps, float weight_decay, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && m && v && stamps && hist && aligned16(p) && aligned16(m) && aligned16(v) && aligned16(hist),
-                  "adamw_table_catchup_ema: pointer/alignment");
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_catchup_ema: width %% 4, sizes, cap >= 1");
-    if (const int rc = lazy_shadow_check("adamw_table_catchup_ema", shadow, p, n_rows, width)) return rc;
-    SEGMM_REQUIRE(relative ? (target == 0 || target == -1) : target >= 0,
-                  "adamw_table_catchup_ema: target=%d (relative=%d: >= 0 by value; 0 or -1 from the device-side step count)", target, relative);
-    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_catchup_ema: lr_scale=%g (finite, >= 0)", (double)lr_scale);
-    const long long n = ids ? (long long)n_ids : (long long)n_rows;
-    if (n == 0 || n_rows == 0) return 0;
-    const StepState* live = relative ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    long long blocks = (n + 3) / 4;          // one wave per row; the flush strides over a capped grid, as segmm_adamw_table_catchup's
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adamw_table_catchup_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, m, v, shadow, (long long)n_rows,
-                       width, (const long long*)ids, n, (int*)stamps, (const AdamwHist*)hist, cap, target, live, lr_scale, beta1, beta2, eps,
-                       weight_decay);
-    LAUNCH_CHECK();
-    return 0;
-}
-
-int segmm_adamw_table_lazy_rows_ema(float* p, const float* g, float* m, float* v, float* shadow, int64_t n_rows, int width, const int64_t* ids,
-                                    int n_ids, int32_t* stamps, const float* hist, int cap, float lr, float lr_scale, float beta1, float beta2,
-                                    float eps, float weight_decay, int step, const float* coef, segmm_stream_t stream) {
-    SEGMM_REQUIRE(p && g && m && v && stamps && hist && (ids || n_ids == 0) && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) &&
-                      aligned16(hist),
-                  "adamw_table_lazy_rows_ema: pointer/alignment");
-    SEGMM_REQUIRE(width > 0 && width % 4 == 0 && n_rows >= 0 && n_ids >= 0 && cap >= 1, "adamw_table_lazy_rows_ema: width %% 4, sizes, cap >= 1");
-    if (const int rc = lazy_shadow_check("adamw_table_lazy_rows_ema", shadow, p, n_rows, width)) return rc;
-    SEGMM_REQUIRE(step >= 1 || step == -1, "adamw_table_lazy_rows_ema: step=%d (>= 1, or -1: the device-side step state)", step);
-    SEGMM_REQUIRE(!(lr < 0.f) || step == -1, "adamw_table_lazy_rows_ema: lr=%g < 0 (SEGMM_LIVE_LR: the device-side rate) needs step == -1", (double)lr);
-    SEGMM_REQUIRE(lr_scale >= 0.f && !__builtin_isinf(lr_scale), "adamw_table_lazy_rows_ema: lr_scale=%g (finite, >= 0)", (double)lr_scale);
-    if (n_rows == 0 || n_ids == 0) return 0;
-    const double bc1 = step > 0 ? 1.0 - pow((double)beta1, step) : 1.0, bc2 = step > 0 ? 1.0 - pow((double)beta2, step) : 1.0;
-    const StepState* live = step < 0 ? (const StepState*)segmm_step_current() : (const StepState*)nullptr;
-    const int w4 = width / 4;
-    if (coef)
-        hipLaunchKernelGGL(adamw_table_lazy_rows_ema_kernel<true>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow,
-                           (long long)n_rows, w4, (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps,
-                           weight_decay, (float)bc1, (float)sqrt(bc2), live, coef, lr_scale);
-    else
-        hipLaunchKernelGGL(adamw_table_lazy_rows_ema_kernel<false>, dim3((n_ids + 3) / 4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow,
-                           (long long)n_rows, w4, (const long long*)ids, n_ids, (int*)stamps, (const AdamwHist*)hist, cap, step, lr, beta1, beta2, eps,
-                           weight_decay, (float)bc1, (float)sqrt(bc2), live, (const float*)nullptr, lr_scale);
-    LAUNCH_CHECK();
-    return 0;
-}
 
 int segmm_vec_swap(float* a, float* b, int64_t n, segmm_stream_t stream) {
     if (const int rc = flat_pair_check("vec_swap", a, b, n)) return rc;

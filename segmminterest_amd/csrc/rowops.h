@@ -929,6 +929,22 @@ __device__ __forceinline__ f32x4 adamw_grad4(f32x4 gg, const float* coef) {
     if constexpr (SCALED) { const float c = *coef; gg *= c; }
     return gg;
 }
+// The scalars of one step, stated once for every kernel of the family: the by-value arguments, or with `live` the bias corrections
+// and the count of the device-side step state, and for lr < 0 (SEGMM_LIVE_LR) the scheduled rate of that step as well.  A kernel
+// that has no use for the count passes 0 and never reads it (the load is dead).
+struct StepScalars { float lr, bc1, bc2_sqrt; int t; };
+__device__ __forceinline__ StepScalars step_scalars(float lr, float bc1, float bc2_sqrt, int t, const StepState* live) {
+    if (live) { t = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    return {lr, bc1, bc2_sqrt, t};
+}
+// the rate fp32(lr * lr_scale) and the step fp32(rate / bc1), in this order and with these two roundings everywhere (lr_scale = 1
+// leaves every bit of lr as it is: adamw_kernel passes the literal, and the multiply folds away)
+struct StepRate { float lr, step; };
+__device__ __forceinline__ StepRate step_rate(float lr, float lr_scale, float bc1) {
+#pragma clang fp contract(off)
+    lr = lr * lr_scale;
+    return {lr, lr / bc1};
+}
 // ---------------------------------------------------------------- fused AdamW over a flat range (a13 / K9)
 // torch.optim.AdamW single-tensor update order (decoupled decay first), bias corrections passed in.
 // SCALED: the gradient is multiplied by *coef first (segmm_adamw_scaled: the clip coefficient segmm_grad_norm wrote)
@@ -941,22 +957,21 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                              float* __restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
                              float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
     if constexpr (GUARD) { if (step_skipped(live)) return; }
-    // bias corrections of the device-side step count; lr < 0 (SEGMM_LIVE_LR): the scheduled rate of that step as well
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    const StepScalars sc = step_scalars(lr, bc1, bc2_sqrt, 0, live);
     const long long n4 = n >> 2;
-    const float step = lr / bc1;
+    const StepRate r = step_rate(sc.lr, 1.0f, sc.bc1);
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         f32x4 pp = ((f32x4*)p)[i];
         const f32x4 gg = adamw_grad4<SCALED>(((const f32x4*)g)[i], coef);
         f32x4 mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        adamw_elem4(pp, gg, mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, gg, mm, vv, r.lr, b1, b2, eps, wd, r.step, sc.bc2_sqrt);
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
     }
     // tail (n % 4)
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const long long i = (n4 << 2) + threadIdx.x;
         f32x4 pp = {p[i], 0.f, 0.f, 0.f}, mm = {m[i], 0.f, 0.f, 0.f}, vv = {v[i], 0.f, 0.f, 0.f};
-        adamw_elem4(pp, adamw_grad4<SCALED>(f32x4{g[i], 0.f, 0.f, 0.f}, coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, adamw_grad4<SCALED>(f32x4{g[i], 0.f, 0.f, 0.f}, coef), mm, vv, r.lr, b1, b2, eps, wd, r.step, sc.bc2_sqrt);
         p[i] = pp.x; m[i] = mm.x; v[i] = vv.x;
     }
 }
@@ -993,7 +1008,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
                              float bc1, float bc2_sqrt, const StepState* live, const float* __restrict__ coef) {
 #pragma clang fp contract(off)
     if constexpr (GUARD) { if (step_skipped(live)) return; }
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
+    const StepScalars st = step_scalars(lr, bc1, bc2_sqrt, 0, live);
     const long long n4 = n >> 2;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -1019,12 +1034,11 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
             sc = seg_lr_scale[ls]; wd = seg_wd[ls];
         }
         if (i >= n4 || fz) continue;
-        const float lr_s = lr * sc;
-        const float step = lr_s / bc1;
+        const StepRate r = step_rate(st.lr, sc, st.bc1);
         f32x4 pp = p4[i];
         const f32x4 gg = adamw_grad4<SCALED>(g4[i], coef);
         f32x4 mm = m4[i], vv = v4[i];
-        adamw_elem4(pp, gg, mm, vv, lr_s, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, gg, mm, vv, r.lr, b1, b2, eps, wd, r.step, st.bc2_sqrt);
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
     // tail (n % 4): the last segment the range touches
@@ -1032,10 +1046,9 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
         const long long i = start + (n4 << 2) + threadIdx.x;
         const int ls = seg_find(seg_end, n_seg, 0, start + n - 1);
         if (!FROZEN || !seg_frozen[ls]) {
-            const float lr_s = lr * seg_lr_scale[ls];
-            const float step = lr_s / bc1;
+            const StepRate r = step_rate(st.lr, seg_lr_scale[ls], st.bc1);
             f32x4 pp = {p[i], 0.f, 0.f, 0.f}, mm = {m[i], 0.f, 0.f, 0.f}, vv = {v[i], 0.f, 0.f, 0.f};
-            adamw_elem4(pp, adamw_grad4<SCALED>(f32x4{g[i], 0.f, 0.f, 0.f}, coef), mm, vv, lr_s, b1, b2, eps, seg_wd[ls], step, bc2_sqrt);
+            adamw_elem4(pp, adamw_grad4<SCALED>(f32x4{g[i], 0.f, 0.f, 0.f}, coef), mm, vv, r.lr, b1, b2, eps, seg_wd[ls], r.step, st.bc2_sqrt);
             p[i] = pp.x; m[i] = mm.x; v[i] = vv.x;
         }
     }
@@ -1044,17 +1057,11 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
 // AdamW of an id-embedding table in two passes (segmm_adamw_table): the arithmetic of adamw_kernel, element for element
 // (lr_scale: the rate is fp32(lr * lr_scale), lr being the argument or the device state's -- segmm_adamw_table_lrs; 1 elsewhere,
 // which leaves every bit of lr as it is)
-__global__ __launch_bounds__(256) void table_mark_kernel(const long long* __restrict__ ids, int n, long long n_rows, unsigned int* __restrict__ flags) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) {
-        const long long id = ids[k];
-        if (id >= 0 && id < n_rows) flags[id] = 1u;
-    }
-}
-// the same under the guard: a skipped step marks nothing (its phase 1 returns as well and would leave the marks standing)
-__global__ __launch_bounds__(256) void table_mark_guarded_kernel(const long long* __restrict__ ids, int n, long long n_rows, unsigned int* __restrict__ flags,
-                                                                 const StepState* live) {
-    if (step_skipped(live)) return;
+// (GUARD: a skipped step marks nothing -- its phase 1 returns as well and would leave the marks standing)
+template <bool GUARD = false>
+__global__ __launch_bounds__(256) void table_mark_kernel(const long long* __restrict__ ids, int n, long long n_rows, unsigned int* __restrict__ flags,
+                                                         const StepState* live) {
+    if constexpr (GUARD) { if (step_skipped(live)) return; }
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) {
         const long long id = ids[k];
@@ -1069,15 +1076,14 @@ __global__ __launch_bounds__(256) void adamw_table_rest_kernel(float* __restrict
                                                                float lr_scale) {
 #pragma clang fp contract(off)
     if constexpr (GUARD) { if (step_skipped(live)) return; }
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
-    lr = lr * lr_scale;
-    const float step = lr / bc1;
+    const StepScalars sc = step_scalars(lr, bc1, bc2_sqrt, 0, live);
+    const StepRate r = step_rate(sc.lr, lr_scale, sc.bc1);
     const long long n4 = n_rows * w4;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         if (flags[i / w4] != 0u) continue;
         f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        adamw_elem4(pp, zero, mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, zero, mm, vv, r.lr, b1, b2, eps, wd, r.step, sc.bc2_sqrt);
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
     }
 }
@@ -1090,9 +1096,8 @@ __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict
                                                                const float* __restrict__ coef, float lr_scale) {
 #pragma clang fp contract(off)
     if constexpr (GUARD) { if (step_skipped(live)) return; }
-    if (live) { bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
-    lr = lr * lr_scale;
-    const float step = lr / bc1;
+    const StepScalars sc = step_scalars(lr, bc1, bc2_sqrt, 0, live);
+    const StepRate r = step_rate(sc.lr, lr_scale, sc.bc1);
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (k >= n_ids) return;
@@ -1105,117 +1110,7 @@ __global__ __launch_bounds__(256) void adamw_table_rows_kernel(float* __restrict
     for (int c = lane; c < w4; c += 64) {
         const long long i = id * w4 + c;
         f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        adamw_elem4(pp, adamw_grad4<SCALED>(((const f32x4*)g)[i], coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
-        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
-    }
-}
-
-// ---------------------------------------------------------------- lazy exact AdamW of an id table (segmm_adamw_table_catchup)
-// A row without a gradient takes a step that depends on nothing but its own (p, m, v) and the step's scalars, so the step can be
-// taken LATER, in order, with the same fp32 operations: bit for bit adamw_table_rest_kernel's update of that row.  Each row carries
-// a stamp (int32: the optimizer steps already applied to it); the scalars of step t that move from step to step -- the rate
-// before lr_scale, bc1, bc2_sqrt -- sit in slot t % cap of a device ring, one 16-byte entry per step (hist_push_kernel).
-struct AdamwHist { float lr, bc1, bc2_sqrt, pad_; };
-__global__ void adamw_hist_push_kernel(AdamwHist* __restrict__ hist, int cap, int t, float lr, float bc1, float bc2_sqrt, const StepState* live) {
-    if (live) { t = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
-    if (t < 0) return;          // (a step state that was never set)
-    hist[t % cap] =AdamwHist{lr, bc1, bc2_sqrt, 0.f};
-}
-// the stamps of the listed rows become at least `target` (the rows phase 1 has just stepped); ids == NULL: every stamp IS target
-__global__ __launch_bounds__(256) void table_stamp_kernel(const long long* __restrict__ ids, long long n, long long n_rows, int* __restrict__ stamps,
-                                                          int target, const StepState* live) {
-    if (live) target += live->step;
-    for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
-        if (!ids) { stamps[k] = target; continue; }
-        const long long id = ids[k];
-        if (id >= 0 && id < n_rows) atomicMax(stamps + id, target);
-    }
-}
-// Rows behind `target` replay their missed steps stamp + 1 .. target with g = 0 from the ring and are written once.  One wave per
-// row, four rows per workgroup, four floats per lane (adamw_table_rows_kernel's shape); lane 0 claims the row with an atomic max of
-// its stamp: a second list entry with the same id, or a row already at target, finds old >= target and leaves the row alone (no
-// load, no store).  ids == NULL: the rows 0 .. n_items - 1 themselves (the flush; the grid is capped and strides).  flags != NULL:
-// every valid listed row is marked for phase 1 of segmm_adamw_table, which the lazy step runs without a phase 0.  target - stamp
-// <= cap is the caller's rule (a slot is overwritten cap steps later).  The replay is a dependent chain of sqrt and divide per
-// element and step; four independent elements per lane keep the VALU busy from one wave: a whole workgroup per row with one float
-// per thread (four waves per row at width 256) measured 2.7-2.9x SLOWER per row-step at every gap from 32 to 1024 and 3.9x in the
-// flush (profiles/lazy_tables/), and was dropped.
-__global__ __launch_bounds__(256) void adamw_table_catchup_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long n_rows,
-                                                                  int width, const long long* __restrict__ ids, long long n_items,
-                                                                  int* __restrict__ stamps, unsigned int* __restrict__ flags,
-                                                                  const AdamwHist* __restrict__ hist, int cap, int target, const StepState* live,
-                                                                  float lr_scale, float b1, float b2, float eps, float wd) {
-#pragma clang fp contract(off)
-    if (live) target += live->step;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int w4 = width >> 2;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (long long k = blockIdx.x * 4LL + wave; k < n_items; k += gridDim.x * 4LL) {
-        const long long id = ids ? ids[k] : k;
-        int old = target;
-        if (lane == 0 && id >= 0 && id < n_rows) {
-            old = atomicMax(stamps + id, target);
-            if (flags) flags[id] = 1u;
-        }
-        old = __builtin_amdgcn_readfirstlane(old);
-        if (old >= target) continue;
-        for (int c = lane; c < w4; c += 64) {
-            const long long i = id * w4 + c;
-            f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-            int slot = (int)((unsigned)(old + 1) % (unsigned)cap);          // (a stamp is never negative; whatever it holds, the slot is in the ring)
-            for (int s = old + 1; s <= target; ++s) {
-                const AdamwHist h = hist[slot];
-                slot = slot + 1 == cap ? 0 : slot + 1;
-                const float lr = h.lr * lr_scale;
-                const float step = lr / h.bc1;
-                adamw_elem4(pp, zero, mm, vv, lr, b1, b2, eps, wd, step, h.bc2_sqrt);
-            }
-            ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
-        }
-    }
-}
-// The data-parallel tail of a lazy step (segmm_adamw_table_lazy_rows): the listed rows -- those of ALL ranks, known only after the
-// row exchange -- replay the g = 0 steps old + 1 .. T - 1 from the ring (adamw_table_catchup_kernel's loop) and then take step T
-// with their gradient row and step T's own scalars (adamw_table_rows_kernel's: lr = lr * lr_scale, step = lr / bc1), in one pass
-// over the row: p, m, v are read once and written once, where catch-up + phase 1 + stamp read and write them twice in three
-// launches on the exposed end of the step.  The same shape, one wave per list entry and four floats per lane; the claim is the
-// atomic max of the stamp with T itself, so no flags are involved: a duplicate entry, or a row already at T, finds old >= T and
-// is neither loaded nor stored.  The gradient vector is loaded ahead of the replay: nothing needs it before the dependent sqrt /
-// divide chain of the replayed steps has run, which hides its latency (at a gap of 0 it travels with p, m, v in one round).
-template <bool SCALED>
-__global__ __launch_bounds__(256) void adamw_table_lazy_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                    float* __restrict__ v, long long n_rows, int w4,
-                                                                    const long long* __restrict__ ids, int n_ids, int* __restrict__ stamps,
-                                                                    const AdamwHist* __restrict__ hist, int cap, int T, float lr, float b1, float b2,
-                                                                    float eps, float wd, float bc1, float bc2_sqrt, const StepState* live,
-                                                                    const float* __restrict__ coef, float lr_scale) {
-#pragma clang fp contract(off)
-    if (live) { T = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
-    lr = lr * lr_scale;
-    const float step = lr / bc1;
-    const int lane = threadIdx.x & 63;
-    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (k >= n_ids) return;
-    const long long id = ids[k];
-    if (id < 0 || id >= n_rows) return;
-    int old = T;
-    if (lane == 0) old = atomicMax(stamps + id, T);
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (old >= T) return;          // another entry of the list holds the same id and has taken the row, or the row was stepped already
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (int c = lane; c < w4; c += 64) {
-        const long long i = id * w4 + c;
-        const f32x4 graw = ((const f32x4*)g)[i];
-        f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-        int slot = (int)((unsigned)(old + 1) % (unsigned)cap);          // (as in the catch-up: whatever the stamp holds, the slot is in the ring)
-        for (int s = old + 1; s < T; ++s) {
-            const AdamwHist h = hist[slot];
-            slot = slot + 1 == cap ? 0 : slot + 1;
-            const float lr_s = h.lr * lr_scale;
-            const float step_s = lr_s / h.bc1;
-            adamw_elem4(pp, zero, mm, vv, lr_s, b1, b2, eps, wd, step_s, h.bc2_sqrt);
-        }
-        adamw_elem4(pp, adamw_grad4<SCALED>(graw, coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
+        adamw_elem4(pp, adamw_grad4<SCALED>(((const f32x4*)g)[i], coef), mm, vv, r.lr, b1, b2, eps, wd, r.step, sc.bc2_sqrt);
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
     }
 }
@@ -1427,95 +1322,136 @@ __global__ __launch_bounds__(256, VEC_ADD_WG_PER_CU) void ema_update_kernel(floa
     }
 }
 
-// ---------------------------------------------------------------- lazy exact AdamW with the EMA shadow replayed beside it
-// (segmm_adamw_hist_push_ema, segmm_adamw_table_catchup_ema, segmm_adamw_table_lazy_rows_ema).  What holds for a row's (p, m, v)
-// holds for its shadow: shadow_t = shadow_{t-1} + (p_t - shadow_{t-1}) w_t depends on the row's own p_t and on the step's weight
-// only, so a row that replays its missed steps replays its shadow with them, in order, with ema_lerp's three rounded operations:
-// after a flush the shadow holds the bits ema_update_kernel leaves when it runs over the dense table every step.  w_t sits in the
-// fourth float of the ring's entry of step t -- the weight that step actually used, so the EMA's decay may move between steps.
-// The kernels are the two above with a fourth vector per lane (one wave per list entry, four floats per lane, four rows per
-// workgroup); the shadow's lerp does not feed the next AdamW step, so it is independent work beside the dependent sqrt / divide
-// chain.  The old kernels are untouched: the loops are stated again here.
-__global__ void adamw_hist_push_ema_kernel(AdamwHist* __restrict__ hist, int cap, int t, float lr, float bc1, float bc2_sqrt, float weight, int warmup,
-                                           const StepState* live) {
-    const float w = ema_weight(weight, warmup, t, live);          // (ema_update_kernel's call: t by value, or the state's count)
-    if (live) { t = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
-    if (t < 0) return;          // (a step state that was never set)
-    hist[t % cap] = AdamwHist{lr, bc1, bc2_sqrt, w};
+// ---------------------------------------------------------------- lazy exact AdamW of an id table (segmm_adamw_table_catchup)
+// A row without a gradient takes a step that depends on nothing but its own (p, m, v) and the step's scalars, so the step can be
+// taken LATER, in order, with the same fp32 operations: bit for bit adamw_table_rest_kernel's update of that row.  Each row carries
+// a stamp (int32: the optimizer steps already applied to it); the scalars of step t that move from step to step -- the rate
+// before lr_scale, bc1, bc2_sqrt -- sit in slot t % cap of a device ring, one 16-byte entry per step (adamw_hist_push_kernel).
+// With the EMA shadow replayed beside the row (EMA = true: segmm_adamw_hist_push_ema, segmm_adamw_table_catchup_ema,
+// segmm_adamw_table_lazy_rows_ema): what holds for a row's (p, m, v) holds for its shadow.  shadow_t = shadow_{t-1} +
+// (p_t - shadow_{t-1}) w_t depends on the row's own p_t and on the step's weight only, so a row that replays its missed steps
+// replays its shadow with them, in order, with ema_lerp's three rounded operations: after a flush the shadow holds the bits
+// ema_update_kernel leaves when it runs over the dense table every step.  w_t sits in the fourth float of the ring's entry of
+// step t -- the weight that step actually used, so the EMA's decay may move between steps (0 where no EMA is kept).  The shadow is
+// a fourth vector per lane; its lerp does not feed the next AdamW step, so it is independent work beside the dependent sqrt /
+// divide chain.
+struct AdamwHist { float lr, bc1, bc2_sqrt, ema_w; };
+template <bool EMA>
+__global__ void adamw_hist_push_kernel(AdamwHist* __restrict__ hist, int cap, int t, float lr, float bc1, float bc2_sqrt, float weight, int warmup,
+                                       const StepState* live) {
+    float w = 0.f;
+    if constexpr (EMA) w = ema_weight(weight, warmup, t, live);          // (ema_update_kernel's call: t by value, or the state's count)
+    const StepScalars sc = step_scalars(lr, bc1, bc2_sqrt, t, live);
+    if (sc.t < 0) return;          // (a step state that was never set)
+    hist[sc.t % cap] = AdamwHist{sc.lr, sc.bc1, sc.bc2_sqrt, w};
 }
-// adamw_table_catchup_kernel without flags, plus the shadow: per replayed step s the AdamW step with g = 0, then the lerp with w_s
-__global__ __launch_bounds__(256) void adamw_table_catchup_ema_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                                      float* __restrict__ shadow, long long n_rows, int width,
-                                                                      const long long* __restrict__ ids, long long n_items, int* __restrict__ stamps,
-                                                                      const AdamwHist* __restrict__ hist, int cap, int target, const StepState* live,
-                                                                      float lr_scale, float b1, float b2, float eps, float wd) {
+// the stamps of the listed rows become at least `target` (the rows phase 1 has just stepped); ids == NULL: every stamp IS target
+__global__ __launch_bounds__(256) void table_stamp_kernel(const long long* __restrict__ ids, long long n, long long n_rows, int* __restrict__ stamps,
+                                                          int target, const StepState* live) {
+    if (live) target += live->step;
+    for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
+        if (!ids) { stamps[k] = target; continue; }
+        const long long id = ids[k];
+        if (id >= 0 && id < n_rows) atomicMax(stamps + id, target);
+    }
+}
+// The g = 0 steps from .. end - 1 of this lane's four elements, from the ring: per step the AdamW step with that step's scalars, then
+// (EMA) the shadow's lerp with that step's weight.  Whatever `from` holds, the slot is in the ring (a stamp is never negative).
+template <bool EMA>
+__device__ __forceinline__ void adamw_replay4(f32x4& pp, f32x4& mm, f32x4& vv, f32x4& ss, const AdamwHist* __restrict__ hist, int cap, int from,
+                                              int end, float lr_scale, float b1, float b2, float eps, float wd) {
 #pragma clang fp contract(off)
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    int slot = (int)((unsigned)from % (unsigned)cap);
+    for (int s = from; s < end; ++s) {
+        const AdamwHist h = hist[slot];
+        slot = slot + 1 == cap ? 0 : slot + 1;
+        const StepRate r = step_rate(h.lr, lr_scale, h.bc1);
+        adamw_elem4(pp, zero, mm, vv, r.lr, b1, b2, eps, wd, r.step, h.bc2_sqrt);
+        if constexpr (EMA) ss = ema_lerp(ss, pp, h.ema_w);
+    }
+}
+// The row claim of the row-per-wave kernels below: lane 0 raises the row's stamp to `target` with an atomic max and the wave learns
+// what the stamp was.  A second list entry with the same id, or a row already at target, finds old >= target and leaves the row
+// alone (no load, no store); so does a wave whose id is outside the table (valid = false: nothing is touched, old = target).
+__device__ __forceinline__ int row_claim(int* __restrict__ stamps, long long id, int target, bool valid, int lane) {
+    int old = target;
+    if (lane == 0 && valid) old = atomicMax(stamps + id, target);
+    return __builtin_amdgcn_readfirstlane(old);
+}
+// Rows behind `target` replay their missed steps stamp + 1 .. target with g = 0 from the ring and are written once.  One wave per
+// row, four rows per workgroup, four floats per lane (adamw_table_rows_kernel's shape).  ids == NULL: the rows 0 .. n_items - 1
+// themselves (the flush; the grid is capped and strides).  flags != NULL (EMA = false only; the EMA form takes none and compiles
+// them out): every valid listed row is marked for phase 1 of segmm_adamw_table, which the lazy step runs without a phase 0.
+// target - stamp <= cap is the caller's rule (a slot is overwritten cap steps later).  The replay is a dependent chain of sqrt and
+// divide per element and step; four independent elements per lane keep the VALU busy from one wave: a whole workgroup per row with
+// one float per thread (four waves per row at width 256) measured 2.7-2.9x SLOWER per row-step at every gap from 32 to 1024 and
+// 3.9x in the flush (profiles/lazy_tables/), and was dropped.
+// (`flags` stays the LAST argument: ahead of `hist` it moved the kernel arguments of the EMA form, which never reads it, and that
+// form compiled to 65 VGPRs instead of 50 -- one occupancy step down; profiles/adamw_once/kernel_resources.txt)
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_table_catchup_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                                  float* __restrict__ shadow, long long n_rows, int width,
+                                                                  const long long* __restrict__ ids, long long n_items, int* __restrict__ stamps,
+                                                                  const AdamwHist* __restrict__ hist, int cap, int target, const StepState* live,
+                                                                  float lr_scale, float b1, float b2, float eps, float wd,
+                                                                  unsigned int* __restrict__ flags) {
     if (live) target += live->step;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int w4 = width >> 2;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     for (long long k = blockIdx.x * 4LL + wave; k < n_items; k += gridDim.x * 4LL) {
         const long long id = ids ? ids[k] : k;
-        int old = target;
-        if (lane == 0 && id >= 0 && id < n_rows) old = atomicMax(stamps + id, target);
-        old = __builtin_amdgcn_readfirstlane(old);
+        const bool valid = id >= 0 && id < n_rows;
+        if constexpr (!EMA) { if (lane == 0 && valid && flags) flags[id] = 1u; }
+        const int old = row_claim(stamps, id, target, valid, lane);
         if (old >= target) continue;
         for (int c = lane; c < w4; c += 64) {
             const long long i = id * w4 + c;
-            f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], ss = ((f32x4*)shadow)[i];
-            int slot = (int)((unsigned)(old + 1) % (unsigned)cap);          // (whatever the stamp holds, the slot is in the ring)
-            for (int s = old + 1; s <= target; ++s) {
-                const AdamwHist h = hist[slot];
-                slot = slot + 1 == cap ? 0 : slot + 1;
-                const float lr = h.lr * lr_scale;
-                const float step = lr / h.bc1;
-                adamw_elem4(pp, zero, mm, vv, lr, b1, b2, eps, wd, step, h.bc2_sqrt);
-                ss = ema_lerp(ss, pp, h.pad_);
-            }
-            ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv; ((f32x4*)shadow)[i] = ss;
+            f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], ss = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (EMA) ss = ((f32x4*)shadow)[i];
+            adamw_replay4<EMA>(pp, mm, vv, ss, hist, cap, old + 1, target + 1, lr_scale, b1, b2, eps, wd);
+            ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+            if constexpr (EMA) ((f32x4*)shadow)[i] = ss;
         }
     }
 }
-// adamw_table_lazy_rows_kernel plus the shadow: the replay as above, step T with the gradient row, then the lerp with w_T -- read
-// from the ring's entry of T, which adamw_hist_push_ema_kernel wrote on this stream ahead of this launch
-template <bool SCALED>
-__global__ __launch_bounds__(256) void adamw_table_lazy_rows_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                        float* __restrict__ v, float* __restrict__ shadow, long long n_rows, int w4,
-                                                                        const long long* __restrict__ ids, int n_ids, int* __restrict__ stamps,
-                                                                        const AdamwHist* __restrict__ hist, int cap, int T, float lr, float b1,
-                                                                        float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                                        const StepState* live, const float* __restrict__ coef, float lr_scale) {
-#pragma clang fp contract(off)
-    if (live) { T = live->step; bc1 = live->bc1; bc2_sqrt = live->bc2_sqrt; if (lr < 0.f) lr = live->lr; }
-    lr = lr * lr_scale;
-    const float step = lr / bc1;
+// The data-parallel tail of a lazy step (segmm_adamw_table_lazy_rows): the listed rows -- those of ALL ranks, known only after the
+// row exchange -- replay the g = 0 steps old + 1 .. T - 1 from the ring and then take step T with their gradient row and step T's
+// own scalars (adamw_table_rows_kernel's), in one pass over the row: p, m, v are read once and written once, where catch-up +
+// phase 1 + stamp read and write them twice in three launches on the exposed end of the step.  The same shape, one wave per list
+// entry and four floats per lane; the claim is made with T itself, so no flags are involved: a duplicate entry, or a row already
+// at T, is neither loaded nor stored.  The gradient vector is loaded ahead of the replay: nothing needs it before the dependent
+// sqrt / divide chain of the replayed steps has run, which hides its latency (at a gap of 0 it travels with p, m, v in one round).
+// EMA: after step T the shadow's lerp with w_T -- read from the ring's entry of T, which adamw_hist_push_kernel<true> wrote on
+// this stream ahead of this launch.
+template <bool SCALED, bool EMA>
+__global__ __launch_bounds__(256) void adamw_table_lazy_rows_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                    float* __restrict__ v, float* __restrict__ shadow, long long n_rows, int w4,
+                                                                    const long long* __restrict__ ids, int n_ids, int* __restrict__ stamps,
+                                                                    const AdamwHist* __restrict__ hist, int cap, int T, float lr, float b1, float b2,
+                                                                    float eps, float wd, float bc1, float bc2_sqrt, const StepState* live,
+                                                                    const float* __restrict__ coef, float lr_scale) {
+    const StepScalars sc = step_scalars(lr, bc1, bc2_sqrt, T, live);
+    const StepRate r = step_rate(sc.lr, lr_scale, sc.bc1);
+    T = sc.t;
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (k >= n_ids) return;
     const long long id = ids[k];
     if (id < 0 || id >= n_rows) return;
-    int old = T;
-    if (lane == 0) old = atomicMax(stamps + id, T);
-    old = __builtin_amdgcn_readfirstlane(old);
+    const int old = row_claim(stamps, id, T, true, lane);
     if (old >= T) return;          // another entry of the list holds the same id and has taken the row, or the row was stepped already
-    const float w_T = hist[(unsigned)T % (unsigned)cap].pad_;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    float w_T = 0.f;
+    if constexpr (EMA) w_T = hist[(unsigned)T % (unsigned)cap].ema_w;
     for (int c = lane; c < w4; c += 64) {
         const long long i = id * w4 + c;
         const f32x4 graw = ((const f32x4*)g)[i];
-        f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], ss = ((f32x4*)shadow)[i];
-        int slot = (int)((unsigned)(old + 1) % (unsigned)cap);
-        for (int s = old + 1; s < T; ++s) {
-            const AdamwHist h = hist[slot];
-            slot = slot + 1 == cap ? 0 : slot + 1;
-            const float lr_s = h.lr * lr_scale;
-            const float step_s = lr_s / h.bc1;
-            adamw_elem4(pp, zero, mm, vv, lr_s, b1, b2, eps, wd, step_s, h.bc2_sqrt);
-            ss = ema_lerp(ss, pp, h.pad_);
-        }
-        adamw_elem4(pp, adamw_grad4<SCALED>(graw, coef), mm, vv, lr, b1, b2, eps, wd, step, bc2_sqrt);
-        ss = ema_lerp(ss, pp, w_T);
-        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv; ((f32x4*)shadow)[i] = ss;
+        f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i], ss = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (EMA) ss = ((f32x4*)shadow)[i];
+        adamw_replay4<EMA>(pp, mm, vv, ss, hist, cap, old + 1, T, lr_scale, b1, b2, eps, wd);
+        adamw_elem4(pp, adamw_grad4<SCALED>(graw, coef), mm, vv, r.lr, b1, b2, eps, wd, r.step, sc.bc2_sqrt);
+        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+        if constexpr (EMA) { ss = ema_lerp(ss, pp, w_T); ((f32x4*)shadow)[i] = ss; }
     }
 }
 

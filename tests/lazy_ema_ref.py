@@ -1,6 +1,6 @@
 """The lazy exact AdamW protocol WITH the weight average (lazy_tables=dict(ema=True)) restated on the host in numpy float32:
 ``lazy_table_ref.LazyTable`` plus a shadow per row and the step's EMA weight w_t in the ring's fourth float (csrc/rowops.h
-adamw_table_catchup_ema_kernel / adamw_table_lazy_rows_ema_kernel).  Every AdamW element update is ``adamw_ref.emul32``'s, every
+adamw_table_catchup_kernel<true> / adamw_table_lazy_rows_kernel<SCALED, true>).  Every AdamW element update is ``adamw_ref.emul32``'s, every
 lerp ``ema_ref.lerp``'s, so the statement to check is again one of ORDER: a row that takes its g = 0 steps late takes the lerps of
 those steps late too, each behind its own AdamW step and with its own step's weight, and then holds the bits of the shadow that
 was averaged over the dense table after every step.
